@@ -11,6 +11,7 @@ d=32) column-panel sharded over all ranks with one RCCL broadcast per panel (str
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus N ...        # starts N ranks itself (torch.distributed.run) when WORLD_SIZE is unset
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py ... --dump-outputs DIR  # rank 0's results of the last timed step as DIR/<name>.npy (float64)
 """
 import argparse
 import hashlib
@@ -138,6 +139,15 @@ def cpu_baseline(N, d, kernel, full=True, gpu_lml=None):
         "lml_grad_value": 1.0 / t_grad,
         "lml_grad_sample": f"oracle LML+grad measured at N={Ng} ({t_grad_meas:.1f}s), scaled by (N/{Ng})^3 -> {t_grad:.0f}s per eval",
     }
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one float64 DIR/<name>.npy per array.  The inputs
+    (synth_problem seed 0, theta_sequence) are fixed by the arguments, so two builds can be compared file for file; every
+    array is a scalar or a d-vector, far below a 64 MB cap."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray(a, dtype=np.float64))
 
 
 # ------------------------------------------------------------------------------------------------ launching ranks
@@ -352,6 +362,9 @@ def main():
                          "(tests/test_gpu_distributed.py); its timings say nothing about the links")
     ap.add_argument("--chains-per-gpu", type=int, default=3,
                     help="extra record: this many handles evaluated side by side on every GPU (independent chains; 0/1: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's results of the last timed step to DIR/<name>.npy (float64): lml, and with --grad-steps "
+                         "the last LML + gradient evaluation (lml_grad_value, lml_grad_gradient)")
     args = ap.parse_args()
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -405,6 +418,8 @@ def main():
             if "error" in rec:
                 print(json.dumps({"metric": "gp_lml_evals_per_s", "value": None, "n_gpus": world, "sharded": rec}), flush=True)
             else:
+                if args.dump_outputs:
+                    dump_outputs(args.dump_outputs, {"lml": rec["lml"]})
                 print(json.dumps(as_line(rec)), flush=True)
         dist.barrier()
         dist.destroy_process_group()
@@ -437,6 +452,7 @@ def main():
 
     # LML + gradient (the MAP loop of BASELINE config 3 and every NUTS leapfrog step): same handle, same thetas
     grad_rec = None
+    outputs = {"lml": vals[-1]}
     if want_grad:
         gp.lml_grad(thetas[0])
         torch.cuda.synchronize(dev)
@@ -451,6 +467,7 @@ def main():
         tg = torch.tensor([time.perf_counter() - tg], dtype=torch.float64, device=dev)
         dist.all_reduce(tg, op=dist.ReduceOp.MAX)
         tg = float(tg.item()) / ng
+        outputs["lml_grad_value"], outputs["lml_grad_gradient"] = v, g
         grad_rec = {"lml_grad_evals_per_s": world / tg, "ms_per_eval": tg * 1e3, "steps": ng,
                     "algorithmic_flops": "N^3 (factor N^3/3 + L^-T N^3/3 + K^-1 = U U^T N^3/3)",
                     "tflops_whole_eval": N ** 3 / tg * 1e-12, "frac_of_fp64_peak": N ** 3 / tg * 1e-12 / FP64_PEAK_TFLOPS}
@@ -664,6 +681,8 @@ def main():
     if rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, d, args.kernel, full=not args.cpu_baseline_sample, gpu_lml=gpu_ref_lml)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
     if exit_code:
         # a rank whose sharded step failed must not walk into the final barrier: its peers may be stuck inside the
