@@ -109,6 +109,8 @@ def load():
     lib.mi_gp_predict.argtypes = [vp, vp, ci, vp, cl, vp, vp, ci]
     lib.mi_gp_predict_u.argtypes = [vp, vp, ci, vp, cl, vp, vp, ci]
     lib.mi_gp_predict_grad.argtypes = [vp, vp, ci, vp, cl, vp, vp, ci, vp, vp]
+    lib.mi_gp_factor_batch.argtypes = [vp, ci, dp, ip]
+    lib.mi_gp_predict_batch.argtypes = [vp, ci, vp, ci, vp, cl, cl, vp, vp, ci, vp, vp]
     lib.mi_gp_set_option.argtypes = [vp, ci, ci]
     lib.mi_gp_get_option.argtypes = [vp, ci, ip]
     lib.mi_gp_set_profiling.argtypes = [vp, ci]
@@ -165,6 +167,8 @@ EXPORTS = [
     "mi_gp_predict",
     "mi_gp_predict_u",
     "mi_gp_predict_grad",
+    "mi_gp_factor_batch",
+    "mi_gp_predict_batch",
     "mi_gp_set_option",
     "mi_gp_get_option",
     "mi_gp_set_profiling",

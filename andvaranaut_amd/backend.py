@@ -195,6 +195,100 @@ class MiGP:
         self.batch_info = info
         return out, grad
 
+    # ------------------------------------------------------------------ batched conditional (posterior predictive)
+    def factor_batch(self, thetas):
+        """Factorise k covariances in the conditional form (mi_gp_factor_batch), one theta each, in one lockstep evaluation.
+        Returns the (k,) info array (0, or the 1-based first bad pivot).  The factors stay in the batch buffers for
+        predict_batch; the single-evaluation factor is gone, so a later predict() refactorises."""
+        th = self._thetas(thetas)
+        k = th.shape[0]
+        self._ensure_batch(k, False)
+        self._factored_ok = False
+        self._u_theta_ok = False
+        self._pred_count = 0
+        if self._bad_data:
+            raise FloatingPointError("the last update_data carried non-finite values: nothing to factorise")
+        info = np.zeros(k, dtype=np.int32)
+        dpt, ipt = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        self._check(self.lib.mi_gp_factor_batch(self.h, k, th.ctypes.data_as(dpt), info.ctypes.data_as(ipt)), "mi_gp_factor_batch")
+        self.batch_info = info
+        return info
+
+    def predict_batch_capacity(self, m):
+        """Draws that one factor_batch + predict_batch call holds for chunks of m points: K_p, its leaf inverses, the
+        work block and the moments per draw against 80 % of the device's free memory (sized like the NUTS batch)."""
+        mp = (min(int(m), 1 << 30) + 127) // 128 * 128
+        have = getattr(self, "_batch_k", 0)
+        per = ((self.np_ + 128) * self.lda + (self.np_ // 128 + 4) * 128 * 128 + mp * self.lda + 2 * mp) * 8
+        if getattr(self, "_batch_grad", False):
+            per += 2 * self.np_ * self.lda * 8  # (_ensure_batch grows U and K^-1 with K once they exist)
+        free, _total = torch.cuda.mem_get_info(self.dev)
+        held = have * per  # (buffers this handle holds already are reused, not added)
+        return max(1, int((0.8 * free + held) // per))
+
+    def predict_batch(self, thetas, Xnew, pred_noise=True, mixture=True, chunk=16384, max_batch=None):
+        """Posterior mean / variance at Xnew under each of k hyper-parameter vectors (mi_gp_factor_batch +
+        mi_gp_predict_batch): row p equals factor(thetas[p]) + predict(thetas[p], Xnew) bit for bit; rows of draws whose
+        covariance is not positive definite are NaN (``self.batch_info``).  Chunked over draws by batch capacity (or
+        ``max_batch``) and over points by ``chunk``.  Returns (means[k, m], vars[k, m]) and, with ``mixture``, also the
+        equal-weight mixture (mix_mean[m], mix_var[m]) over the positive-definite draws: each draw-chunk's mixture
+        comes from the device, chunks are combined here in chunk order (law of total variance)."""
+        th = self._thetas(thetas)
+        k = th.shape[0]
+        Xnew = np.ascontiguousarray(Xnew, dtype=np.float64)
+        if Xnew.ndim != 2 or Xnew.shape[1] != self.d:
+            raise ValueError("Xnew must be (m, d)")
+        m = Xnew.shape[0]
+        chunk = max(1, int(chunk))
+        cap = self.predict_batch_capacity(min(chunk, m))
+        if max_batch is not None:
+            cap = max(1, min(cap, int(max_batch)))
+        means = np.empty((k, m))
+        vars_ = np.empty((k, m))
+        info_all = np.zeros(k, dtype=np.int32)
+        parts = []  # per draw-chunk: (positive-definite draws, mixture mean, mixture variance)
+        with torch.cuda.device(self.dev):
+            for b0 in range(0, k, cap):
+                kc = min(cap, k - b0)
+                info = self.factor_batch(th[b0 : b0 + kc])
+                info_all[b0 : b0 + kc] = info
+                mix_m, mix_v = np.empty(m), np.empty(m)
+                for s in range(0, m, chunk):
+                    mc = min(chunk, m - s)
+                    mp = (mc + 127) // 128 * 128
+                    work = getattr(self, "_bwork", None)
+                    if work is None or work.numel() < kc * mp * self.lda:
+                        self._bwork = None
+                        self._bwork = torch.empty(kc * mp * self.lda, dtype=torch.float64, device=self.dev)
+                        work = self._bwork
+                    xn = torch.from_numpy(Xnew[s : s + mc]).to(self.dev)
+                    out = torch.empty((2 * kc + 2, mc), dtype=torch.float64, device=self.dev)
+                    torch.cuda.synchronize(self.dev)
+                    mix = (out[2 * kc].data_ptr(), out[2 * kc + 1].data_ptr()) if mixture else (None, None)
+                    self._check(self.lib.mi_gp_predict_batch(self.h, kc, xn.data_ptr(), mc, work.data_ptr(), self.lda, mp * self.lda,
+                                                             out[0].data_ptr(), out[kc].data_ptr(), 1 if pred_noise else 0, *mix),
+                                "mi_gp_predict_batch")
+                    o = out.cpu().numpy()
+                    means[b0 : b0 + kc, s : s + mc] = o[:kc]
+                    vars_[b0 : b0 + kc, s : s + mc] = o[kc : 2 * kc]
+                    if mixture:
+                        mix_m[s : s + mc], mix_v[s : s + mc] = o[2 * kc], o[2 * kc + 1]
+                parts.append((int(np.count_nonzero(info == 0)), mix_m, mix_v))
+        self.batch_info = info_all
+        if not mixture:
+            return means, vars_
+        parts = [p for p in parts if p[0] > 0]
+        if not parts:
+            return means, vars_, np.full(m, np.nan), np.full(m, np.nan)
+        if len(parts) == 1:
+            return means, vars_, parts[0][1], parts[0][2]
+        # (relative to the first chunk's moments, as the device sums: chunks that all agree return those moments exactly)
+        tot = sum(c for c, _, _ in parts)
+        m0, v0 = parts[0][1], parts[0][2]
+        mu = m0 + sum(c * (pm - m0) for c, pm, _ in parts) / tot
+        var = v0 + sum(c * (pv - v0 + (pm - mu) ** 2) for c, pm, pv in parts) / tot
+        return means, vars_, mu, var
+
     def lml_grad_data(self, theta, want_x=True):
         """(LML, dLML/dtheta, dLML/dy, dLML/dX) -- the data-side gradients drive the chain rule through
         warps (cwgp / iwgp) and free input rows (inverse_opt).  dLML/dX is None unless want_x."""
@@ -428,7 +522,7 @@ class MiGP:
             self.lib.mi_gp_destroy(self.h)  # synchronises the handle's streams first
             self.h = None
         # the device buffers the handle borrowed (a batch holds K-fold copies of K, U, K^-1)
-        for name in ("_bK", "_bZ", "_bW", "K_t", "Z_t", "W_t", "_work", "_work2", "_gx_t", "_pin_io"):
+        for name in ("_bK", "_bZ", "_bW", "_bwork", "K_t", "Z_t", "W_t", "_work", "_work2", "_gx_t", "_pin_io"):
             if hasattr(self, name):
                 setattr(self, name, None)
         self._batch_k = 0

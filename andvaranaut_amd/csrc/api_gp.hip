@@ -115,6 +115,9 @@ struct mi_gp_handle {
   int* b_info_dev;
   double* b_lr_part_dev;
   unsigned* b_lr_sync_dev;
+  int b_cond_k;            // problems whose conditional factors (L_p, beta_p, leaf inverses) the last batch call left in the batch
+                           // buffers: mi_gp_factor_batch sets it, every other batch call, mi_gp_set_batch / _set_data / _set_diag and
+                           // a single evaluation into the batch's K clear it (0)
   bool factored;
   bool have_u;             // Z_dev holds U = L^-T and alpha_dev = K^-1 y of the last mi_gp_factor (mi_gp_predict_grad)
   bool have_kinv;          // W_dev holds K^-1 (lower) and alpha_dev = K^-1 y of the last mi_gp_lml_grad
@@ -321,6 +324,7 @@ extern "C" int mi_gp_set_data(mi_gp_handle* h, const mi_gp_buffers* b) {
   }
   h->buf = *b;
   h->have_data = true;
+  h->b_cond_k = 0;
   return 0;
 }
 
@@ -1122,6 +1126,11 @@ static int factor_internal(mi_gp_handle* h, const double* theta, int what) {
   h->have_kinv = false;
   h->have_u = false;
   if (!h->have_data) { snprintf(h->err, sizeof(h->err), "mi_gp_set_data has not been called"); return -1; }
+  if (h->b_cond_k > 0) {  // (a caller may let the single K_dev alias one of the batch's: this evaluation then overwrites that factor)
+    const char *s0 = (const char*)h->buf.K_dev, *s1 = s0 + sizeof(double) * (size_t)(h->np + 128) * h->buf.lda;
+    const char *b0 = (const char*)h->bbuf.K_dev, *b1 = b0 + sizeof(double) * (size_t)h->bbuf.count * h->bbuf.stride_k;
+    if (s0 < b1 && b0 < s1) h->b_cond_k = 0;
+  }
   HCK(hipSetDevice(h->device), "hipSetDevice");
   for (int i = 0; i < h->ntheta; ++i) {
     if (!std::isfinite(theta[i])) { snprintf(h->err, sizeof(h->err), "theta[%d] is not finite", i); return -1; }
@@ -1196,14 +1205,17 @@ extern "C" int mi_gp_timers(mi_gp_handle* h, double* out, int n) {
 // U = L^-T (upper triangular, row-major in Z_dev) by leaf solves + level-batched block doubling:
 //   [[L11, 0], [L21, L22]]^-T = [[U11, -U11 L21^T U22], [0, U22]]
 // then Kinv = U U^T (lower tiles, W_dev), alpha = U beta, and the contraction kernel.
+// single_form: a batched launch takes the tile form (64x64 / 128x128) that the same product of ONE problem takes -- a rule of the
+// shape, not of the batch size (gemm_uses_small_tiles counts tiles x batch)
 static hipError_t gemm_call(mi_gp_handle* h, int ak, int bk, const double* A, long lda, long sA, const double* B, long ldb,
                             long sB, double* C, long ldc, long sC, int mt, int nt, int k, int tri, int kmode,
-                            double alpha, double beta, int batch, long zA = 0, long zB = 0, long zC = 0) {
+                            double alpha, double beta, int batch, long zA = 0, long zB = 0, long zC = 0, bool single_form = false) {
   GemmParams p;
   p.A = A; p.B = B; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.strideA = sA; p.strideB = sB; p.strideC = sC;
   p.mt = mt; p.nt = nt; p.k = k; p.tri = tri; p.kmode = kmode; p.alpha = alpha; p.beta = beta;
   p.small_below = h->small_below; p.band = h->band_rows; p.tail_small = h->tail_small;
+  if (h->btp && single_form) p.small_below = gemm_uses_small_tiles(p, batch) ? 0x7fffffff : 0;
   if (h->btp) {  // batched evaluation: the problems are the second batch level (zA / zB / zC: the strides of the matrices A, B, C live in)
     p.batch1 = batch;
     p.strideA2 = zA; p.strideB2 = zB; p.strideC2 = zC;
@@ -1365,6 +1377,7 @@ extern "C" int mi_gp_set_diag(mi_gp_handle* h, const double* diag_dev) {
   h->diag_dev = diag_dev;
   h->factored = false;
   h->have_kinv = false;
+  h->b_cond_k = 0;
   return 0;
 }
 
@@ -1410,10 +1423,22 @@ extern "C" int mi_gp_set_batch(mi_gp_handle* h, const mi_gp_batch_buffers* b) {
     h->batch_cap = b->count;
   }
   h->bbuf = *b;
+  h->b_cond_k = 0;
   return 0;
 }
 
-// what: 0 LML, 2 LML + gradient.  info_out[p]: 0, or the 1-based index of problem p's first bad pivot (its LML is -inf then).
+// strides of a batch of k problems in the batch buffers / scratch (h->bt; swork is the caller's, mi_gp_predict_batch)
+static void set_batch_strides(mi_gp_handle* h, int k) {
+  h->bt = Batch();
+  h->bt.nb = k;
+  h->bt.sK = h->bbuf.stride_k; h->bt.sZ = h->bt.sW = h->bbuf.stride_zw;
+  h->bt.sdinv = (long)MINV_ELEMS * (h->ntc + 4); h->bt.salpha = h->np;
+  h->bt.spart = (long)grad_contract_blocks(h->n) * h->ntheta;
+  h->bt.stheta = h->ntheta; h->bt.sinfo = 4; h->bt.sout = 16;
+}
+
+// what: 0 LML, 1 the conditional's factors (mi_gp_factor_batch: they stay in the batch buffers), 2 LML + gradient.
+// info_out[p]: 0, or the 1-based index of problem p's first bad pivot (its LML is -inf then).  lml_out may be null.
 static int batch_internal(mi_gp_handle* h, int k, const double* thetas, int what, double* lml_out, double* grad_out, int* info_out) {
   if (!h->have_data || h->batch_cap < 1) { snprintf(h->err, sizeof(h->err), "call mi_gp_set_data and mi_gp_set_batch first"); return -1; }
   if (k < 1 || k > h->bbuf.count) { snprintf(h->err, sizeof(h->err), "batch of %d problems, buffers for %d", k, h->bbuf.count); return -1; }
@@ -1424,6 +1449,7 @@ static int batch_internal(mi_gp_handle* h, int k, const double* thetas, int what
     h->b_theta_host[i] = thetas[i];
   }
   h->factored = h->have_kinv = h->have_u = false;  // the single-evaluation state of the handle is not touched, but K_dev may alias
+  h->b_cond_k = 0;
   // point the evaluation at the batch's arrays, run the ordinary enqueue code with blockIdx.z = problem, restore
   const mi_gp_buffers buf0 = h->buf;
   double *theta_dev0 = h->theta_dev, *dinv0 = h->dinv_dev, *alpha0 = h->alpha_dev, *part0 = h->part_dev, *grad0 = h->grad_host,
@@ -1435,11 +1461,7 @@ static int batch_internal(mi_gp_handle* h, int k, const double* thetas, int what
   h->buf.K_dev = h->bbuf.K_dev; h->buf.Z_dev = h->bbuf.Z_dev; h->buf.W_dev = h->bbuf.W_dev;
   h->theta_dev = h->b_theta_dev; h->dinv_dev = h->b_dinv_dev; h->alpha_dev = h->b_alpha_dev; h->part_dev = h->b_part_dev;
   h->grad_host = h->b_grad_host; h->out_host = h->b_out_host; h->theta_host = h->b_theta_host; h->info_dev = h->b_info_dev;
-  h->bt.nb = k;
-  h->bt.sK = h->bbuf.stride_k; h->bt.sZ = h->bt.sW = h->bbuf.stride_zw;
-  h->bt.sdinv = (long)MINV_ELEMS * (h->ntc + 4); h->bt.salpha = h->np;
-  h->bt.spart = (long)grad_contract_blocks(h->n) * h->ntheta;
-  h->bt.stheta = h->ntheta; h->bt.sinfo = 4; h->bt.sout = 16;
+  set_batch_strides(h, k);
   h->btp = &h->bt;
   const int prof0 = h->prof_level;
   h->prof_level = 0;
@@ -1471,10 +1493,11 @@ static int batch_internal(mi_gp_handle* h, int k, const double* thetas, int what
     const int info = (int)h->b_out_host[16 * p + 3];
     const bool ok = info == 0x7f7f7f7f;
     if (info_out) info_out[p] = ok ? 0 : info;
-    lml_out[p] = ok ? h->b_out_host[16 * p] : -INFINITY;
+    if (lml_out) lml_out[p] = ok ? h->b_out_host[16 * p] : -INFINITY;
     if (grad_out)
       for (int i = 0; i < h->ntheta; ++i) grad_out[(size_t)p * h->ntheta + i] = ok ? h->b_grad_host[(size_t)p * h->ntheta + i] : 0.0;
   }
+  if (what == 1) h->b_cond_k = k;
   return 0;
 }
 
@@ -1496,19 +1519,21 @@ extern "C" int mi_gp_factor(mi_gp_handle* h, const double* theta) {
   return r;
 }
 
-// solve X L^T = B in place for tile columns [c0, c0+w) of the mp x np work matrix
+// solve X L^T = B in place for tile columns [c0, c0+w) of the mp x np work matrix (a batch, h->btp: every problem's, work
+// blocks bt.swork apart, L_p and its leaf inverses in the batch buffers; the GEMMs take the single problem's tile form)
 static hipError_t trsm_rec(mi_gp_handle* h, double* Bw, long ldw, int mp, int c0, int w) {
   const double* L = h->buf.K_dev;
   const long lda = h->buf.lda;
+  const long zW = h->btp ? h->btp->swork : 0, zK = h->btp ? h->btp->sK : 0;
   if (w == 1) {
-    return launch_trsm_strip128(h->dinv_dev + (size_t)c0 * MINV_ELEMS, Bw + (long)c0 * 128, ldw, mp, h->stream);
+    return launch_trsm_strip128(h->dinv_dev + (size_t)c0 * MINV_ELEMS, Bw + (long)c0 * 128, ldw, mp, h->stream, h->btp, zW);
   }
   const int w1 = w / 2, w2 = w - w1;
   hipError_t e = trsm_rec(h, Bw, ldw, mp, c0, w1);
   if (e != hipSuccess) return e;
   // B[:, c0+w1 : c0+w) -= X[:, c0 : c0+w1) * L[c0+w1 : c0+w, c0 : c0+w1)^T
   e = gemm_call(h, 0, 0, Bw + (long)c0 * 128, ldw, 0, L + (long)(c0 + w1) * 128 * lda + (long)c0 * 128, lda, 0,
-                Bw + (long)(c0 + w1) * 128, ldw, 0, mp / 128, w2, w1 * 128, 0, 0, -1.0, 1.0, 1);
+                Bw + (long)(c0 + w1) * 128, ldw, 0, mp / 128, w2, w1 * 128, 0, 0, -1.0, 1.0, 1, zW, zK, zW, true);
   if (e != hipSuccess) return e;
   return trsm_rec(h, Bw, ldw, mp, c0 + w1, w2);
 }
@@ -1532,6 +1557,76 @@ extern "C" int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, dou
   const double sg = std::sqrt(th[nk * d + 2 * nk]);
   HCK(launch_predict_reduce(work_dev, ldw, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, m, kd,
                             pred_noise ? sg * sg : 0.0, mean_dev, var_dev, h->stream), "predict_reduce");
+  HCK(hipStreamSynchronize(h->stream), "stream sync");
+  return 0;
+}
+
+// ---------------------------------------------------------------- batched conditional
+// The posterior predictive over k hyper-parameter draws: k conditional-form factorisations in lockstep (batch_internal, what = 1,
+// the kernels of mi_gp_factor with blockIdx.z = problem), then mi_gp_predict's three steps -- cross-covariance, blocked
+// triangular solve, reduction -- for all k problems in the same launches.  Problem p's rows are mi_gp_factor(theta_p) +
+// mi_gp_predict's bits: same kernels, same per-element arithmetic, and the solve's GEMMs take the single problem's tile form.
+extern "C" int mi_gp_factor_batch(mi_gp_handle* h, int k, const double* thetas, int* info_out) {
+  if (!h) return -1;
+  if (k < 1 || !thetas) { snprintf(h->err, sizeof(h->err), "mi_gp_factor_batch: k >= 1 and thetas are required"); return -1; }
+  return batch_internal(h, k, thetas, 1, nullptr, nullptr, info_out);
+}
+
+extern "C" int mi_gp_predict_batch(mi_gp_handle* h, int k, const double* Xnew_dev, int m, double* work_dev, long ldw,
+                                   long stride_work, double* mean_dev, double* var_dev, int pred_noise, double* mix_mean_dev,
+                                   double* mix_var_dev) {
+  if (!h) return -1;
+  if (k < 1 || !Xnew_dev || !work_dev || !mean_dev || !var_dev || m <= 0) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_predict_batch: k >= 1, m >= 1 and the point / work / output buffers are required");
+    return -1;
+  }
+  if (!mix_mean_dev != !mix_var_dev) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_predict_batch: mix_mean_dev and mix_var_dev go together (both or neither)");
+    return -1;
+  }
+  if (h->b_cond_k < 1) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_predict_batch: mi_gp_factor_batch must be the last batch call");
+    return -1;
+  }
+  if (k != h->b_cond_k) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_predict_batch: %d problems, the last mi_gp_factor_batch factorised %d", k, h->b_cond_k);
+    return -1;
+  }
+  const int mp = (m + 127) / 128 * 128;
+  if (ldw < h->np || (ldw & 1)) { snprintf(h->err, sizeof(h->err), "mi_gp_predict_batch: ldw must be even and >= padded n"); return -1; }
+  if (stride_work < (long)mp * ldw || (stride_work & 1)) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_predict_batch: stride_work must be even and >= ceil(m/128)*128 * ldw = %ld", (long)mp * ldw);
+    return -1;
+  }
+  HCK(hipSetDevice(h->device), "hipSetDevice");
+  // point the solve at the batch's factors (as batch_internal does), run the single-problem code with blockIdx.z = problem, restore
+  const mi_gp_buffers buf0 = h->buf;
+  double* dinv0 = h->dinv_dev;
+  h->buf.K_dev = h->bbuf.K_dev;
+  h->dinv_dev = h->b_dinv_dev;
+  set_batch_strides(h, k);
+  h->bt.swork = stride_work;
+  h->btp = &h->bt;
+  Batch bw = h->bt;
+  bw.sK = stride_work;  // (the assembly writes the cross-covariance blocks: its output stride is the work blocks')
+  hipError_t e = launch_assemble(h->spec, h->b_theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, mp, h->np, 0, 0, h->stream,
+                                 -2147483647 - 1, nullptr, &bw);
+  const char* where = "assemble cross";
+  if (e == hipSuccess) { e = trsm_rec(h, work_dev, ldw, mp, 0, h->ntc); where = "trsm"; }
+  if (e == hipSuccess) {
+    e = launch_predict_reduce_batched(h->spec, h->b_theta_dev, work_dev, ldw, h->buf.K_dev + (long)h->np * h->buf.lda, h->b_info_dev,
+                                      h->n, m, pred_noise ? 1 : 0, mean_dev, var_dev, h->stream, h->bt);
+    where = "predict_reduce";
+  }
+  if (e == hipSuccess && mix_mean_dev) {
+    e = launch_mixture_moments(mean_dev, var_dev, m, k, h->b_info_dev, h->bt.sinfo, mix_mean_dev, mix_var_dev, h->stream);
+    where = "mixture";
+  }
+  h->btp = nullptr;
+  h->bt = Batch();
+  h->buf = buf0;
+  h->dinv_dev = dinv0;
+  if (e != hipSuccess) return hfail(h, e, where);
   HCK(hipStreamSynchronize(h->stream), "stream sync");
   return 0;
 }

@@ -594,16 +594,12 @@ __global__ void grad_final_kernel(const double* __restrict__ part, int nblk, int
   }
 }
 
-// mean[i] = A_i . beta ; var[i] = kdiag - |A_i|^2 (+ noise), one wave per prediction point
-__global__ __launch_bounds__(256) void predict_reduce_kernel(const double* __restrict__ A, long lda,
-                                                             const double* __restrict__ beta, int n, int m,
-                                                             double kdiag, double noise, double* __restrict__ mean,
-                                                             double* __restrict__ var) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= m) return;
-  const double* a = A + (long)row * lda;
-  double s1 = 0.0, s2 = 0.0;
+// s1 = A_i . beta, s2 = |A_i|^2 of one row, one wave: lane-strided partial sums, then a wave64 tree (every entry point that
+// predicts reduces its rows through this one sequence, so a batched row has the bits of a single one)
+__device__ __forceinline__ void predict_row_sums(const double* __restrict__ a, const double* __restrict__ beta, int n, int lane,
+                                                 double& s1, double& s2) {
+  s1 = 0.0;
+  s2 = 0.0;
   for (int k = lane; k < n; k += 64) {
     const double v = a[k];
     s1 += v * beta[k];
@@ -613,10 +609,101 @@ __global__ __launch_bounds__(256) void predict_reduce_kernel(const double* __res
     s1 += __shfl_down(s1, off, 64);
     s2 += __shfl_down(s2, off, 64);
   }
+}
+
+// mean[i] = A_i . beta ; var[i] = kdiag - |A_i|^2 (+ noise), one wave per prediction point
+__global__ __launch_bounds__(256) void predict_reduce_kernel(const double* __restrict__ A, long lda,
+                                                             const double* __restrict__ beta, int n, int m,
+                                                             double kdiag, double noise, double* __restrict__ mean,
+                                                             double* __restrict__ var) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= m) return;
+  double s1, s2;
+  predict_row_sums(A + (long)row * lda, beta, n, lane, s1, s2);
   if (lane == 0) {
     mean[row] = s1;
     var[row] = kdiag - s2 + noise;
   }
+}
+
+// The prior diagonal and the predictive noise of one theta, as mi_gp_predict folds them on the host: Stationary.diag == 1, so
+// the composite diagonal is the +/* fold of kv; the noise is sqrt(gv)^2.  Contraction off: the host has no FMA here, and
+// kd * kv_c + kv_(c+1) fused would be another rounding.
+__device__ __forceinline__ void prior_diag_noise(const KernSpec& spec, const double* __restrict__ th, int pred_noise, double& kd,
+                                                 double& noise) {
+#pragma clang fp contract(off)
+  const int nk = spec.nkern, d = spec.d;
+  kd = th[nk * d];
+  for (int c = 1; c < nk; ++c) kd = (spec.op[c - 1] == 0) ? kd + th[nk * d + c] : kd * th[nk * d + c];
+  noise = 0.0;
+  if (pred_noise) {
+    const double sg = sqrt(th[nk * d + 2 * nk]);  // (correctly rounded, as std::sqrt on the host)
+    noise = sg * sg;
+  }
+}
+
+// predict_reduce_kernel for problem blockIdx.z of a batch (mi_gp_predict_batch); rows of a problem without a positive-definite
+// factor are NaN
+__global__ __launch_bounds__(256) void predict_reduce_batch_kernel(KernSpec spec, const double* __restrict__ theta, int stheta,
+                                                                   const double* __restrict__ A, long lda, long sA,
+                                                                   const double* __restrict__ beta, long sbeta,
+                                                                   const int* __restrict__ info, int sinfo, int n, int m,
+                                                                   int pred_noise, double* __restrict__ mean,
+                                                                   double* __restrict__ var) {
+  const int z = blockIdx.z;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= m) return;
+  mean += (long)z * m;
+  var += (long)z * m;
+  if (info[(long)z * sinfo] != INFO_OK) {
+    if (lane == 0) mean[row] = var[row] = __builtin_nan("");
+    return;
+  }
+  double s1, s2;
+  predict_row_sums(A + (long)z * sA + (long)row * lda, beta + (long)z * sbeta, n, lane, s1, s2);
+  if (lane == 0) {
+    double kd, noise;
+    prior_diag_noise(spec, theta + (long)z * stheta, pred_noise, kd, noise);
+    mean[row] = s1;
+    var[row] = kd - s2 + noise;
+  }
+}
+
+// Equal-weight mixture of the k problems' moments at each point, one thread per point: two passes over the problems in index
+// order (the bits do not depend on the launch), the sums taken relative to the first member's moments -- the same quantities,
+// no cancellation in the sums, and draws that all agree return that draw's moments exactly.  Reads 3 k m doubles (the means
+// twice), writes 2 m: bandwidth-bound; the threads of a wave read consecutive points of one problem.
+__global__ __launch_bounds__(256) void mixture_moments_kernel(const double* __restrict__ mean, const double* __restrict__ var,
+                                                              int m, int k, const int* __restrict__ info, int sinfo,
+                                                              double* __restrict__ mix_mean, double* __restrict__ mix_var) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  int cnt = 0, p0 = -1;
+  double mu0 = 0.0, s = 0.0;
+  for (int p = 0; p < k; ++p)
+    if (info[(long)p * sinfo] == INFO_OK) {
+      const double v = mean[(long)p * m + i];
+      if (p0 < 0) { p0 = p; mu0 = v; }
+      s += v - mu0;
+      ++cnt;
+    }
+  if (cnt == 0) {
+    mix_mean[i] = mix_var[i] = __builtin_nan("");
+    return;
+  }
+  const double mu = mu0 + s / cnt;
+  const double v0 = var[(long)p0 * m + i];
+  double sv = 0.0, sd = 0.0;
+  for (int p = p0; p < k; ++p)
+    if (info[(long)p * sinfo] == INFO_OK) {
+      const double dl = mean[(long)p * m + i] - mu;
+      sv += var[(long)p * m + i] - v0;
+      sd += dl * dl;
+    }
+  mix_mean[i] = mu;
+  mix_var[i] = v0 + sv / cnt + sd / cnt;
 }
 
 hipError_t launch_set_identity_blocks(double* U, long ld, int nblocks, hipStream_t stream, const Batch* bt) {
@@ -887,6 +974,20 @@ hipError_t launch_grad_x(const KernSpec& spec, const double* theta, const double
 hipError_t launch_predict_reduce(const double* A, long lda, const double* beta, int n, int m, double kdiag,
                                  double noise, double* mean, double* var, hipStream_t stream) {
   predict_reduce_kernel<<<(m + 3) / 4, 256, 0, stream>>>(A, lda, beta, n, m, kdiag, noise, mean, var);
+  return hipGetLastError();
+}
+
+hipError_t launch_predict_reduce_batched(const KernSpec& spec, const double* theta, const double* A, long lda, const double* beta,
+                                         const int* info, int n, int m, int pred_noise, double* mean, double* var,
+                                         hipStream_t stream, const Batch& bt) {
+  predict_reduce_batch_kernel<<<dim3((m + 3) / 4, 1, bt.nb), 256, 0, stream>>>(spec, theta, bt.stheta, A, lda, bt.swork, beta, bt.sK,
+                                                                              info, bt.sinfo, n, m, pred_noise, mean, var);
+  return hipGetLastError();
+}
+
+hipError_t launch_mixture_moments(const double* mean, const double* var, int m, int k, const int* info, int sinfo,
+                                  double* mix_mean, double* mix_var, hipStream_t stream) {
+  mixture_moments_kernel<<<(m + 255) / 256, 256, 0, stream>>>(mean, var, m, k, info, sinfo, mix_mean, mix_var);
   return hipGetLastError();
 }
 

@@ -16,6 +16,7 @@ struct Batch {
   int stheta = 0;               // ... theta vectors (device copy, pinned host source, pinned gradient)
   int sinfo = 0;                // ... bad-pivot words (ints)
   int sout = 0;                 // ... scalar records in pinned host memory (doubles)
+  long swork = 0;               // ... prediction work blocks (mi_gp_predict_batch: K(X*, X) -> L^-1 K(X, X*), one per problem)
 };
 
 // ---------------------------------------------------------------- gemm_f64.hip
@@ -188,6 +189,18 @@ hipError_t launch_predict_grad(const KernSpec& spec, const double* theta, const 
                                hipStream_t stream);
 hipError_t launch_predict_reduce(const double* A, long lda, const double* beta, int n, int m, double kdiag,
                                  double noise, double* mean, double* var, hipStream_t stream);
+// batched form (mi_gp_predict_batch, blockIdx.z = problem z): A + z * bt->swork, beta + z * bt->sK, theta + z * bt->stheta; kdiag
+// and the noise come from problem z's own theta (the host fold of mi_gp_predict, same operations); mean / var rows z * m ..;
+// a problem whose bad-pivot word info[z * bt->sinfo] is not INFO_OK gets NaN rows
+constexpr int INFO_OK = 0x7f7f7f7f;  // the bad-pivot word of a positive-definite factorisation (set_yrows_kernel's reset value)
+hipError_t launch_predict_reduce_batched(const KernSpec& spec, const double* theta, const double* A, long lda, const double* beta,
+                                         const int* info, int n, int m, int pred_noise, double* mean, double* var,
+                                         hipStream_t stream, const Batch& bt);
+// equal-weight mixture over the problems whose bad-pivot word is INFO_OK, point by point, problems summed in index order:
+// mix_mean = sum mean_p / K', mix_var = sum var_p / K' + sum (mean_p - mix_mean)^2 / K' (NaN where K' = 0); the sums run
+// relative to the first member's moments (draws that all agree return its moments exactly)
+hipError_t launch_mixture_moments(const double* mean, const double* var, int m, int k, const int* info, int sinfo,
+                                  double* mix_mean, double* mix_var, hipStream_t stream);
 
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)

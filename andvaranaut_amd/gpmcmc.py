@@ -739,12 +739,105 @@ class GPMCMC(ConsumersMixin):
             y, yv = self.__gh_stats(x, y, yv, normvar, deg, EI=EI, EIopt=EIopt)
         return (y, yv) if return_var else y
 
+    @staticmethod
+    def _draw_indices(total, ndraws):
+        """Indices of ``ndraws`` evenly spaced draws among ``total`` (all of them for None or ndraws >= total)."""
+        if ndraws is None or int(ndraws) >= total:
+            return np.arange(total)
+        if int(ndraws) < 1:
+            raise ValueError("ndraws must be >= 1 (or None for all draws)")
+        return (np.arange(int(ndraws)) * total) // int(ndraws)
+
+    def _posterior_thetas(self, data, ndraws, jitter):
+        """C-ABI theta of every selected draw of an MCMC trace: draws flattened chain-major, then evenly spaced."""
+        post = data.posterior
+        warps = sorted(name for name in post if "wgp" in name)
+        if warps:
+            raise ValueError(f"predict_posterior: the trace carries warp parameters {warps}; per-draw warps change the converted "
+                             "data themselves and are not supported (predict with the extracted hypers instead)")
+        for name in ("l", "kv") + (("gv",) if self.noise else ()):
+            if name not in post:
+                raise ValueError(f"predict_posterior: the trace has no '{name}' draws (fit(method='mcmc_*', return_data=True))")
+        flat = {name: np.asarray(v).reshape((-1,) + np.shape(v)[2:]) for name, v in post.items()}
+        total = len(flat["l"])
+        idx = self._draw_indices(total, ndraws)
+        thetas = np.array([self._theta_from_hypers({name: v[i] for name, v in flat.items()}, jitter) for i in idx])
+        return thetas, idx
+
+    def predict_posterior(self, x, data, ndraws=100, return_var=False, convert=True, revert=True, normvar=False, jitter=1e-6,
+                          EI=False, EIopt=None, deg=8):
+        """Posterior predictive over the MCMC hyper-parameter draws of ``data`` (the trace of fit(method='mcmc_*',
+        return_data=True)): the equal-weight mixture of the conditionals at ``ndraws`` evenly spaced draws (chain-major;
+        None: all), computed in lockstep batches on the device (MiGP.predict_batch).  The arguments are predict()'s.
+        revert=False: the mixture's mean / variance in converted space.  revert=True: each draw's conditional is reverted by
+        Gauss-Hermite quadrature as predict() does (draw by draw); mean = average of the draws' reverted means (EI=True: their EI),
+        variance = average of the draws' reverted second moments - mean^2 (summed as the law of total variance: average
+        variance + variance of the means).  Draws whose covariance is not positive definite are dropped and counted in
+        ``self.posterior_info``; none left raises FloatingPointError.  One distinct draw reproduces predict() at its hypers: the
+        unreverted moments bit for bit where predict() takes the triangular solve (not U = L^-T, MiGP.predict), the reverted
+        ones to rounding."""
+        if self._ensure_gp() is None or self.m is None:
+            raise Exception("Error: fit the GP before predicting")
+        thetas, idx = self._posterior_thetas(data, ndraws, jitter)
+        if convert:
+            xarg = np.zeros_like(x)
+            for i in range(self.nx):
+                xarg[:, i] = self.xconrevs[i].con(x[:, i])
+        else:
+            xarg = copy.deepcopy(x)
+            x = copy.deepcopy(x)
+            for i in range(self.nx):
+                x[:, i] = self.xconrevs[i].rev(x[:, i])
+        if self.verbose:
+            print(f"Predicting over {len(thetas)} posterior draws...")
+        t0 = stopwatch()
+        mu, var, mix_mu, mix_var = self.gp.predict_batch(thetas, xarg, pred_noise=True, mixture=True)
+        ok = np.asarray(self.gp.batch_info) == 0
+        self.posterior_info = {"draws": idx, "used": int(ok.sum()), "failed": int((~ok).sum()),
+                               "failed_draws": idx[~ok], "info": np.asarray(self.gp.batch_info).copy()}
+        if self.verbose:
+            print(f"Time taken: {stopwatch() - t0:0.2f} s")
+            if not ok.all():
+                print(f"{int((~ok).sum())} of {len(ok)} draws dropped: covariance not positive definite")
+        if not ok.any():
+            raise FloatingPointError("predict_posterior: no draw has a positive-definite covariance")
+        if not revert:
+            y, yv = mix_mu.reshape((-1, 1)), mix_var.reshape((-1, 1))
+            return (y, yv) if return_var else y
+        # the quadrature draw by draw, vectorised over the points as in predict(): the rounding of a BLAS product can depend on its
+        # row count, and the variance's cancellation (second moment - mean^2) would turn that into more than rounding
+        means = self._mean_at(x)
+        gh = [self._gh_moments(means, mu[p].reshape((-1, 1)), var[p].reshape((-1, 1)), deg, EI=EI, EIopt=EIopt)
+              for p in np.flatnonzero(ok)]
+        ym, ym2 = np.array([a for a, _ in gh]), np.array([b for _, b in gh])
+        # averages relative to the first draw's values (the device mixture's form): one distinct draw returns predict()'s numbers
+        yv = ym2 - ym ** 2
+        yout = ym[0] + (ym - ym[0]).mean(axis=0)
+        yvout = yv[0] + (yv - yv[0]).mean(axis=0) + ((ym - yout) ** 2).mean(axis=0)
+        yout, yvout = yout.reshape((-1, 1)), yvout.reshape((-1, 1))
+        if normvar:
+            yvout = yvout / np.power(yout, 2)
+        return (yout, yvout) if return_var else yout
+
     def __gh_stats(self, x, y, yv, normvar=True, deg=8, EI=False, EIopt=None):
         """Gauss-Hermite mean / variance (or EI) of the reverted variable (gpmcmc.py:545-569),
         vectorised over the prediction points instead of the reference's per-point Python loop."""
+        ymean, ym2 = self._gh_moments(self._mean_at(x), y, yv, deg, EI, EIopt)
+        yout = ymean.reshape((-1, 1))
+        yvout = (ym2 - ymean ** 2).reshape((-1, 1))
+        if normvar:
+            yvout = yvout / np.power(yout, 2)
+        return yout, yvout
+
+    def _mean_at(self, x):
+        """The mean function at every row of x (0.0 for the zero mean)."""
+        return np.array([self.mean(x[i, :])[0] for i in range(len(x))]) if self.mean != self.zero_mean else 0.0
+
+    def _gh_moments(self, means, y, yv, deg=8, EI=False, EIopt=None):
+        """First moment (or EI) and second moment of the reverted variable per row, by Gauss-Hermite quadrature of the
+        converted-space normal N(y, yv); ``means``: the mean function per row (or 0.0)."""
         xi, wi = np.polynomial.hermite.hermgauss(deg)
         yi = np.sqrt(2.0 * yv) * xi[None, :] + y  # [M, deg]
-        means = np.array([self.mean(x[i, :])[0] for i in range(len(x))]) if self.mean != self.zero_mean else 0.0
         yir = self.yconrevs[0].rev(yi) + np.reshape(means, (-1, 1) if np.ndim(means) else ())
         if EI:
             ydiff = (yir - self.yopt) if EIopt == "max" else (self.yopt - yir)
@@ -753,11 +846,7 @@ class GPMCMC(ConsumersMixin):
             first = yir
         ymean = (first @ wi) / np.sqrt(np.pi)
         ym2 = ((yir ** 2) @ wi) / np.sqrt(np.pi)
-        yout = ymean.reshape((-1, 1))
-        yvout = (ym2 - ymean ** 2).reshape((-1, 1))
-        if normvar:
-            yvout = yvout / np.power(yout, 2)
-        return yout, yvout
+        return ymean, ym2
 
     def __del__(self):
         try:

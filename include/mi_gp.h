@@ -138,6 +138,26 @@ MI_GP_API int mi_gp_predict_u(mi_gp_handle* h, const double* Xnew_dev, int m, do
 MI_GP_API int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw, double* mean_dev,
                        double* var_dev, int pred_noise, double* dmean_dev, double* dvar_dev);
 
+/* Posterior predictive over k hyper-parameter draws (the MCMC draws of GPMCMC.fit(method='mcmc_*'); PyMC's gp.conditional +
+ * sample_posterior_predictive), on the buffers of mi_gp_set_batch (k <= count):
+ *   mi_gp_factor_batch   factorises k covariances in the conditional form, one theta each (what mi_gp_factor does, k problems in
+ *                        lockstep) and keeps every problem's L_p, beta_p = L_p^-1 y and leaf inverses in the batch buffers.
+ *                        info_out[p] (optional): 0, or the 1-based index of problem p's first non-positive pivot.  Like the other
+ *                        batch calls it invalidates the handle's single-evaluation state.
+ *   mi_gp_predict_batch  per problem p: A_p = L_p^-1 K_p(X, X*), mean_dev[p*m + i] = A_p,i . beta_p, var_dev[p*m + i] =
+ *                        kdiag_p - |A_p,i|^2 (+ gv_p if pred_noise) -- bit for bit what mi_gp_factor(theta_p) + mi_gp_predict
+ *                        return.  Rows of a problem whose info was non-zero are NaN.  mix_mean_dev / mix_var_dev (optional, both
+ *                        or neither; m doubles each): the equal-weight mixture over the K' problems with info 0,
+ *                        mix_mean = sum mean_p / K', mix_var = sum var_p / K' + sum (mean_p - mix_mean)^2 / K' (two passes,
+ *                        problems in index order, sums relative to the first member's moments: K' equal draws return that
+ *                        draw's moments exactly; NaN if K' = 0).  work_dev holds k blocks of ceil(m/128)*128 rows x ldw,
+ *                        stride_work elements apart (even, >= ceil(m/128)*128 * ldw).  Returns -1 unless mi_gp_factor_batch with
+ *                        the same k was the last batch call (mi_gp_set_batch, mi_gp_set_data and mi_gp_set_diag also end it).
+ * Xnew_dev, mean_dev, var_dev and the mixture outputs are device-visible addresses as for mi_gp_predict. */
+MI_GP_API int mi_gp_factor_batch(mi_gp_handle* h, int k, const double* thetas_host, int* info_out);
+MI_GP_API int mi_gp_predict_batch(mi_gp_handle* h, int k, const double* Xnew_dev, int m, double* work_dev, long ldw, long stride_work,
+                                  double* mean_dev, double* var_dev, int pred_noise, double* mix_mean_dev, double* mix_var_dev);
+
 /* tuning knobs (benchmarks / A-B tests), ALL per handle -- nothing here is process-wide:
  *   0  look-ahead: factor the next super-panel on a second stream while the trailing update runs; 0 never, 1 by size
  *      (default: from 20 tile columns = N > 2432 on, where the overlap beats the cross-stream hand-offs -- and from 4 tile
