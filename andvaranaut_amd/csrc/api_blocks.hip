@@ -29,11 +29,24 @@ static int ensure_init() {
   return 0;
 }
 
+// Arguments of mi_gp_gemm_f64 / _tuned (include/mi_gp.h): nullptr if the product is one the kernels cover, else the reason.
+// A tile's k range under kmode 1-4 starts or ends at its own row / column tile (128 or 64 rows): it stays inside [0, k) and is
+// never empty exactly when the triangular operand is square or longer in k -- k >= n (kmode 1, 4), k >= m (kmode 2, 3).
+// k = 0 is refused: the 128x128-tile kernel's epilogue always consumes its last two chunks (gemm_f64.hip).
+static const char* gemm_args_error(int m, int n, int k, long lda, long ldb, int kmode) {
+  if (m % 128 || n % 128 || k % 32 || m <= 0 || n <= 0 || k <= 0 || (lda & 1) || (ldb & 1))
+    return "m,n must be multiples of 128, k a positive multiple of 32, lda/ldb even";
+  if (kmode < 0 || kmode > 4) return "kmode must be 0..4";
+  if ((kmode == 1 || kmode == 4) && k < n) return "kmode 1 and 4 need k >= n";
+  if ((kmode == 2 || kmode == 3) && k < m) return "kmode 2 and 3 need k >= m";
+  return nullptr;
+}
+
 extern "C" int mi_gp_gemm_f64(int transa, int transb, int m, int n, int k, double alpha, const double* A, long lda,
                               const double* B, long ldb, double beta, double* C, long ldc, int tri, int kmode,
                               int batch, long strideA, long strideB, long strideC, void* stream) {
-  if (m % 128 || n % 128 || k % 32 || m <= 0 || n <= 0 || k < 0 || (lda & 1) || (ldb & 1)) {
-    snprintf(g_err, sizeof(g_err), "mi_gp_gemm_f64: m,n must be multiples of 128, k of 32, lda/ldb even");
+  if (const char* why = gemm_args_error(m, n, k, lda, ldb, kmode)) {
+    snprintf(g_err, sizeof(g_err), "mi_gp_gemm_f64: %s", why);
     return -1;
   }
   if (int r = ensure_init()) return r;
@@ -54,8 +67,8 @@ extern "C" int mi_gp_gemm_f64(int transa, int transb, int m, int n, int k, doubl
 extern "C" int mi_gp_gemm_f64_tuned(int transa, int transb, int m, int n, int k, double alpha, const double* A, long lda,
                                     const double* B, long ldb, double beta, double* C, long ldc, int tri, int kmode,
                                     int small_below, int tail_small, int band, int one_per_cu, void* stream) {
-  if (m % 128 || n % 128 || k % 32 || m <= 0 || n <= 0 || k < 0 || (lda & 1) || (ldb & 1)) {
-    snprintf(g_err, sizeof(g_err), "mi_gp_gemm_f64_tuned: m,n must be multiples of 128, k of 32, lda/ldb even");
+  if (const char* why = gemm_args_error(m, n, k, lda, ldb, kmode)) {
+    snprintf(g_err, sizeof(g_err), "mi_gp_gemm_f64_tuned: %s", why);
     return -1;
   }
   if (int r = ensure_init()) return r;
@@ -92,17 +105,6 @@ extern "C" int mi_gp_gemm_nt_kseg(int m, int n, int k, double alpha, const doubl
 }
 
 // ---------------------------------------------------------------- distributed-matrix building blocks
-static KernSpec make_spec(int d, int nkern, const int* kernel_ids, const int* ops) {
-  KernSpec s;
-  s.nkern = nkern;
-  s.d = d;
-  for (int i = 0; i < MAX_KERN; ++i) {
-    s.kid[i] = i < nkern ? kernel_ids[i] : 0;
-    s.op[i] = i < nkern ? ops[i] : 0;
-  }
-  return s;
-}
-
 extern "C" int mi_gp_assemble_block(int d, int nkern, const int* kernel_ids, const int* ops, const double* theta_dev,
                                     const double* Xrows_dev, int nrows, const double* Xcols_dev, int ncols,
                                     int row0, int col0, double* K_dev, long ldk, int rows_pad, int cols_pad,
@@ -111,7 +113,11 @@ extern "C" int mi_gp_assemble_block(int d, int nkern, const int* kernel_ids, con
     snprintf(g_err, sizeof(g_err), "mi_gp_assemble_block: bad argument (pads multiples of 64, ldk even)");
     return -1;
   }
-  const KernSpec spec = make_spec(d, nkern, kernel_ids, ops);
+  if (const char* why = kern_spec_error(nkern, kernel_ids, ops)) {
+    snprintf(g_err, sizeof(g_err), "mi_gp_assemble_block: %s", why);
+    return -1;
+  }
+  const KernSpec spec = make_kern_spec(d, nkern, kernel_ids, ops);
   hipError_t e = launch_assemble(spec, theta_dev, Xrows_dev, nrows, Xcols_dev, ncols, K_dev, ldk, rows_pad, cols_pad, 0,
                                  noise_form, (hipStream_t)stream, row0 - col0);
   if (e != hipSuccess) return fail(e, "assemble_block");
@@ -162,9 +168,14 @@ extern "C" int mi_gp_chol_panel(double* A_dev, long lda, int row_tiles, int w_ti
   return 0;
 }
 
-// out[1] += sum log L_ii over n diagonal entries, out[2] += sum beta_i^2 (out[0] is scratch)
+// out[1] = sum log L_ii over n diagonal entries, out[2] = sum beta_i^2, out[0] = -n/2 log(2 pi) - out[2]/2 - out[1] (all
+// three overwritten; out[3..] untouched)
 extern "C" int mi_gp_lml_partial(const double* L_dev, long ld, const double* beta_dev, int n, double* out_dev,
                                  void* stream) {
+  if (!L_dev || !beta_dev || !out_dev || n <= 0) {
+    snprintf(g_err, sizeof(g_err), "mi_gp_lml_partial: bad argument (null buffer or n <= 0)");
+    return -1;
+  }
   hipError_t e = launch_lml_reduce(L_dev, ld, beta_dev, n, out_dev, (hipStream_t)stream);
   if (e != hipSuccess) return fail(e, "lml_partial");
   return 0;
@@ -232,7 +243,11 @@ extern "C" int mi_gp_grad_contract_block(int d, int nkern, const int* kernel_ids
     snprintf(g_err, sizeof(g_err), "mi_gp_grad_contract_block: scratch shorter than mi_gp_grad_contract_block_scratch()");
     return -1;
   }
-  const KernSpec spec = make_spec(d, nkern, kernel_ids, ops);
+  if (const char* why = kern_spec_error(nkern, kernel_ids, ops)) {
+    snprintf(g_err, sizeof(g_err), "mi_gp_grad_contract_block: %s", why);
+    return -1;
+  }
+  const KernSpec spec = make_kern_spec(d, nkern, kernel_ids, ops);
   hipError_t e = launch_grad_contract_slab(spec, theta_dev, X_dev, n, W_dev, ldw, row0, col0, cols, alpha_dev, part_dev,
                                            grad_dev, (hipStream_t)stream);
   if (e != hipSuccess) return fail(e, "grad_contract_block");

@@ -194,17 +194,16 @@ extern "C" int mi_gp_create(const mi_gp_config* cfg, mi_gp_handle** out) {
     set_global_error("mi_gp_create: n, d must be positive and 1 <= nkern <= 8");
     return -1;
   }
-  for (int i = 0; i < cfg->nkern; ++i)
-    if (cfg->kernel_ids[i] < 0 || cfg->kernel_ids[i] > KID_RATQUAD) { set_global_error("mi_gp_create: unknown kernel id"); return -1; }
+  if (const char* why = kern_spec_error(cfg->nkern, cfg->kernel_ids, cfg->ops)) {
+    char msg[128];
+    snprintf(msg, sizeof(msg), "mi_gp_create: %s", why);
+    set_global_error(msg);
+    return -1;
+  }
   mi_gp_handle* h = new mi_gp_handle();  // value-initialised: every pointer / stream / event starts null
   memset(h->err, 0, sizeof(h->err));
   h->cfg = *cfg;
-  h->spec.nkern = cfg->nkern;
-  h->spec.d = cfg->d;
-  for (int i = 0; i < MAX_KERN; ++i) {
-    h->spec.kid[i] = i < cfg->nkern ? cfg->kernel_ids[i] : 0;
-    h->spec.op[i] = i < cfg->nkern ? cfg->ops[i] : 0;
-  }
+  h->spec = make_kern_spec(cfg->d, cfg->nkern, cfg->kernel_ids, cfg->ops);
   h->n = cfg->n;
   h->np = (cfg->n + 127) / 128 * 128;
   h->ntc = h->np / 128;

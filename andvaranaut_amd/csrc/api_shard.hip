@@ -134,14 +134,13 @@ extern "C" int mi_gp_shard_create(const mi_gp_shard_config* cfg, mi_gp_shard** o
     snprintf(g_shard_err, sizeof(g_shard_err), "mi_gp_shard_create: bad argument (positive sizes, rank < world, even leading dimensions, no null buffers)");
     return -1;
   }
+  if (const char* why = kern_spec_error(cfg->nkern, cfg->kernel_ids, cfg->ops)) {
+    snprintf(g_shard_err, sizeof(g_shard_err), "mi_gp_shard_create: %s", why);
+    return -1;
+  }
   mi_gp_shard* s = new mi_gp_shard();
   s->cfg = *cfg;
-  s->spec.nkern = cfg->nkern;
-  s->spec.d = cfg->d;
-  for (int i = 0; i < MAX_KERN; ++i) {
-    s->spec.kid[i] = i < cfg->nkern ? cfg->kernel_ids[i] : 0;
-    s->spec.op[i] = i < cfg->nkern ? cfg->ops[i] : 0;
-  }
+  s->spec = make_kern_spec(cfg->d, cfg->nkern, cfg->kernel_ids, cfg->ops);
   s->np = (cfg->n + 127) / 128 * 128;
   s->ntc = s->np / 128;
   s->ntr = s->ntc + 1;

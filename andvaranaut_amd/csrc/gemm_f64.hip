@@ -207,8 +207,9 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
     if (p.fc > 0) tile_from_index_fc(p.mt, p.nt, p.fc, p.band, idx, ti, tj);
     else if (p.band > 0 && p.tri && p.kmode == 0) tile_from_index_banded(p, idx, p.band, ti, tj);
     else tile_from_index(p, idx, ti, tj);
-    if (p.kmode == 2) ti = p.mt - 1 - ti;
-    if (p.kmode == 4 && !p.tri) { tj = p.nt - 1 - idx / p.mt; ti = idx % p.mt; }  // longest-k columns first (LPT order)
+    // longest-k tiles first (LPT order); a triangular launch keeps its enumeration, which names only tiles on / below the diagonal
+    if (p.kmode == 2 && !p.tri) ti = p.mt - 1 - ti;
+    if (p.kmode == 4 && !p.tri) { tj = p.nt - 1 - idx / p.mt; ti = idx % p.mt; }
     rc = ti;
     cc = tj;
   }
@@ -507,7 +508,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
       tile_from_index(p, bid, ti, tj);
       if (p.dead_last_half && ti == p.mt - 1) return;
     }
-    if (p.kmode == 2) ti = p.mt - 1 - ti;
+    if (p.kmode == 2 && !p.tri) ti = p.mt - 1 - ti;  // as in the 128x128-tile kernel
     if (p.kmode == 4 && !p.tri) { tj = p.nt - 1 - (int)blockIdx.x / p.mt; ti = (int)blockIdx.x % p.mt; }  // longest-k columns first (LPT order)
     rc = ti;
     cc = tj;

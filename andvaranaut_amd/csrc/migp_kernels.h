@@ -140,6 +140,29 @@ struct KernSpec {
   int kid[MAX_KERN];
   int op[MAX_KERN];  // op[i] joins component i and i+1: 0 '+', 1 '*'
 };
+// Host-side check of a composition as the C-ABI receives it: nullptr if nkern components with ids kernel_ids[0 .. nkern)
+// joined by ops[0 .. nkern - 1) are a covariance the kernels evaluate, else the reason.  ops may be null for one component.
+inline const char* kern_spec_error(int nkern, const int* kernel_ids, const int* ops) {
+  if (nkern <= 0 || nkern > MAX_KERN) return "1 <= nkern <= 8";
+  if (!kernel_ids) return "null kernel_ids";
+  for (int i = 0; i < nkern; ++i)
+    if (kernel_ids[i] < KID_RBF || kernel_ids[i] > KID_RATQUAD) return "unknown kernel id";
+  if (nkern > 1 && !ops) return "null ops";
+  for (int i = 0; i + 1 < nkern; ++i)
+    if (ops[i] != 0 && ops[i] != 1) return "ops must be 0 ('+') or 1 ('*')";
+  return nullptr;
+}
+// the KernSpec of a composition that passed kern_spec_error (op[nkern - 1 ..] unused, set to 0)
+inline KernSpec make_kern_spec(int d, int nkern, const int* kernel_ids, const int* ops) {
+  KernSpec s;
+  s.nkern = nkern;
+  s.d = d;
+  for (int i = 0; i < MAX_KERN; ++i) {
+    s.kid[i] = i < nkern ? kernel_ids[i] : 0;
+    s.op[i] = i + 1 < nkern ? ops[i] : 0;
+  }
+  return s;
+}
 // sym=1: lower 64x64 tiles of K(X1,X1) + noise on the diagonal, identity in the padding;
 // sym=0: full K(X1,X2), zeros in the padding.  noise_form: 0 marginal, 1 conditional, 2 explicit.
 hipError_t launch_assemble(const KernSpec& spec, const double* theta, const double* X1, int n1, const double* X2,

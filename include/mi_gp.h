@@ -254,10 +254,13 @@ MI_GP_API int mi_gp_timers(mi_gp_handle* h, double* out, int n);
 /* ---- block-level operations (also used by the multi-GPU driver and the parity tests) ---- */
 
 /* C = beta*C + alpha*op(A)*op(B) in fp64 on v_mfma_f64_16x16x4_f64; row-major, m,n multiples of
- * 128, k multiple of 32.  transa=0: A is m x k; 1: A is k x m.  transb=0: B is k x n; 1: B is n x k.
+ * 128, k a positive multiple of 32.  transa=0: A is m x k; 1: A is k x m.  transb=0: B is k x n; 1: B is n x k.
  * tri=1 computes only tiles on/below the block diagonal (the element-wise lower triangle is
  * guaranteed, the strict upper part of diagonal blocks is unspecified); kmode restricts k per tile for triangular
- * operands (0 full, 1 k>=col-tile start, 2 k<row-tile end, 3 k>=row-tile start, 4 k<col-tile end).
+ * operands (0 full, 1 k>=col-tile start, 2 k<row-tile end, 3 k>=row-tile start, 4 k<col-tile end), i.e. it presumes
+ * op(B) lower (1), op(A) lower (2), op(A) upper (3) or op(B) upper (4) triangular in its leading square; the skipped
+ * k range must hold zeros.  kmode 1 and 4 need k >= n, 2 and 3 k >= m (the tile's k range then stays inside [0, k)).
+ * beta = 0 never reads C (NaN there does not propagate).  Anything else returns -1 before touching the device.
  * Replaces the OpenBLAS dgemm/dsyrk calls inside LAPACK dpotrf/dtrtri/dlauum that PyTensor's
  * Cholesky Op reaches (gpmcmc.py:313; scipy.linalg.cholesky). */
 MI_GP_API int mi_gp_gemm_f64(int transa, int transb, int m, int n, int k, double alpha, const double* A_dev, long lda,
@@ -282,7 +285,8 @@ MI_GP_API int mi_gp_gemm_nt_kseg(int m, int n, int k, double alpha, const double
 /* K(Xrows, Xcols) for one rectangular block of a (distributed) covariance: rows row0.. and columns
  * col0.. of the global matrix; noise + jitter go on the global diagonal, identity in the padding
  * (rows >= nrows / columns >= ncols of the padded block).  Same kernel as the single-GPU assembly
- * (gpmcmc.py:282-312). */
+ * (gpmcmc.py:282-312).  kernel_ids[0 .. nkern) must be MI_GP_* ids and ops[0 .. nkern-1) MI_GP_OP_* (ops may be null
+ * for one component), here, in mi_gp_grad_contract_block and in mi_gp_create / mi_gp_shard_create: else -1. */
 MI_GP_API int mi_gp_assemble_block(int d, int nkern, const int* kernel_ids, const int* ops, const double* theta_dev,
                          const double* Xrows_dev, int nrows, const double* Xcols_dev, int ncols, int row0, int col0,
                          double* K_dev, long ldk, int rows_pad, int cols_pad, int noise_form, void* hip_stream);
@@ -295,7 +299,8 @@ MI_GP_API int mi_gp_assemble_block(int d, int nkern, const int* kernel_ids, cons
 MI_GP_API int mi_gp_chol_panel(double* A_dev, long lda, int row_tiles, int w_tiles, double* dinv_dev, int* info_dev,
                      int col_base, void* hip_stream);
 
-/* out_dev[1] = sum_i log L[i][i], out_dev[2] = sum_i beta[i]^2 over n entries (one workgroup). */
+/* out_dev[1] = sum_i log L[i][i], out_dev[2] = sum_i beta[i]^2 over n >= 1 entries (one workgroup), and
+ * out_dev[0] = -n/2 log(2 pi) - out_dev[2]/2 - out_dev[1]: all three are overwritten, out_dev[3..] is not touched. */
 MI_GP_API int mi_gp_lml_partial(const double* L_dev, long ld, const double* beta_dev, int n, double* out_dev, void* hip_stream);
 
 /* ---- sharded gradient ("gradient at C4 scale needs distributed K^-1"): the reference gets dLML/dtheta from

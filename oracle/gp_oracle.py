@@ -236,6 +236,46 @@ def lml_grad(X, y, kerns, ops, theta, form="marginal"):
     return val, g
 
 
+def dK_dtheta(X, kerns, ops, theta):
+    """d K / d theta_p for every natural parameter p of the C-ABI layout: (ntheta, n, n), d/d gv and d/d jitter the identity.
+    Squared distances in the direct form sum_m ((x_im - x_jm) / l_m)^2 (the gradient kernels' form, not the expansion
+    square_dist uses), so that points on a dyadic grid with power-of-two length scales give them exactly.  Test
+    infrastructure for the block-level gradient contraction (mi_gp_grad_contract_block)."""
+    X = np.asarray(X, dtype=np.float64)
+    n, d = X.shape
+    nk = len(kerns)
+    ls, kv, alpha, _, _ = split_theta(theta, d, nk)
+    diffs, r2s, comps = [], [], []
+    for c in range(nk):
+        Xs = X * (1.0 / ls[c])
+        df = Xs[:, None, :] - Xs[None, :, :]
+        r2 = np.sum(df * df, axis=2)
+        diffs.append(df)
+        r2s.append(r2)
+        comps.append(kv[c] * base_kernel(kerns[c], r2, alpha[c]))
+    out = np.zeros((nk * d + 2 * nk + 2, n, n))
+    for c in range(nk):
+        coef = np.ones((n, n))  # d K / d K_c of the left-to-right fold
+        T = comps[0]
+        for i in range(1, nk):
+            if i == c:
+                coef = np.ones((n, n)) if ops[i - 1] == "+" else T.copy()
+            elif i > c and ops[i - 1] == "*":
+                coef = coef * comps[i]
+            T = T + comps[i] if ops[i - 1] == "+" else T * comps[i]
+        dk = kv[c] * base_kernel_dr2(kerns[c], r2s[c], alpha[c])
+        dk = np.where(r2s[c] > 0.0, dk, 0.0)
+        for m in range(d):
+            out[c * d + m] = coef * dk * (-2.0 * diffs[c][:, :, m] ** 2 / ls[c, m])
+        out[nk * d + c] = coef * comps[c] / kv[c]
+        if kerns[c] == "RatQuad":
+            u = 0.5 * r2s[c] / alpha[c]
+            out[nk * d + nk + c] = coef * comps[c] * (-np.log1p(u) + u / (1.0 + u))
+    out[nk * d + 2 * nk] = np.eye(n)
+    out[nk * d + 2 * nk + 1] = np.eye(n)
+    return out
+
+
 def lml_grad_data(X, y, kerns, ops, theta, form="marginal", extra_diag=None):
     """Data-side gradients of the LML: (LML, dLML/dy, dLML/dX).
         dLML/dy = -alpha,   dLML/dx_im = sum_j (alpha_i alpha_j - Kinv_ij) dK_ij/dx_im
