@@ -110,6 +110,8 @@ def load():
     lib.mi_gp_predict_u.argtypes = [vp, vp, ci, vp, cl, vp, vp, ci]
     lib.mi_gp_predict_grad.argtypes = [vp, vp, ci, vp, cl, vp, vp, ci, vp, vp]
     lib.mi_gp_factor_batch.argtypes = [vp, ci, dp, ip]
+    lib.mi_gp_reserve.argtypes = [vp, ci]
+    lib.mi_gp_append.argtypes = [vp, vp, vp, vp, ci, vp, cl]
     lib.mi_gp_predict_batch.argtypes = [vp, ci, vp, ci, vp, cl, cl, vp, vp, ci, vp, vp]
     lib.mi_gp_set_option.argtypes = [vp, ci, ci]
     lib.mi_gp_get_option.argtypes = [vp, ci, ip]
@@ -146,6 +148,8 @@ def load():
 
 # every symbol include/mi_gp.h declares (checked by tests/test_abi.py against the header text)
 EXPORTS = [
+    "mi_gp_reserve",
+    "mi_gp_append",
     "mi_gp_last_global_error",
     "mi_gp_last_error",
     "mi_gp_create",

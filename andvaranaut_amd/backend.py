@@ -35,7 +35,7 @@ def pack_theta(ls, kv, gv, jitter, alpha=None):
 class MiGP:
     """One GP data set + kernel structure bound to one MI355X and one HIP stream."""
 
-    def __init__(self, X, y, kernel="RBF", device=0, panel_tiles=0, need_grad=True):
+    def __init__(self, X, y, kernel="RBF", device=0, panel_tiles=0, need_grad=True, capacity=None):
         if not torch.cuda.is_available():
             raise RuntimeError("MiGP needs a ROCm GPU: the GP hot path has no CPU implementation")
         self.lib = _lib.load()
@@ -68,23 +68,73 @@ class MiGP:
         self.h = h
         self.np_ = int(self.lib.mi_gp_padded_n(h))
         self.ntheta = int(self.lib.mi_gp_num_theta(h))
-        # leading dimension: padded n plus 16 doubles so that column panels are not power-of-two strided
-        self.lda = self.np_ + 16
-        with torch.cuda.device(self.dev):
-            self.X_t = torch.from_numpy(X).to(self.dev)
-            self.y_t = torch.from_numpy(y).to(self.dev)
-            self.K_t = torch.empty((self.np_ + 128, self.lda), dtype=torch.float64, device=self.dev)
-            self.Z_t = self.W_t = None
-            if need_grad:
-                self.Z_t = torch.zeros((self.np_, self.lda), dtype=torch.float64, device=self.dev)
-                self.W_t = torch.zeros((self.np_, self.lda), dtype=torch.float64, device=self.dev)
-            torch.cuda.synchronize(self.dev)
+        self.need_grad = bool(need_grad)
+        self.append_refactors = 0  # capacity growths of append() (each one refactorises once)
+        self.capacity = None
+        if capacity is None:
+            # leading dimension: padded n plus 16 doubles so that column panels are not power-of-two strided
+            self.lda = self.np_ + 16
+            with torch.cuda.device(self.dev):
+                self.X_t = torch.from_numpy(X).to(self.dev)
+                self.y_t = torch.from_numpy(y).to(self.dev)
+                self.K_t = torch.empty((self.np_ + 128, self.lda), dtype=torch.float64, device=self.dev)
+                self.Z_t = self.W_t = None
+                if need_grad:
+                    self.Z_t = torch.zeros((self.np_, self.lda), dtype=torch.float64, device=self.dev)
+                    self.W_t = torch.zeros((self.np_, self.lda), dtype=torch.float64, device=self.dev)
+                torch.cuda.synchronize(self.dev)
+            self._bind()
+        else:
+            if int(capacity) < self.n:
+                raise ValueError(f"capacity {capacity} < n = {self.n}")
+            self._allocate(int(capacity), X, y, None)
+
+    def _bind(self):
         b = _lib.MiGpBuffers()
         b.X_dev, b.y_dev, b.K_dev = self.X_t.data_ptr(), self.y_t.data_ptr(), self.K_t.data_ptr()
         b.lda = self.lda
-        b.Z_dev = self.Z_t.data_ptr() if need_grad else None
-        b.W_dev = self.W_t.data_ptr() if need_grad else None
-        self._check(self.lib.mi_gp_set_data(h, ctypes.byref(b)), "mi_gp_set_data")
+        b.Z_dev = self.Z_t.data_ptr() if self.Z_t is not None else None
+        b.W_dev = self.W_t.data_ptr() if self.Z_t is not None else None
+        self._check(self.lib.mi_gp_set_data(self.h, ctypes.byref(b)), "mi_gp_set_data")
+
+    @staticmethod
+    def _padded(n):
+        return (int(n) + 127) // 128 * 128
+
+    def _allocate(self, capacity, X, y, diag):
+        """Buffers for up to `capacity` points (the first n hold X, y and the optional diagonal), bound to the handle with
+        mi_gp_set_data + mi_gp_reserve; X_t / y_t / _diag_t are views of the first n rows."""
+        cp = self._padded(capacity)
+        self.lda = cp + 16
+        with torch.cuda.device(self.dev):
+            self._X_store = torch.zeros((capacity, self.d), dtype=torch.float64, device=self.dev)
+            self._y_store = torch.zeros(capacity, dtype=torch.float64, device=self.dev)
+            self._X_store[: self.n].copy_(torch.as_tensor(X).to(self.dev))
+            self._y_store[: self.n].copy_(torch.as_tensor(y).to(self.dev))
+            self.K_t = None
+            self.K_t = torch.empty((cp + 128, self.lda), dtype=torch.float64, device=self.dev)
+            self.Z_t = self.W_t = None
+            if self.need_grad:
+                self.Z_t = torch.zeros((cp, self.lda), dtype=torch.float64, device=self.dev)
+                self.W_t = torch.zeros((cp, self.lda), dtype=torch.float64, device=self.dev)
+            self._diag_store = None
+            if diag is not None:
+                self._diag_store = torch.zeros(capacity, dtype=torch.float64, device=self.dev)
+                self._diag_store[: self.n].copy_(torch.as_tensor(diag).to(self.dev))
+            self._awork = None
+            torch.cuda.synchronize(self.dev)
+        self.capacity = capacity
+        self._views()
+        self._bind()
+        self._check(self.lib.mi_gp_reserve(self.h, capacity), "mi_gp_reserve")
+        if diag is not None:
+            self._check(self.lib.mi_gp_set_diag(self.h, self._diag_t.data_ptr()), "mi_gp_set_diag")
+
+    def _views(self):
+        self.X_t = self._X_store[: self.n]
+        self.y_t = self._y_store[: self.n]
+        if getattr(self, "_diag_store", None) is not None:
+            self._diag_t = self._diag_store[: self.n]
 
     def _check(self, r, what):
         if r < 0:
@@ -345,13 +395,18 @@ class MiGP:
         self._factored_ok = False
         with torch.cuda.device(self.dev):
             if diag is None:
-                self._diag_t = None
+                self._diag_t = self._diag_store = None
                 self._check(self.lib.mi_gp_set_diag(self.h, None), "mi_gp_set_diag")
                 return
             diag = np.ascontiguousarray(np.asarray(diag, dtype=np.float64).reshape(-1))
             if diag.shape != (self.n,):
                 raise ValueError("diag must have n entries")
-            self._diag_t = torch.from_numpy(diag).to(self.dev)
+            if self.capacity is None:
+                self._diag_t = torch.from_numpy(diag).to(self.dev)
+            else:  # (room for appended points: mi_gp_append writes their entries behind the first n)
+                self._diag_store = torch.zeros(self.capacity, dtype=torch.float64, device=self.dev)
+                self._diag_store[: self.n].copy_(torch.from_numpy(diag).to(self.dev))
+                self._diag_t = self._diag_store[: self.n]
             torch.cuda.synchronize(self.dev)
             self._check(self.lib.mi_gp_set_diag(self.h, self._diag_t.data_ptr()), "mi_gp_set_diag")
 
@@ -367,6 +422,78 @@ class MiGP:
         if self.info == 0:
             self._factored_ok, self._factored_theta = True, theta.copy()
         return self.info
+
+    APPEND_CHUNK = 128  # points per mi_gp_append call
+
+    def append(self, Xnew, ynew, diag=None):
+        """Condition the resident factorisation (the last successful factor(), conditional form) on new points at the same
+        theta (mi_gp_append, O(n^2 k) instead of an O(n^3) refactorisation), in chunks of 128 points.  ``diag``: the new
+        points' entries of the per-point diagonal, required exactly when one is set.  When the capacity is exhausted the
+        buffers grow about 1.5x and the handle is refactorised once at the factored theta (``append_refactors`` counts
+        these).  Returns 0, or the LAPACK-style info of a chunk whose block is not positive definite: that chunk and the
+        ones after it are not appended (``self.n`` says how many points are resident), the factor stays usable."""
+        Xnew = np.ascontiguousarray(np.atleast_2d(np.asarray(Xnew, dtype=np.float64)))
+        ynew = np.ascontiguousarray(np.asarray(ynew, dtype=np.float64).reshape(-1))
+        if Xnew.ndim != 2 or Xnew.shape[1] != self.d or Xnew.shape[0] != ynew.shape[0]:
+            raise ValueError("Xnew must be (k, d) and ynew (k,)")
+        if not (np.isfinite(Xnew).all() and np.isfinite(ynew).all()):
+            raise ValueError("Xnew and ynew must be finite")
+        has_diag = getattr(self, "_diag_t", None) is not None
+        if (diag is not None) != has_diag:
+            raise ValueError("diag must be given exactly when a per-point diagonal is set (set_diag)")
+        if diag is not None:
+            diag = np.ascontiguousarray(np.asarray(diag, dtype=np.float64).reshape(-1))
+            if diag.shape != ynew.shape or not np.isfinite(diag).all():
+                raise ValueError("diag must hold one finite entry per new point")
+        if not getattr(self, "_factored_ok", False) or self._bad_data:
+            raise RuntimeError("append() extends a factorisation: call factor() (or predict) first")
+        total = ynew.shape[0]
+        self.info = 0
+        for s in range(0, total, self.APPEND_CHUNK):
+            kc = min(self.APPEND_CHUNK, total - s)
+            if self.capacity is None or self.n + kc > self.capacity:
+                self._grow(max(self.n + total - s, int(np.ceil(1.5 * max(self.n, 1)))))
+            with torch.cuda.device(self.dev):
+                need = 4 * 128 * self.lda + 65600
+                if getattr(self, "_awork", None) is None or self._awork.numel() < need:
+                    self._awork = None
+                    self._awork = torch.empty(need, dtype=torch.float64, device=self.dev)
+                xn = torch.from_numpy(Xnew[s : s + kc]).to(self.dev)
+                yn = torch.from_numpy(ynew[s : s + kc]).to(self.dev)
+                dn = torch.from_numpy(diag[s : s + kc]).to(self.dev) if diag is not None else None
+                torch.cuda.synchronize(self.dev)
+                r = self._check(self.lib.mi_gp_append(self.h, xn.data_ptr(), yn.data_ptr(), dn.data_ptr() if dn is not None else None,
+                                                      kc, self._awork.data_ptr(), self.lda), "mi_gp_append")
+            if r != 0:
+                self.info = r
+                return r
+            self.n += kc
+            self.np_ = self._padded(self.n)
+            self._views()
+            self._gx_t = None  # (sized for n)
+            self._drop_batch()
+        return 0
+
+    def _drop_batch(self):
+        """The batch buffers were sized for the old n: the next batch call re-creates them (mi_gp_append ended the batch state)."""
+        self._bK = self._bZ = self._bW = self._bwork = None
+        self._batch_k = 0
+        self._batch_grad = False
+
+    def _grow(self, need):
+        """Re-allocate for at least `need` points (about 1.5x), rebind and refactorise once at the factored theta."""
+        theta = self._factored_theta.copy()
+        with torch.cuda.device(self.dev):
+            X = self.X_t.clone()
+            y = self.y_t.clone()
+            diag = self._diag_t.clone() if getattr(self, "_diag_t", None) is not None else None
+        self._drop_batch()
+        self._work = self._work2 = None
+        self._allocate(max(int(need), int(np.ceil(1.5 * self.n))), X, y, diag)
+        self.np_ = self._padded(self.n)
+        self.append_refactors += 1
+        if self.factor(theta) != 0:
+            raise FloatingPointError(f"covariance not positive definite at pivot {self.info} (refactorisation for append)")
 
     def _ensure_factored(self, theta):
         """Factorise unless the resident factor already belongs to this theta (BO sweeps, DE populations and
@@ -522,7 +649,8 @@ class MiGP:
             self.lib.mi_gp_destroy(self.h)  # synchronises the handle's streams first
             self.h = None
         # the device buffers the handle borrowed (a batch holds K-fold copies of K, U, K^-1)
-        for name in ("_bK", "_bZ", "_bW", "_bwork", "K_t", "Z_t", "W_t", "_work", "_work2", "_gx_t", "_pin_io"):
+        for name in ("_bK", "_bZ", "_bW", "_bwork", "K_t", "Z_t", "W_t", "_work", "_work2", "_gx_t", "_pin_io", "_awork", "_X_store",
+                     "_y_store", "_diag_store"):
             if hasattr(self, name):
                 setattr(self, name, None)
         self._batch_k = 0

@@ -181,15 +181,21 @@ class ConsumersMixin:
         return xout
 
     # ------------------------------------------------------------------ BO
-    def _bo_potential(self, method, opt_type, normvar, jitter):
+    def _bo_potential(self, method, opt_type, normvar, jitter, reuse_factor=False):
         """pm.Potential of BO's single-point model (gpmcmc.py:766-815) as x -> (value, gradient): the
-        Gauss-Hermite reverted mean (+-), the (normalised) variance, or the expected improvement."""
+        Gauss-Hermite reverted mean (+-), the (normalised) variance, or the expected improvement.  ``reuse_factor``: a
+        handle already factored at this theta keeps its factor (BO with refit_every > 1: it carries appended points that a
+        refactorisation would also see, but the resident factor is already theirs)."""
         import torch
 
         theta = self._theta_from_hypers(self.hypers, jitter)
         xi_np, wi_np = np.polynomial.hermite.hermgauss(8)
         xi, wi = torch.from_numpy(xi_np), torch.from_numpy(wi_np)
         state = {"fresh": True}
+        if reuse_factor:
+            gp = self._ensure_gp()
+            state["fresh"] = not (getattr(gp, "_factored_ok", False) and np.array_equal(np.asarray(theta, dtype=np.float64),
+                                                                                         gp._factored_theta))
         ycon = self.yconrevs[0]
 
         def potential(x):
@@ -226,10 +232,21 @@ class ConsumersMixin:
         return potential
 
     def BO(self, opt_type="min", opt_method="predict", fit_method="map", max_iter=16, method="EI", eps=0.1, iwgp=False,
-           cwgp=False, jitter=1e-6, conv=0.01, predict_samps=10000, normvar=True, refine=True, **kwargs):
+           cwgp=False, jitter=1e-6, conv=0.01, predict_samps=10000, normvar=True, refine=True, refit_every=1, **kwargs):
         """Bayesian optimisation loop of gpmcmc.py:601-906: propose (batched prediction over an LHC sample or
         differential evolution, optionally refined by a MAP on the differentiable single-point predictive, or a
-        MAP / MCMC on it alone), evaluate the target, refit, until the proposal stops moving."""
+        MAP / MCMC on it alone), evaluate the target, refit, until the proposal stops moving.
+
+        ``refit_every``: 1 (default) refits after every evaluated point, as the reference does.  r > 1 goes beyond the
+        reference: the hyper-parameters are refitted only at every r-th iteration (and the last one); in between the
+        resident GP is conditioned on the new point at the current hyper-parameters (MiGP.append, O(n^2) instead of a
+        fit and an O(n^3) refactorisation).  Not with iwgp / cwgp: their warp parameters belong to the fit and change the
+        converted data themselves."""
+        refit_every = int(refit_every)
+        if refit_every < 1:
+            raise ValueError("refit_every must be >= 1")
+        if refit_every > 1 and (iwgp or cwgp):
+            raise ValueError("refit_every > 1 is not supported with iwgp / cwgp (the warps are refitted with the hyper-parameters)")
         if self.ny > 1:
             raise Exception("Bayesian minimisation only implemented for single output")
         if opt_type == "max":
@@ -293,7 +310,7 @@ class ConsumersMixin:
                     self.verbose = verb
             if opt_method not in ("DE", "predict") or (opt_method == "predict" and refine):
                 imodel = InputModel([pymc_prior(p) for p in self.priors])
-                potential = self._bo_potential(method, opt_type, normvar, jitter)
+                potential = self._bo_potential(method, opt_type, normvar, jitter, reuse_factor=refit_every > 1)
                 roll = np.random.rand()
                 if method != "eps-RS" or roll > eps:
                     if opt_method == "map" or (opt_method == "predict" and refine):
@@ -324,6 +341,14 @@ class ConsumersMixin:
                 print(f"New sample is {ys + ym} at x point {xs}")
             self.xopt = self.x[xoptf(self.y[:, 0]), :]
             self.yopt = yoptf(self.y)
+            if refit_every > 1 and (it + 1) % refit_every != 0 and it != max_iter - 1:
+                # condition the resident GP on the new point at the current hyper-parameters (GPMCMC.predict's theta)
+                gp = self._ensure_gp()
+                gp._ensure_factored(self._theta_from_hypers(self.hypers, 1e-6))
+                xc_new, yc_new = self._converted(xs, ys - ym.reshape(len(xs), self.ny))
+                if gp.append(xc_new, yc_new) != 0:
+                    raise FloatingPointError(f"covariance not positive definite after appending {xs} (pivot {gp.info})")
+                continue
             if fit_method == "map":
                 try:
                     self.fit(method=fit_method, iwgp=iwgp, cwgp=cwgp, start=self.hypers)

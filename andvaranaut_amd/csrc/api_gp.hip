@@ -122,6 +122,9 @@ struct mi_gp_handle {
   bool have_u;             // Z_dev holds U = L^-T and alpha_dev = K^-1 y of the last mi_gp_factor (mi_gp_predict_grad)
   bool have_kinv;          // W_dev holds K^-1 (lower) and alpha_dev = K^-1 y of the last mi_gp_lml_grad
   const double* diag_dev;  // optional per-point diagonal added at assembly (mi_gp_set_diag)
+  int cap;                 // points the n-dependent scratch above is sized for (mi_gp_reserve; n until it is called)
+  size_t gxs_elems;        // doubles gxs_dev holds
+  double* app_stats_dev;   // [4] mi_gp_append's scalar increments and bad-pivot word
   char err[256];
 };
 
@@ -143,7 +146,7 @@ static void release_handle(mi_gp_handle* h) {
   if (h->pstream) (void)hipStreamSynchronize(h->pstream);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   (void)hipFree(h->theta_dev); (void)hipFree(h->dinv_dev); (void)hipFree(h->info_dev); (void)hipFree(h->sig_dev);
-  (void)hipFree(h->alpha_dev); (void)hipFree(h->part_dev); (void)hipFree(h->gxs_dev);
+  (void)hipFree(h->alpha_dev); (void)hipFree(h->part_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
   (void)hipFree(h->lr_part_dev); (void)hipFree(h->lr_sync_dev); (void)hipFree(h->b_lr_part_dev); (void)hipFree(h->b_lr_sync_dev);
   (void)hipFree(h->b_theta_dev); (void)hipFree(h->b_dinv_dev); (void)hipFree(h->b_alpha_dev); (void)hipFree(h->b_part_dev);
   (void)hipFree(h->b_info_dev);
@@ -215,6 +218,8 @@ extern "C" int mi_gp_create(const mi_gp_config* cfg, mi_gp_handle** out) {
   h->have_u = false;
   h->diag_dev = nullptr;
   h->gxs_dev = nullptr;
+  h->gxs_elems = 0;
+  h->cap = cfg->n;
   h->t_trtri_ms = h->t_lauum_ms = h->t_contract_ms = 0.0;
   h->t_gemm_big_ms = h->gemm_big_flops = h->n_gemm_big = 0.0;
   h->prof_level = 0;
@@ -1361,8 +1366,14 @@ extern "C" int mi_gp_grad_x(mi_gp_handle* h, double* gx_dev) {
   if (!h->have_kinv) { snprintf(h->err, sizeof(h->err), "mi_gp_grad_x: call mi_gp_lml_grad first"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
   const int nsplit = grad_x_splits(h->n, h->cfg.d);
-  if (nsplit > 1 && !h->gxs_dev)
-    HCK(hipMalloc(&h->gxs_dev, sizeof(double) * (size_t)nsplit * h->n * h->cfg.d), "grad_x scratch");
+  const size_t gxs_need = (size_t)nsplit * h->n * h->cfg.d;
+  if (nsplit > 1 && gxs_need > h->gxs_elems) {  // (grown by mi_gp_append: the handle's n is larger than at the first call)
+    (void)hipFree(h->gxs_dev);
+    h->gxs_dev = nullptr;
+    h->gxs_elems = 0;
+    HCK(hipMalloc(&h->gxs_dev, sizeof(double) * gxs_need), "grad_x scratch");
+    h->gxs_elems = gxs_need;
+  }
   HCK(launch_grad_x(h->spec, h->theta_dev, h->buf.X_dev, h->n, h->buf.W_dev, h->buf.lda, h->alpha_dev, gx_dev,
                     nsplit > 1 ? h->gxs_dev : nullptr, h->stream), "grad_x");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
@@ -1725,5 +1736,133 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
   HCK(launch_predict_grad(h->spec, h->theta_dev, h->buf.X_dev, h->n, Xnew_dev, m, h->alpha_dev, wrows, ldw, dmean_dev,
                           dvar_dev, h->stream), "predict_grad");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
+  return 0;
+}
+
+// ---------------------------------------------------------------- appending points at fixed theta
+// The handle's n-dependent scratch for up to `capacity` points; the resident contents (leaf inverses, alpha) are kept.
+extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
+  if (!h) { set_global_error("mi_gp_reserve: null handle"); return -1; }
+  if (capacity < h->n) { snprintf(h->err, sizeof(h->err), "mi_gp_reserve: capacity %d < n = %d", capacity, h->n); return -1; }
+  const int cap_np = (capacity + 127) / 128 * 128;
+  if (h->have_data && h->buf.lda < cap_np) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_reserve: lda %ld of mi_gp_set_data < padded capacity %d", h->buf.lda, cap_np);
+    return -1;
+  }
+  if (capacity <= h->cap) return 0;
+  HCK(hipSetDevice(h->device), "hipSetDevice");
+  HCK(hipStreamSynchronize(h->stream), "stream sync");
+  const int cap_ntc = cap_np / 128;
+  double *dinv = nullptr, *alpha = nullptr, *part = nullptr;
+  hipError_t e = hipMalloc(&dinv, sizeof(double) * MINV_ELEMS * (size_t)(cap_ntc + 4));
+  if (e == hipSuccess) e = hipMalloc(&alpha, sizeof(double) * cap_np);
+  if (e == hipSuccess) e = hipMalloc(&part, sizeof(double) * (size_t)grad_contract_blocks(capacity) * h->ntheta);
+  if (e == hipSuccess) e = hipMemcpy(dinv, h->dinv_dev, sizeof(double) * MINV_ELEMS * (size_t)h->ntc, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipMemcpy(alpha, h->alpha_dev, sizeof(double) * h->np, hipMemcpyDeviceToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(dinv); (void)hipFree(alpha); (void)hipFree(part);
+    return hfail(h, e, "mi_gp_reserve");
+  }
+  (void)hipFree(h->dinv_dev); (void)hipFree(h->alpha_dev); (void)hipFree(h->part_dev);
+  h->dinv_dev = dinv; h->alpha_dev = alpha; h->part_dev = part;
+  h->cap = capacity;
+  return 0;
+}
+
+// Conditional-form factor of n points -> n + k points at the same theta (Schur complement of the appended block):
+//   L21 = K21 L11^-T, S = K22 + noise - L21 L21^T = L22 L22^T, beta2 = L22^-1 (y2 - L21 beta1),
+//   logdet += sum log diag L22, quad += |beta2|^2; with U resident U12 = -U11 L21^T U22, U22 = L22^-T, alpha = U beta.
+// Everything up to the factor of S runs in the caller's work block: a non-positive-definite S leaves the handle untouched.
+// work_dev layout (R = 128 * ldw doubles): [0, R) L21 (then -L22^-1 L21 U11^T), [R, 2R) K21 (then L21 U11^T), [2R, 4R) the
+// k-segmented partial products of L21 L21^T, then the S block (2 * 16384), S's leaf inverse (16384) and L22^-1 row-major (16384).
+extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
+                            double* work_dev, long ldw) {
+  if (!h) { set_global_error("mi_gp_append: null handle"); return -1; }
+  if (!Xnew_dev || !ynew_dev || !work_dev) { snprintf(h->err, sizeof(h->err), "mi_gp_append: null point, value or work buffer"); return -1; }
+  if (k < 1 || k > 128) { snprintf(h->err, sizeof(h->err), "mi_gp_append: 1 <= k <= 128 (got %d)", k); return -1; }
+  if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_append: call mi_gp_factor first"); return -1; }
+  if (h->n + k > h->cap) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_append: n + k = %d exceeds the capacity %d (mi_gp_reserve)", h->n + k, h->cap);
+    return -1;
+  }
+  if (!diag_new_dev != !h->diag_dev) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_append: diag_new_dev must be given exactly when a diagonal is set (mi_gp_set_diag)");
+    return -1;
+  }
+  const int n = h->n, n2 = n + k;
+  const int np = h->np, ntc = h->ntc, np2 = (n2 + 127) / 128 * 128;
+  const long ld = h->buf.lda;
+  if (ldw < np2 || (ldw & 1)) { snprintf(h->err, sizeof(h->err), "mi_gp_append: ldw must be even and >= padded(n + k) = %d", np2); return -1; }
+  if (ld < np2) { snprintf(h->err, sizeof(h->err), "mi_gp_append: lda of mi_gp_set_data < padded(n + k) = %d", np2); return -1; }
+  HCK(hipSetDevice(h->device), "hipSetDevice");
+  if (!h->app_stats_dev) HCK(hipMalloc(&h->app_stats_dev, sizeof(double) * 4), "append scratch");
+  const long R = 128L * ldw;
+  double *L21 = work_dev, *W1 = work_dev + R, *parts = work_dev + 2 * R, *S = work_dev + 4 * R;
+  double *Sinv = S + 2 * MINV_ELEMS, *Linv22 = Sinv + MINV_ELEMS;
+  const hipStream_t st = h->stream;
+  const double* beta1 = h->buf.K_dev + (long)np * ld;
+  // ---- phase 1: scratch only
+  if (h->have_u) {  // L21 = K21 U11: one GEMM against the resident inverse (mi_gp_predict_u's route)
+    HCK(launch_assemble(h->spec, h->theta_dev, Xnew_dev, k, h->buf.X_dev, n, W1, ldw, 128, np, 0, 0, st), "assemble K21");
+    HCK(gemm_call(h, 0, 1, W1, ldw, 0, h->buf.Z_dev, ld, 0, L21, ldw, 0, 1, ntc, np, 0, 4, 1.0, 0.0, 1), "K21 U11");
+  } else {
+    HCK(launch_assemble(h->spec, h->theta_dev, Xnew_dev, k, h->buf.X_dev, n, L21, ldw, 128, np, 0, 0, st), "assemble K21");
+    HCK(trsm_rec(h, L21, ldw, 128, 0, ntc), "trsm L21");
+  }
+  // L21 L21^T in k segments of st_tiles tile columns (a single 128 x 128 output over k = n would run on 4 workgroups)
+  const int st_tiles = (ntc + 63) / 64, nfull = ntc / st_tiles, rem = ntc - nfull * st_tiles;
+  HCK(gemm_call(h, 0, 0, L21, ldw, st_tiles * 128L, L21, ldw, st_tiles * 128L, parts, 128, MINV_ELEMS, 1, 1, st_tiles * 128, 0, 0,
+                1.0, 0.0, nfull), "syrk segments");
+  if (rem > 0) {
+    const long off = (long)nfull * st_tiles * 128;
+    HCK(gemm_call(h, 0, 0, L21 + off, ldw, 0, L21 + off, ldw, 0, parts + (long)nfull * MINV_ELEMS, 128, 0, 1, 1, rem * 128, 0, 0,
+                  1.0, 0.0, 1), "syrk tail");
+  }
+  HCK(hipMemsetAsync(S, 0, sizeof(double) * 2 * MINV_ELEMS, st), "S clear");
+  HCK(launch_assemble(h->spec, h->theta_dev, Xnew_dev, k, Xnew_dev, k, S, 128, 128, 128, 1, 1, st, -2147483647 - 1, diag_new_dev),
+      "assemble K22");
+  HCK(launch_append_schur(S, parts, nfull + (rem > 0 ? 1 : 0), L21, ldw, beta1, np, ynew_dev, k, st), "schur");
+  HCK(hipMemsetAsync(h->info_dev, 0x7f, sizeof(int), st), "info reset");
+  HCK(launch_potrf_leaf128(S, 128, Sinv, n, h->info_dev, st, S + MINV_ELEMS), "leaf S");
+  HCK(launch_append_stats(S, k, h->info_dev, h->app_stats_dev, st), "append stats");
+  double stats[3];
+  HCK(hipMemcpyAsync(stats, h->app_stats_dev, sizeof(stats), hipMemcpyDeviceToHost, st), "stats download");
+  HCK(hipStreamSynchronize(st), "stream sync");
+  const int info = (int)stats[2];
+  if (info != INFO_OK) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_append: the appended block is not positive definite (pivot %d); the handle is unchanged", info);
+    return info;
+  }
+  // ---- phase 2: commit
+  HCK(hipMemcpyAsync(const_cast<double*>(h->buf.X_dev) + (long)n * h->cfg.d, Xnew_dev, sizeof(double) * k * h->cfg.d,
+                     hipMemcpyDeviceToDevice, st), "X rows");
+  HCK(hipMemcpyAsync(const_cast<double*>(h->buf.y_dev) + n, ynew_dev, sizeof(double) * k, hipMemcpyDeviceToDevice, st), "y rows");
+  if (h->diag_dev)
+    HCK(hipMemcpyAsync(const_cast<double*>(h->diag_dev) + n, diag_new_dev, sizeof(double) * k, hipMemcpyDeviceToDevice, st), "diag rows");
+  if (h->have_u)  // P = L21 U11^T (U11 upper: k >= column tile), read before U grows
+    HCK(gemm_call(h, 0, 0, L21, ldw, 0, h->buf.Z_dev, ld, 0, W1, ldw, 0, 1, ntc, np, 0, 1, 1.0, 0.0, 1), "L21 U11^T");
+  HCK(launch_append_commit(h->buf.K_dev, ld, n, k, np, np2, L21, ldw, S, st), "commit rows");
+  const int t0 = n / 128, t1 = (n2 - 1) / 128;
+  HCK(launch_tile_inverse_rows(h->buf.K_dev + (long)t0 * 128 * (ld + 1), ld, 128 * (ld + 1), h->dinv_dev + (size_t)t0 * MINV_ELEMS,
+                               MINV_ELEMS, n - t0 * 128, t1 - t0 + 1, 0, st), "leaf inverses");
+  if (h->have_u) {
+    HCK(launch_tile_inverse_rows(S, 128, 0, Linv22, 0, 0, 1, 1, st), "L22 inverse");
+    HCK(gemm_call(h, 0, 1, Linv22, 128, 0, W1, ldw, 0, L21, ldw, 0, 1, ntc, 128, 0, 0, -1.0, 0.0, 1), "U12^T");
+    HCK(launch_append_u(h->buf.Z_dev, ld, n, k, np, np2, L21, ldw, Linv22, st), "U columns");
+    HCK(launch_trmv_upper(h->buf.Z_dev, ld, h->buf.K_dev + (long)np2 * ld, n2, h->alpha_dev, st), "trmv");
+  }
+  HCK(hipStreamSynchronize(st), "stream sync");
+  h->n = n2;
+  h->np = np2;
+  h->ntc = np2 / 128;
+  h->out_host[1] += stats[0];
+  h->out_host[2] += stats[1];
+  h->out_host[0] = -0.5 * (double)n2 * 1.8378770664093453 - 0.5 * h->out_host[2] - h->out_host[1];
+  h->have_kinv = false;
+  // the caller's batch buffers were sized for the old n: every batch call is refused until mi_gp_set_batch (which re-sizes the
+  // batch scratch for the new n)
+  h->b_cond_k = 0;
+  h->bbuf = mi_gp_batch_buffers();
+  h->batch_cap = 0;
   return 0;
 }

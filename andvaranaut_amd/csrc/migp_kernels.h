@@ -225,6 +225,24 @@ hipError_t launch_predict_reduce_batched(const KernSpec& spec, const double* the
 hipError_t launch_mixture_moments(const double* mean, const double* var, int m, int k, const int* info, int sinfo,
                                   double* mix_mean, double* mix_var, hipStream_t stream);
 
+// ---------------------------------------------------------------- append_f64.hip (mi_gp_append)
+// S block: 256 x 128 doubles (ld 128): S = K22 + noise (identity-padded) in rows 0 .. 127, r / beta2 in row 128.
+// S -= sum of nparts 128 x 128 partial products (parts, 16384 doubles apart); r = y2 - L21 beta1 (k entries, zeros beyond)
+hipError_t launch_append_schur(double* S, const double* parts, int nparts, const double* L21, long ldw, const double* beta1, int np,
+                               const double* y2, int k, hipStream_t stream);
+// stats[0] = sum log L22_ii, stats[1] = |beta2|^2 (k entries), stats[2] = (double)*info
+hipError_t launch_append_stats(const double* S, int k, const int* info, double* stats, hipStream_t stream);
+// beta row moved to / extended at row np_new, then rows [n, n + k) of K = [L21, L22, 0] (and identity padding rows of a new tile)
+hipError_t launch_append_commit(double* K, long ld, int n, int k, int np_old, int np_new, const double* L21, long ldw, const double* S,
+                                hipStream_t stream);
+// inverses of ntiles (1 or 2) consecutive lower-triangular 128 x 128 tiles T + t * sT into out + t * sout, rows [i0_first, 128) of
+// the first (the rows above it are resident) and every row of a second; plain: row-major instead of minv_index order
+hipError_t launch_tile_inverse_rows(const double* T, long ldt, long sT, double* out, long sout, int i0_first, int ntiles, int plain,
+                                    hipStream_t stream);
+// U = L^-T extended in place by the appended columns: U12 from Qt (k rows, row p = -(L22^-1 L21 U11^T) row p), U22 = Linv22^T
+hipError_t launch_append_u(double* Z, long ld, int n, int k, int np_old, int np_new, const double* Qt, long ldw, const double* Linv22,
+                           hipStream_t stream);
+
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)
 void set_global_error(const char* text);

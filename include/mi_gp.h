@@ -158,6 +158,31 @@ MI_GP_API int mi_gp_factor_batch(mi_gp_handle* h, int k, const double* thetas_ho
 MI_GP_API int mi_gp_predict_batch(mi_gp_handle* h, int k, const double* Xnew_dev, int m, double* work_dev, long ldw, long stride_work,
                                   double* mean_dev, double* var_dev, int pred_noise, double* mix_mean_dev, double* mix_var_dev);
 
+/* Appending observations at fixed hyper-parameters (BO / sequential designs that keep theta for several iterations; the
+ * reference refits after every evaluated point, gpmcmc.py:883-888 -- SURVEY 8 f-4's "update the Cholesky factor when data are
+ * appended").  Costs O(n^2 k) against the O(n^3) of a refactorisation.
+ *   mi_gp_reserve  the handle may grow to `capacity` points: every handle-owned scratch that depends on n is sized for it
+ *                  (resident contents kept).  The caller promises that the buffers of mi_gp_set_data hold that many points:
+ *                  X_dev / y_dev (and the diagonal of mi_gp_set_diag) capacity rows, K_dev padded(capacity) + 128 rows, Z_dev /
+ *                  W_dev padded(capacity) rows, lda >= padded(capacity) (checked when data are bound).  Without it a handle
+ *                  cannot grow (mi_gp_append returns -1) and behaves as before.  -1 if capacity < n.
+ *   mi_gp_append   extends the conditional-form factorisation of the last successful mi_gp_factor by k points (1 <= k <= 128,
+ *                  Xnew_dev k x d, ynew_dev k, diag_new_dev k entries of the per-point diagonal -- required exactly when one is
+ *                  set) at the same theta: L21 = K21 L11^-T, L22 = chol(K22 + noise - L21 L21^T), beta2 = L22^-1 (y2 - L21 beta1).
+ *                  The points are copied into rows n .. n + k - 1 of X_dev / y_dev (/ the diagonal); n grows by k and the padded
+ *                  size by a tile when a 128-row boundary is crossed (the beta row moves along).  The first n rows of the
+ *                  factor are not touched.  With U = L^-T resident (mi_gp_predict_u / mi_gp_predict_grad) it is extended in
+ *                  place and alpha recomputed; mi_gp_predict, _predict_u and _predict_grad continue without a refactorisation,
+ *                  mi_gp_lml_parts returns the grown logdet and quad.  K^-1 is invalidated (mi_gp_alpha / mi_gp_grad_x need a
+ *                  new mi_gp_lml_grad), and so is the batch state: every batch call returns -1 until mi_gp_set_batch is
+ *                  called again (buffers sized for the new n).  work_dev: 4 * 128 * ldw + 65600 doubles, ldw even and
+ *                  >= padded(n + k).  Returns -1 without a prior mi_gp_factor, for n + k > capacity, k out of range, a
+ *                  diagonal mismatch or ldw too small; info > 0 (1-based global index of the bad pivot) if the appended block
+ *                  is not positive definite -- the handle is then exactly as it was. */
+MI_GP_API int mi_gp_reserve(mi_gp_handle* h, int capacity);
+MI_GP_API int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
+                           double* work_dev, long ldw);
+
 /* tuning knobs (benchmarks / A-B tests), ALL per handle -- nothing here is process-wide:
  *   0  look-ahead: factor the next super-panel on a second stream while the trailing update runs; 0 never, 1 by size
  *      (default: from 20 tile columns = N > 2432 on, where the overlap beats the cross-stream hand-offs -- and from 4 tile
