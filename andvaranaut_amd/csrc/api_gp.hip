@@ -14,6 +14,22 @@ using namespace migp;
 
 constexpr int SIG_SLOTS = 1024;  // cross-stream edges of one evaluation (a 16384-point factorisation has ~60)
 
+// Per-problem scratch of an evaluation, for k problems (the single evaluation's k = 1, a batch's k = its count); problem p's
+// part of an array starts p per-problem sizes in (scratch_strides()).
+struct Scratch {
+  int k = 0;                    // problems it is sized for (0: none)
+  double* theta_dev = nullptr;  // [k][ntheta]
+  double* dinv_dev = nullptr;   // [k][ntc + 4][MINV_ELEMS] explicit inverses of the diagonal blocks of L (leaf output, strip operand)
+  double* alpha_dev = nullptr;  // [k][np] K^-1 y
+  double* part_dev = nullptr;   // [k][grad_contract_blocks(n)][ntheta]
+  int* info_dev = nullptr;      // [k][4] bad-pivot words
+  double* lr_part_dev = nullptr;    // [k][2 * LML_REDUCE_BLOCKS] slice sums of lml_reduce_kernel
+  unsigned* lr_sync_dev = nullptr;  // [2k]: [0, k) lml_reduce's tickets, [k, 2k) grad_final's (zero between evaluations)
+  double* grad_host = nullptr;  // pinned [k][ntheta]
+  double* out_host = nullptr;   // pinned [k][16] scalar records
+  double* theta_host = nullptr; // pinned [k][ntheta]
+};
+
 struct mi_gp_handle {
   mi_gp_config cfg;
   KernSpec spec;
@@ -81,18 +97,8 @@ struct mi_gp_handle {
                        // trailing update's enumeration instead of in launches of its own (0: never)
   mi_gp_buffers buf;
   bool have_data;
-  // handle-owned small scratch
-  double* theta_dev;    // [ntheta]
-  double* dinv_dev;     // [ntc][128][128] explicit inverses of the diagonal blocks of L (leaf output, strip operand)
-  double* alpha_dev;    // [np] K^-1 y
-  double* part_dev;     // [grad_contract_blocks(n)][ntheta]
+  Scratch one;          // the single evaluation's scratch (k = 1, sized for cap points)
   double* gxs_dev;      // [grad_x_splits][n][d] partial dLML/dX (allocated on first mi_gp_grad_x)
-  double* grad_host;    // pinned [ntheta]
-  int* info_dev;
-  double* lr_part_dev;  // [2 * LML_REDUCE_BLOCKS] slice sums of lml_reduce_kernel
-  unsigned* lr_sync_dev;  // its ticket (zero between evaluations)
-  double* out_host;     // pinned [16]
-  double* theta_host;   // pinned
   // profiling
   int prof_level;
   hipEvent_t ev[8];
@@ -105,19 +111,13 @@ struct mi_gp_handle {
   double t_trtri_ms, t_lauum_ms, t_contract_ms;
   double t_enqueue_ms;  // host time of enqueueing the last single evaluation (always measured: two clock reads)
   double t_gemm_big_ms, gemm_big_flops, n_gemm_big;  // the 128x128-tile kernel only
-  // batched evaluation (mi_gp_set_batch / mi_gp_lml_batch / mi_gp_lml_grad_batch): while a batch runs, buf / the scratch
-  // pointers above point at the batch's arrays and bt carries the strides; nullptr / nb = 1 otherwise
-  Batch bt;
-  const Batch* btp;        // &bt while a batch is being enqueued, nullptr otherwise (what the launchers get)
+  // batched evaluation (mi_gp_set_batch / mi_gp_lml_batch / mi_gp_lml_grad_batch): the caller's K / Z / W and the batch's
+  // scratch (k = bbuf.count or more, sized for n points); batch_eval() hands both to the enqueue code
   mi_gp_batch_buffers bbuf;
-  int batch_cap;           // problems the batch scratch below is sized for
-  double *b_theta_dev, *b_dinv_dev, *b_alpha_dev, *b_part_dev, *b_grad_host, *b_out_host, *b_theta_host;
-  int* b_info_dev;
-  double* b_lr_part_dev;
-  unsigned* b_lr_sync_dev;
+  Scratch batch;
   int b_cond_k;            // problems whose conditional factors (L_p, beta_p, leaf inverses) the last batch call left in the batch
-                           // buffers: mi_gp_factor_batch sets it, every other batch call, mi_gp_set_batch / _set_data / _set_diag and
-                           // a single evaluation into the batch's K clear it (0)
+                           // buffers: mi_gp_factor_batch sets it, every other batch call, mi_gp_set_batch / _set_data / _set_diag,
+                           // mi_gp_append and a single evaluation into the batch's K (factor_internal) clear it (0)
   bool factored;
   bool have_u;             // Z_dev holds U = L^-T and alpha_dev = K^-1 y of the last mi_gp_factor (mi_gp_predict_grad)
   bool have_kinv;          // W_dev holds K^-1 (lower) and alpha_dev = K^-1 y of the last mi_gp_lml_grad
@@ -140,22 +140,78 @@ static int hfail(mi_gp_handle* h, hipError_t e, const char* where) {
 
 extern "C" const char* mi_gp_last_error(mi_gp_handle* h) { return h ? h->err : "null handle"; }
 
+// The per-problem sizes of the Scratch arrays for up to `cap` points, as the strides of a Batch (+ 4 blocks behind the leaf
+// inverses: the strips' operand-order copies of their first 256 rows for the thin updates, two buffers of two blocks --
+// column mode reads the previous column's copy beside the current one's)
+static Batch scratch_strides(const mi_gp_handle* h, int cap) {
+  const long np = (cap + 127) / 128 * 128;
+  Batch bt;
+  bt.sdinv = MINV_ELEMS * (np / 128 + 4); bt.salpha = np; bt.spart = (long)grad_contract_blocks(cap) * h->ntheta;
+  bt.stheta = h->ntheta; bt.sinfo = 4; bt.sout = 16;
+  return bt;
+}
+
+static void free_scratch(Scratch& s) {
+  (void)hipFree(s.theta_dev); (void)hipFree(s.dinv_dev); (void)hipFree(s.alpha_dev); (void)hipFree(s.part_dev);
+  (void)hipFree(s.info_dev); (void)hipFree(s.lr_part_dev); (void)hipFree(s.lr_sync_dev);
+  if (s.grad_host) (void)hipHostFree(s.grad_host);
+  if (s.out_host) (void)hipHostFree(s.out_host);
+  if (s.theta_host) (void)hipHostFree(s.theta_host);
+  s = Scratch();
+}
+
+// s (empty) for k problems of up to cap points; on failure s keeps what it got (free_scratch) and k stays 0
+static hipError_t alloc_scratch(const mi_gp_handle* h, Scratch& s, int k, int cap) {
+  const Batch z = scratch_strides(h, cap);
+  const size_t kk = (size_t)k;
+  hipError_t e = hipMalloc(&s.theta_dev, sizeof(double) * kk * z.stheta);
+  if (e == hipSuccess) e = hipMalloc(&s.dinv_dev, sizeof(double) * kk * z.sdinv);
+  if (e == hipSuccess) e = hipMalloc(&s.alpha_dev, sizeof(double) * kk * z.salpha);
+  if (e == hipSuccess) e = hipMalloc(&s.part_dev, sizeof(double) * kk * z.spart);
+  if (e == hipSuccess) e = hipMalloc(&s.info_dev, sizeof(int) * kk * z.sinfo);
+  if (e == hipSuccess) e = hipMalloc(&s.lr_part_dev, sizeof(double) * kk * 2 * LML_REDUCE_BLOCKS);
+  if (e == hipSuccess) e = hipMalloc(&s.lr_sync_dev, sizeof(unsigned) * kk * 2);
+  if (e == hipSuccess) e = hipMemset(s.lr_sync_dev, 0, sizeof(unsigned) * kk * 2);
+  if (e == hipSuccess) e = hipHostMalloc(&s.grad_host, sizeof(double) * kk * z.stheta);
+  if (e == hipSuccess) e = hipHostMalloc(&s.out_host, sizeof(double) * kk * z.sout);
+  if (e == hipSuccess) memset(s.out_host, 0, sizeof(double) * kk * z.sout);  // (the sequence words: wait_evaluation())
+  if (e == hipSuccess) e = hipHostMalloc(&s.theta_host, sizeof(double) * kk * z.stheta);
+  if (e == hipSuccess) s.k = k;
+  return e;
+}
+
+// What the enqueue code evaluates: the single problem (one_eval) or a batch of problems (batch_eval) -- its K / Z / W, its
+// scratch and its per-problem strides.  X, y and lda are the handle's (h->buf) either way.  Built by each call, never stored:
+// the handle itself always describes the single problem.
+struct Eval {
+  double *K, *Z, *W;
+  const Scratch& s;
+  Batch bt;         // nb = 1 and every stride 0 for the single problem
+  bool batched;
+  int prof;         // profiling level (a batch: 0)
+  const Batch* lb() const { return batched ? &bt : nullptr; }  // what the launchers get (nullptr: one problem)
+};
+
+static Eval one_eval(const mi_gp_handle* h) {
+  return {h->buf.K_dev, h->buf.Z_dev, h->buf.W_dev, h->one, Batch(), false, h->prof_level};
+}
+
+// the first k problems of the batch buffers and scratch
+static Eval batch_eval(const mi_gp_handle* h, int k) {
+  Batch bt = scratch_strides(h, h->n);
+  bt.nb = k;
+  bt.sK = h->bbuf.stride_k; bt.sZ = bt.sW = h->bbuf.stride_zw;
+  return {h->bbuf.K_dev, h->bbuf.Z_dev, h->bbuf.W_dev, h->batch, bt, true, 0};
+}
+
 // frees whatever a (possibly half-built) handle owns; every member is null / empty until it is created
 static void release_handle(mi_gp_handle* h) {
   (void)hipSetDevice(h->device);
   if (h->pstream) (void)hipStreamSynchronize(h->pstream);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(h->theta_dev); (void)hipFree(h->dinv_dev); (void)hipFree(h->info_dev); (void)hipFree(h->sig_dev);
-  (void)hipFree(h->alpha_dev); (void)hipFree(h->part_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
-  (void)hipFree(h->lr_part_dev); (void)hipFree(h->lr_sync_dev); (void)hipFree(h->b_lr_part_dev); (void)hipFree(h->b_lr_sync_dev);
-  (void)hipFree(h->b_theta_dev); (void)hipFree(h->b_dinv_dev); (void)hipFree(h->b_alpha_dev); (void)hipFree(h->b_part_dev);
-  (void)hipFree(h->b_info_dev);
-  if (h->b_grad_host) (void)hipHostFree(h->b_grad_host);
-  if (h->b_out_host) (void)hipHostFree(h->b_out_host);
-  if (h->b_theta_host) (void)hipHostFree(h->b_theta_host);
-  if (h->grad_host) (void)hipHostFree(h->grad_host);
-  if (h->out_host) (void)hipHostFree(h->out_host);
-  if (h->theta_host) (void)hipHostFree(h->theta_host);
+  free_scratch(h->one);
+  free_scratch(h->batch);
+  (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -170,18 +226,18 @@ static void release_handle(mi_gp_handle* h) {
 // behind it on the main stream -- finds that out before an evaluation can stall for seconds; such a handle uses events
 // (gpmcmc.py:331-339: the reference's evaluations never fail for reasons of scheduling).  ~40 us where dispatch is concurrent.
 static hipError_t probe_dispatch(mi_gp_handle* h) {
-  hipError_t e = hipMemset(h->info_dev, 0x7f, sizeof(int) * 4);
+  hipError_t e = hipMemset(h->one.info_dev, 0x7f, sizeof(int) * 4);
   // (both streams have launched before: the probe does not time the first launch's code-object load)
-  if (e == hipSuccess) e = launch_signal_write_wait(h->sig_dev + SIG_SLOTS - 1, nullptr, 0u, h->info_dev, h->pstream);
-  if (e == hipSuccess) e = launch_signal_write_wait(h->sig_dev + SIG_SLOTS - 1, nullptr, 0u, h->info_dev, h->stream);
+  if (e == hipSuccess) e = launch_signal_write_wait(h->sig_dev + SIG_SLOTS - 1, nullptr, 0u, h->one.info_dev, h->pstream);
+  if (e == hipSuccess) e = launch_signal_write_wait(h->sig_dev + SIG_SLOTS - 1, nullptr, 0u, h->one.info_dev, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->pstream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess) e = launch_signal_write_wait(nullptr, h->sig_dev + SIG_SLOTS - 1, 1u, h->info_dev, h->pstream, 1, 0, 14);
-  if (e == hipSuccess) e = launch_signal_write_wait(h->sig_dev + SIG_SLOTS - 1, nullptr, 1u, h->info_dev, h->stream);
+  if (e == hipSuccess) e = launch_signal_write_wait(nullptr, h->sig_dev + SIG_SLOTS - 1, 1u, h->one.info_dev, h->pstream, 1, 0, 14);
+  if (e == hipSuccess) e = launch_signal_write_wait(h->sig_dev + SIG_SLOTS - 1, nullptr, 1u, h->one.info_dev, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->pstream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   int info = 0;
-  if (e == hipSuccess) e = hipMemcpy(&info, h->info_dev, sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&info, h->one.info_dev, sizeof(int), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemset(h->sig_dev + SIG_SLOTS - 1, 0, sizeof(unsigned));
   if (e == hipSuccess && info == SIGNAL_TIMEOUT_INFO) {
     h->use_smo = 0;
@@ -279,22 +335,9 @@ extern "C" int mi_gp_create(const mi_gp_config* cfg, mi_gp_handle** out) {
   // 1.017 ms, 4096 2.470 -> 2.388, 8192 6.417 -> 6.348, 16384 28.59 -> 28.39 against the 8 / 4 split of round 1)
   h->lowocc_thr = 1 << 20;
   h->w_thr[0] = 1 << 20; h->w_thr[1] = 0; h->w_thr[2] = 0;
-  if (e == hipSuccess) e = hipMalloc(&h->theta_dev, sizeof(double) * h->ntheta);
-  // (+ 4 blocks behind the leaf inverses: the strips' operand-order copies of their first 256 rows for the thin updates, two
-  // buffers of two blocks -- column mode reads the previous column's copy beside the current one's)
-  if (e == hipSuccess) e = hipMalloc(&h->dinv_dev, sizeof(double) * MINV_ELEMS * (size_t)(h->ntc + 4));
-  if (e == hipSuccess) e = hipMalloc(&h->alpha_dev, sizeof(double) * h->np);
-  if (e == hipSuccess) e = hipMalloc(&h->part_dev, sizeof(double) * (size_t)grad_contract_blocks(h->n) * h->ntheta);
-  if (e == hipSuccess) e = hipHostMalloc(&h->grad_host, sizeof(double) * h->ntheta);
-  if (e == hipSuccess) e = hipMalloc(&h->info_dev, sizeof(int) * 4);
+  if (e == hipSuccess) e = alloc_scratch(h, h->one, 1, h->cap);
   if (e == hipSuccess) e = hipMalloc(&h->sig_dev, sizeof(unsigned) * SIG_SLOTS);
   if (e == hipSuccess) e = hipMemset(h->sig_dev, 0, sizeof(unsigned) * SIG_SLOTS);
-  if (e == hipSuccess) e = hipMalloc(&h->lr_part_dev, sizeof(double) * 2 * LML_REDUCE_BLOCKS);
-  if (e == hipSuccess) e = hipMalloc(&h->lr_sync_dev, sizeof(unsigned) * 2);  // [0] lml_reduce's ticket, [1] grad_final's
-  if (e == hipSuccess) e = hipMemset(h->lr_sync_dev, 0, sizeof(unsigned) * 2);
-  if (e == hipSuccess) e = hipHostMalloc(&h->out_host, sizeof(double) * 16);
-  if (e == hipSuccess) memset(h->out_host, 0, sizeof(double) * 16);  // (the sequence words: wait_evaluation())
-  if (e == hipSuccess) e = hipHostMalloc(&h->theta_host, sizeof(double) * h->ntheta);
   for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
   if (e == hipSuccess) e = gemm_f64_enable_lds();
   if (e == hipSuccess) e = leaf_enable_lds();
@@ -419,9 +462,9 @@ extern "C" int mi_gp_set_profiling(mi_gp_handle* h, int level) {
 }
 
 // ---------------------------------------------------------------- driver pieces
-static hipError_t prof_gemm(mi_gp_handle* h, const GemmParams& p, int ak, int bk, int batch, double flops,
+static hipError_t prof_gemm(mi_gp_handle* h, const Eval& E, const GemmParams& p, int ak, int bk, int batch, double flops,
                             hipStream_t st) {
-  if (h->prof_level >= 2) {
+  if (E.prof >= 2) {
     // one event pair per kernel launch: a split product (gemm_tail_tiles) is two launches, its flops divided by tiles;
     // `flops` are those of the WHOLE product, a sub-range launch (p.tile0 / p.tile_cnt) is credited its share of tiles
     const int tail = gemm_tail_tiles(p, batch);
@@ -465,15 +508,15 @@ static bool thin_shape(const mi_gp_handle* h, int mt, int nc, int kw) {
 }
 
 // wr (in-panel updates only): raised to the evaluation's epoch once everything queued on `st` before this update is done
-static hipError_t syrk_trapezoid(mi_gp_handle* h, double* A, long lda, int ntr, int r0, int nc, int k0, int kw,
+static hipError_t syrk_trapezoid(mi_gp_handle* h, const Eval& E, double* A, long lda, int ntr, int r0, int nc, int k0, int kw,
                                  hipStream_t st, int one_per_cu = 0, int tile0 = 0, int tile_cnt = 0, int fc = 0,
                                  bool in_panel = false, unsigned* wr = nullptr, bool lsw = false, int kflush = 0) {
   // (lsw: the strip in front of this update has written its first rows in operand order -- chol_panel decides both by the same rule)
   if (in_panel && lsw && thin_shape(h, ntr - r0, nc, kw))
     return launch_syrk_thin(A + (long)r0 * 128 * lda + (long)k0 * 128, A + (long)r0 * 128 * lda + (long)r0 * 128, lda, ntr - r0, nc,
-                            kw * 128, st, h->btp, wr, h->sig_epoch, h->dinv_dev + (size_t)h->ntc * MINV_ELEMS);
+                            kw * 128, st, E.lb(), wr, h->sig_epoch, E.s.dinv_dev + (size_t)h->ntc * MINV_ELEMS);
   if (wr != nullptr) {  // (the 64x64-tile kernel has no such hook: a one-lane launch in front of it)
-    hipError_t we = launch_signal_write_wait(wr, nullptr, h->sig_epoch, h->info_dev, st);
+    hipError_t we = launch_signal_write_wait(wr, nullptr, h->sig_epoch, E.s.info_dev, st);
     if (we != hipSuccess) return we;
   }
   GemmParams p;
@@ -489,7 +532,7 @@ static hipError_t syrk_trapezoid(mi_gp_handle* h, double* A, long lda, int ntr, 
   p.B = p.A;
   p.C = A + (long)r0 * 128 * lda + (long)r0 * 128;
   p.lda = p.ldb = p.ldc = lda;
-  p.strideA = p.strideB = p.strideC = h->btp ? h->btp->sK : 0;
+  p.strideA = p.strideB = p.strideC = E.bt.sK;
   p.mt = ntr - r0;
   p.nt = nc;
   p.k = kw * 128;
@@ -504,22 +547,22 @@ static hipError_t syrk_trapezoid(mi_gp_handle* h, double* A, long lda, int ntr, 
   // (full diagonal tiles, a 128-row tile for the y row).
   const double c = nc * 128.0, rows_real = (p.mt - 1) * 128.0;
   const double flops = (double)p.k * (c * (c + 1.0) + 2.0 * (rows_real - c) * c + 2.0 * c);
-  return prof_gemm(h, p, 0, 0, h->btp ? h->btp->nb : 1, flops, st);
+  return prof_gemm(h, E, p, 0, 0, E.bt.nb, flops, st);
 }
 
 // factor tile columns [c0, c0+w) of the (ntr x ntc)-tile trapezoid, recursively halving w; nx (0 / 1): every level's update
 // also covers the nx tile columns behind the panel, so that they are up to date when the panel's last strip is.
 // follow: number of tile columns of the k = 128 update that the CALLER runs right behind this (one-column) panel's strip
-static hipError_t chol_panel(mi_gp_handle* h, double* A, long lda, int ntr, int c0, int w, hipStream_t st, int nx = 0, int follow = 0) {
+static hipError_t chol_panel(mi_gp_handle* h, const Eval& E, double* A, long lda, int ntr, int c0, int w, hipStream_t st, int nx = 0, int follow = 0) {
   hipError_t e;
   if (w == 1) {
     // the update behind this column's strip is a k = 128 one over `fol` columns: on the thin kernel the strip hands it its
     // B operand (the first fol x 128 rows of the strip) in operand order
     const int fol = nx > 0 ? nx : follow;
     const bool sw = fol > 0 && fol <= 2 && thin_shape(h, ntr - c0 - 1, fol, 1);
-    double* lsw = h->dinv_dev + (size_t)h->ntc * MINV_ELEMS;
+    double* lsw = E.s.dinv_dev + (size_t)h->ntc * MINV_ELEMS;
     double* blk = A + (long)c0 * 128 * lda + (long)c0 * 128;
-    double* dinv = h->dinv_dev + (size_t)c0 * MINV_ELEMS;
+    double* dinv = E.s.dinv_dev + (size_t)c0 * MINV_ELEMS;
     const int m = (ntr - c0 - 1) * 128;
     // (the trapezoid's last tile row is the y^T block: below the last tile column there is nothing else, and the leaf
     // solves that one row itself)
@@ -532,11 +575,11 @@ static hipError_t chol_panel(mi_gp_handle* h, double* A, long lda, int ntr, int 
     const bool waits2 = c0 == h->wait2_col && h->wait2_slot >= 0 && h->use_smo >= 2;
     const bool folded = waits2 || (waits && h->wait_slot >= 0 && h->use_smo >= 2);
     if (c0 == h->wait2_col) h->wait2_col = -1;
-    e = launch_potrf_leaf128(blk, lda, dinv, c0 * 128, h->info_dev, st, m == 128 ? blk + 128 * lda : nullptr, h->btp,
+    e = launch_potrf_leaf128(blk, lda, dinv, c0 * 128, E.s.info_dev, st, m == 128 ? blk + 128 * lda : nullptr, E.lb(),
                              waits2 ? h->sig_dev + h->wait2_slot : folded ? h->sig_dev + h->wait_slot : nullptr,
                              h->sig_epoch, h->poll_limit_log2);
     if (e == hipSuccess && m > 128)
-      e = launch_trsm_strip128(dinv, blk + 128 * lda, lda, m, st, h->btp, h->btp ? h->btp->sK : 0, sw ? lsw : nullptr, 8 * fol);
+      e = launch_trsm_strip128(dinv, blk + 128 * lda, lda, m, st, E.lb(), E.bt.sK, sw ? lsw : nullptr, 8 * fol);
     if (e == hipSuccess && waits) {
       h->wait_col = -1;
       if (!folded)
@@ -547,17 +590,17 @@ static hipError_t chol_panel(mi_gp_handle* h, double* A, long lda, int ntr, int 
       unsigned* wr = nullptr;
       if (c0 == h->done_col && h->done_slot >= 0) wr = h->sig_dev + h->done_slot;
       if (c0 == h->done_col) h->done_col = -1;
-      e = syrk_trapezoid(h, A, lda, ntr, c0 + 1, nx, c0, 1, st, 0, 0, 0, 0, true, wr, sw);
+      e = syrk_trapezoid(h, E, A, lda, ntr, c0 + 1, nx, c0, 1, st, 0, 0, 0, 0, true, wr, sw);
     }
     return e;
   }
   const int w1 = w / 2, w2 = w - w1;
-  e = chol_panel(h, A, lda, ntr, c0, w1, st, 0, w1 == 1 ? w2 + nx : 0);
+  e = chol_panel(h, E, A, lda, ntr, c0, w1, st, 0, w1 == 1 ? w2 + nx : 0);
   if (e != hipSuccess) return e;
-  e = syrk_trapezoid(h, A, lda, ntr, c0 + w1, w2 + nx, c0, w1, st, 0, 0, 0, 0, true, nullptr,
+  e = syrk_trapezoid(h, E, A, lda, ntr, c0 + w1, w2 + nx, c0, w1, st, 0, 0, 0, 0, true, nullptr,
                      w1 == 1 && w2 + nx <= 2 && thin_shape(h, ntr - c0 - w1, w2 + nx, 1));
   if (e != hipSuccess) return e;
-  return chol_panel(h, A, lda, ntr, c0 + w1, w2, st, nx);
+  return chol_panel(h, E, A, lda, ntr, c0 + w1, w2, st, nx);
 }
 
 // Right-looking blocked Cholesky of the (ntr x ntc)-tile lower trapezoid with one super-panel of
@@ -640,7 +683,7 @@ static bool whole_columns(const mi_gp_handle* h, int ntc) {
   return h->rl_cols > 0 && (ntc <= h->rl_cols || ntc <= h->rl_whole);
 }
 
-static hipError_t u_levels(mi_gp_handle* h, int final_cols, int max_s);
+static hipError_t u_levels(mi_gp_handle* h, const Eval& E, int final_cols, int max_s);
 
 // COLUMN MODE (round 5, option 37): tile columns [cs, ntc) one by one.  The chain-bound end of a factorisation -- and all of
 // a small one -- pays a fixed ~5-8 us per launch on the panel stream, so the fewest, shortest launches per column win: leaf,
@@ -653,7 +696,7 @@ static hipError_t u_levels(mi_gp_handle* h, int final_cols, int max_s);
 // end of leaf j+1 -- ~58 us for ~20.  Which kernel updates a tile with which k is a matter of the column alone (not of the
 // streams: on one stream the same launches run in program order), so every schedule returns the same bits.
 // t_pending: something queued on the main stream writes columns > cs (the previous super-panel's update): leaf cs polls for it.
-static hipError_t chol_columns(mi_gp_handle* h, double* A, long lda, int ntr, int ntc, int cs, hipStream_t T, hipStream_t P,
+static hipError_t chol_columns(mi_gp_handle* h, const Eval& E, double* A, long lda, int ntr, int ntc, int cs, hipStream_t T, hipStream_t P,
                                bool t_pending) {
   hipError_t e = hipSuccess;
 #define CKC(x) do { e = (x); if (e != hipSuccess) return e; } while (0)
@@ -675,13 +718,13 @@ static hipError_t chol_columns(mi_gp_handle* h, double* A, long lda, int ntr, in
     }
     return se;
   };
-  double* lsw0 = h->dinv_dev + (size_t)h->ntc * MINV_ELEMS;
-  const int group = (h->btp && h->btp->nb > 1) ? h->rl_group : 1;
+  double* lsw0 = E.s.dinv_dev + (size_t)h->ntc * MINV_ELEMS;
+  const int group = E.bt.nb > 1 ? h->rl_group : 1;
   int seg0 = cs;  // grouped schedule: first column (k-segment) the columns behind the chain's next one have not had yet
   if (two && t_pending) CKC(t_signal((cs + 1) % 3));  // polled by leaf cs: the index leaf j polls is (j - 2) mod 3 = (j + 1) mod 3
   for (int j = cs; j < ntc; ++j) {
     double* blk = A + (long)j * 128 * lda + (long)j * 128;
-    double* dinv = h->dinv_dev + (size_t)j * MINV_ELEMS;
+    double* dinv = E.s.dinv_dev + (size_t)j * MINV_ELEMS;
     const int m = (ntr - j - 1) * 128;
     // (the thin update of column c reads the strips of columns c - 2 and c - 1: a strip writes its operand-order copy when the
     // NEXT column's update is a thin one as well -- the limit is monotone in the column, so that covers this column's)
@@ -698,10 +741,10 @@ static hipError_t chol_columns(mi_gp_handle* h, double* A, long lda, int ntr, in
       if (smo && h->sig_next < SIG_SLOTS) sslot = h->sig_next++;
       else CKC(hand_off(h, P, T));  // (behind the previous step's thin update: strip j - 1 is done)
     }
-    CKC(launch_potrf_leaf128(blk, lda, dinv, j * 128, h->info_dev, P, m == 128 ? blk + 128 * lda : nullptr, h->btp,
+    CKC(launch_potrf_leaf128(blk, lda, dinv, j * 128, E.s.info_dev, P, m == 128 ? blk + 128 * lda : nullptr, E.lb(),
                              polls && tslot[pidx] >= 0 ? h->sig_dev + tslot[pidx] : nullptr, h->sig_epoch, h->poll_limit_log2,
                              sslot >= 0 ? h->sig_dev + sslot : nullptr));
-    if (m > 128) CKC(launch_trsm_strip128(dinv, blk + 128 * lda, lda, m, P, h->btp, h->btp ? h->btp->sK : 0, lsw_out ? lswj : nullptr, 16));
+    if (m > 128) CKC(launch_trsm_strip128(dinv, blk + 128 * lda, lda, m, P, E.lb(), E.bt.sK, lsw_out ? lswj : nullptr, 16));
     if (polls && tslot[pidx] < 0) CKC(hipStreamWaitEvent(P, tev[pidx], 0));
     tslot[pidx] = -1;
     tev_set[pidx] = false;
@@ -713,25 +756,25 @@ static hipError_t chol_columns(mi_gp_handle* h, double* A, long lda, int ntr, in
       double* Cc = A + (long)(j + 1) * 128 * lda + (long)(j + 1) * 128;
       if (thin_ok) {
         const double* la = k2 ? lsw0 + (size_t)(2 * ((j - 1) & 1) + 1) * MINV_ELEMS : lswj;  // column j-1: its strip's SECOND block
-        CKC(launch_syrk_thin(Pp, Cc, lda, mt, 1, kw * 128, P, h->btp, nullptr, h->sig_epoch, la, k2 ? lswj : nullptr));
+        CKC(launch_syrk_thin(Pp, Cc, lda, mt, 1, kw * 128, P, E.lb(), nullptr, h->sig_epoch, la, k2 ? lswj : nullptr));
       } else {
-        CKC(syrk_trapezoid(h, A, lda, ntr, j + 1, 1, k0, kw, P));
+        CKC(syrk_trapezoid(h, E, A, lda, ntr, j + 1, 1, k0, kw, P));
       }
     }
     if (t_work) {
       if (sslot >= 0) CKC(hipStreamWaitValue32(T, h->sig_dev + sslot, h->sig_epoch, hipStreamWaitValueGte, 0xffffffffu));
       if (group <= 1) {
-        CKC(syrk_trapezoid(h, A, lda, ntr, j + 2, ntc - j - 2, j - 1, 1, T));
+        CKC(syrk_trapezoid(h, E, A, lda, ntr, j + 2, ntc - j - 2, j - 1, 1, T));
         if (two) CKC(t_signal((j - 1) % 3));
       } else {
         // A batch is bound by the main stream's updates, not by the chain, and a k = 128 update reads and writes the trailing
         // matrices for 128 columns of k.  Same arithmetic, grouped: the column the chain needs next takes the segments it
         // has not had yet (k-segmented launch: the tile takes each 128-column partial sum as a launch of its own would), the
         // columns behind it take `group` segments at a time.  Invariant: every column >= j + 3 has exactly the segments < seg0.
-        CKC(syrk_trapezoid(h, A, lda, ntr, j + 2, 1, seg0, j - seg0, T, 0, 0, 0, 0, false, nullptr, false, j - seg0 > 1 ? 128 : 0));
+        CKC(syrk_trapezoid(h, E, A, lda, ntr, j + 2, 1, seg0, j - seg0, T, 0, 0, 0, 0, false, nullptr, false, j - seg0 > 1 ? 128 : 0));
         if (two) CKC(t_signal((j - 1) % 3));
         if (j - seg0 >= group && j + 3 < ntc) {
-          CKC(syrk_trapezoid(h, A, lda, ntr, j + 3, ntc - j - 3, seg0, j - seg0, T, 0, 0, 0, 0, false, nullptr, false, 128));
+          CKC(syrk_trapezoid(h, E, A, lda, ntr, j + 3, ntc - j - 3, seg0, j - seg0, T, 0, 0, 0, 0, false, nullptr, false, 128));
           seg0 = j;
         }
       }
@@ -740,7 +783,7 @@ static hipError_t chol_columns(mi_gp_handle* h, double* A, long lda, int ntr, in
       // gradient evaluations: U = L^-T over the columns that are final (strips <= j - 1), behind the main stream's update
       const int upto = h->u_leaf_done + h->u_early_cols / 2 < j ? h->u_leaf_done + h->u_early_cols / 2 : j;
       if (!t_work && sslot < 0) CKC(hand_off(h, P, T));
-      CKC(u_levels(h, upto, h->u_early_max_s));
+      CKC(u_levels(h, E, upto, h->u_early_max_s));
     }
   }
 #undef CKC
@@ -751,18 +794,18 @@ static int lookahead_min_tiles(const mi_gp_handle* h, int ntc) {
   return whole_columns(h, ntc) ? COLUMN_MODE_MIN_TILES : LOOKAHEAD_MIN_TILES;
 }
 
-static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr, int ntc);
-static hipError_t cholesky(mi_gp_handle* h, double* A, long lda, int ntr, int ntc) {
-  const hipError_t e = cholesky_enqueue(h, A, lda, ntr, ntc);
+static hipError_t cholesky_enqueue(mi_gp_handle* h, const Eval& E, double* A, long lda, int ntr, int ntc);
+static hipError_t cholesky(mi_gp_handle* h, const Eval& E, double* A, long lda, int ntr, int ntc) {
+  const hipError_t e = cholesky_enqueue(h, E, A, lda, ntr, ntc);
   h->test_drop_signal = 0;  // (option 28 is for ONE evaluation, whether or not its schedule had the edge the hook drops)
   return e;
 }
 
-static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr, int ntc) {
+static hipError_t cholesky_enqueue(mi_gp_handle* h, const Eval& E, double* A, long lda, int ntr, int ntc) {
   // A batched evaluation (blockIdx.z = problem) carries nb times the work per launch, so the look-ahead pays from smaller
   // problems on (nb = 8: N = 2560 +5 %, 3072 +10 %, 4096 +7 %; nb = 2 from 3072 on).  The super-panel widths stay those of
   // the single evaluation of the same size, so that a batch returns the single entry points' bits.
-  const int nb = h->btp ? h->btp->nb : 1;
+  const int nb = E.bt.nb;
   const bool la_single = h->lookahead == 2 || (h->lookahead == 1 && ntc >= lookahead_min_tiles(h, ntc));
   const bool la = la_single || (h->lookahead == 1 && nb >= 2 && ntc >= (nb >= 8 ? 20 : 24));
   hipStream_t T = h->stream, P = la ? h->pstream : h->stream;
@@ -825,13 +868,13 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
   // column mode (chol_columns) for the last rl_cols tile columns -- a rule of the shape alone, like the extended panels
   auto rl = [&](int c0) { return h->rl_cols > 0 && c0 < ntc && (ntc - c0 <= h->rl_cols || (c0 == 0 && whole_columns(h, ntc))); };
   if (rl(0)) {
-    CKE(chol_columns(h, A, lda, ntr, ntc, 0, T, P, false));
+    CKE(chol_columns(h, E, A, lda, ntr, ntc, 0, T, P, false));
     if (P != T) CKE(hand_off(h, P, T));
     return hipSuccess;
   }
   int nx_cur = ext(0, w);
   if (nx_cur) CKE(ext_edges(0, w));
-  CKE(chol_panel(h, A, lda, ntr, 0, w, P, nx_cur));
+  CKE(chol_panel(h, E, A, lda, ntr, 0, w, P, nx_cur));
   for (int J = 0; J < ntc;) {
     const int n1 = J + w;  // first tile column right of this super-panel
     // The panel stream's edges at a super-panel boundary: it tells the main stream that super-panel J is done (the main
@@ -846,7 +889,7 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
       // final (everything left of J) run here instead of behind the factorisation (same launches on the same tiles, only
       // grouped differently over the node batches: same bits).
       const int upto = h->u_leaf_done + h->u_early_cols / 2 < J ? h->u_leaf_done + h->u_early_cols / 2 : J;
-      CKE(u_levels(h, upto, h->u_early_max_s));
+      CKE(u_levels(h, E, upto, h->u_early_max_s));
     }
     if (P != T) {
       const bool stays_two = n1 < ntc && (rl(n1) || !(ntc - n1 <= h->single_below / nb));
@@ -862,8 +905,8 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
       } else if (h->use_smo >= 2 && tp_edge && h->sig_next + 2 <= SIG_SLOTS) {
         const int a = h->sig_next++;
         tp_slot = h->sig_next++;
-        CKE(launch_signal_write_wait(h->sig_dev + a, h->sig_dev + tp_slot, h->sig_epoch, h->info_dev, P, h->btp ? h->btp->nb : 1,
-                                     h->btp ? h->btp->sinfo : 0, h->poll_limit_log2));
+        CKE(launch_signal_write_wait(h->sig_dev + a, h->sig_dev + tp_slot, h->sig_epoch, E.s.info_dev, P, E.bt.nb,
+                                     E.bt.sinfo, h->poll_limit_log2));
         CKE(hipStreamWaitValue32(T, h->sig_dev + a, h->sig_epoch, hipStreamWaitValueGte, 0xffffffffu));
       } else {
         CKE(hand_off(h, P, T));
@@ -879,13 +922,13 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
             if (tp_slot >= 0) CKE(hipStreamWriteValue32(T, h->sig_dev + tp_slot, h->sig_epoch, 0));
             else CKE(hand_off(h, T, P));
           }
-          CKE(syrk_trapezoid(h, A, lda, ntr, n1, 1, J, w, P));
+          CKE(syrk_trapezoid(h, E, A, lda, ntr, n1, 1, J, w, P));
         }
-        if (ntc - n1 - 1 > 0) CKE(syrk_trapezoid(h, A, lda, ntr, n1 + 1, ntc - n1 - 1, J, w, T));
+        if (ntc - n1 - 1 > 0) CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + 1, ntc - n1 - 1, J, w, T));
       } else if (ntc - n1 - nx_cur > 0) {
-        CKE(syrk_trapezoid(h, A, lda, ntr, n1 + nx_cur, ntc - n1 - nx_cur, J, w, T));
+        CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + nx_cur, ntc - n1 - nx_cur, J, w, T));
       }
-      CKE(chol_columns(h, A, lda, ntr, ntc, n1, T, P, P != T && ntc - n1 - 1 > 0));
+      CKE(chol_columns(h, E, A, lda, ntr, ntc, n1, T, P, P != T && ntc - n1 - 1 > 0));
       if (P != T) CKE(hand_off(h, P, T));
       break;
     }
@@ -912,19 +955,19 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
       const int ft = wn * (wn + 1) / 2 + (ar - wn) * wn;
       int x1 = (ft + 511) / 512 * 512;
       if (x1 > atiles) x1 = atiles;
-      CKE(syrk_trapezoid(h, A, lda, ntr, n1, ac, J, w, T, 0, 0, x1, wn));
+      CKE(syrk_trapezoid(h, E, A, lda, ntr, n1, ac, J, w, T, 0, 0, x1, wn));
       if (tp_slot >= 0) CKE(hipStreamWriteValue32(T, h->sig_dev + tp_slot, h->sig_epoch, 0));
       else CKE(hand_off(h, T, P));
       int done = x1;
       if (low && h->split_tiles > 0 && atiles - done >= h->split_tiles + h->split_min_rest) {
-        CKE(syrk_trapezoid(h, A, lda, ntr, n1, ac, J, w, T, 1, done, h->split_tiles, wn));
+        CKE(syrk_trapezoid(h, E, A, lda, ntr, n1, ac, J, w, T, 1, done, h->split_tiles, wn));
         done += h->split_tiles;
-        CKE(syrk_trapezoid(h, A, lda, ntr, n1, ac, J, w, T, 0, done, atiles, wn));
+        CKE(syrk_trapezoid(h, E, A, lda, ntr, n1, ac, J, w, T, 0, done, atiles, wn));
       } else if (atiles > done) {
-        CKE(syrk_trapezoid(h, A, lda, ntr, n1, ac, J, w, T, low, done, atiles, wn));
+        CKE(syrk_trapezoid(h, E, A, lda, ntr, n1, ac, J, w, T, low, done, atiles, wn));
       }
       if (nxn) CKE(ext_edges(n1, wn));
-      CKE(chol_panel(h, A, lda, ntr, n1, wn, P, nxn));
+      CKE(chol_panel(h, E, A, lda, ntr, n1, wn, P, nxn));
       J = n1;
       w = wn;
       nx_cur = nxn;
@@ -941,7 +984,7 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
           if (tp_slot >= 0) CKE(hipStreamWriteValue32(T, h->sig_dev + tp_slot, h->sig_epoch, 0));
           else CKE(hand_off(h, T, P));
         }
-        CKE(syrk_trapezoid(h, A, lda, ntr, n1, 1, J, w, P));
+        CKE(syrk_trapezoid(h, E, A, lda, ntr, n1, 1, J, w, P));
       }
       if (wn > 1) {
         // One workgroup per CU for problems of up to 48 tile columns: the chain's next leaf needs a CU to itself, and with two
@@ -949,7 +992,7 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
         // at N = 8192).  Beyond that the update itself takes so much longer at half occupancy that N >= 8192 loses 1.5-2 % (the
         // chain waits for THIS launch at those steps, not for the leaf); N <= 6144 gains 0.7-1 %.  Scheduling only.
         const int a2low = ntc <= 48 ? 1 : 0;
-        CKE(syrk_trapezoid(h, A, lda, ntr, n1 + 1, wn - 1, J, w, T, a2low));
+        CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + 1, wn - 1, J, w, T, a2low));
         if (h->test_drop_signal && h->use_smo >= 2 && h->sig_next < SIG_SLOTS) {
           // test hook (option 28): this edge's slot is never written -- the panel stream's poll has to give up
           h->test_drop_signal = 0;
@@ -966,7 +1009,7 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
         h->wait_col = n1;
       }
     } else if (wn - nx_cur > 0) {
-      CKE(syrk_trapezoid(h, A, lda, ntr, n1 + nx_cur, wn - nx_cur, J, w, T));
+      CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + nx_cur, wn - nx_cur, J, w, T));
     }
     // (b) the rest of the trailing matrix, concurrently with that panel factorisation; once the panel chain is the
     // critical path the bulk update runs one workgroup per CU so that a leaf / strip workgroup fits beside it everywhere.
@@ -979,27 +1022,27 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
     if (bulk && P != T && nxn && h->use_smo >= 2) {
       // an extended panel follows: its chain polls for the bulk update of column n1 + wn in its middle -- that column first,
       // the signal, then the rest (the same tiles on the same kernels as one launch would give them: same bits)
-      CKE(syrk_trapezoid(h, A, lda, ntr, n1 + wn, 1, J, w, T, low));
+      CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + wn, 1, J, w, T, low));
       CKE(ext_edges(n1, wn));
       ext_done = true;
-      if (bc > 1) CKE(syrk_trapezoid(h, A, lda, ntr, n1 + wn + 1, bc - 1, J, w, T, low));
+      if (bc > 1) CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + wn + 1, bc - 1, J, w, T, low));
     } else if (bulk && P != T) {
       // Early super-panels are bound by the bulk update, not by the chain (the panel stream idles for most of it): only the
       // first split_tiles tiles run one workgroup per CU -- the mode that leaves every CU room for the chain's leaf /
       // strip / in-panel workgroups (and costs the kernel 5 % even alone) -- and the rest runs two per CU once the chain is through
       // (same tiles, same kernels: bit-identical results).  split_tiles ~ what the update gets done while a chain runs.
       if (low && h->split_tiles > 0 && btiles >= h->split_tiles + h->split_min_rest) {
-        CKE(syrk_trapezoid(h, A, lda, ntr, n1 + wn, bc, J, w, T, 1, 0, h->split_tiles));
-        CKE(syrk_trapezoid(h, A, lda, ntr, n1 + wn, bc, J, w, T, 0, h->split_tiles, btiles));
+        CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + wn, bc, J, w, T, 1, 0, h->split_tiles));
+        CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + wn, bc, J, w, T, 0, h->split_tiles, btiles));
       } else {
-        CKE(syrk_trapezoid(h, A, lda, ntr, n1 + wn, bc, J, w, T, low));
+        CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + wn, bc, J, w, T, low));
       }
     }
     // (an extended panel writes column n1 + wn: in every schedule BEHIND this step's bulk update of that column)
-    if (bulk && P == T && nxn) CKE(syrk_trapezoid(h, A, lda, ntr, n1 + wn, ntc - n1 - wn, J, w, T, 0));
+    if (bulk && P == T && nxn) CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + wn, ntc - n1 - wn, J, w, T, 0));
     if (nxn && !ext_done) CKE(ext_edges(n1, wn));
-    CKE(chol_panel(h, A, lda, ntr, n1, wn, P, nxn));
-    if (bulk && P == T && !nxn) CKE(syrk_trapezoid(h, A, lda, ntr, n1 + wn, ntc - n1 - wn, J, w, T, 0));
+    CKE(chol_panel(h, E, A, lda, ntr, n1, wn, P, nxn));
+    if (bulk && P == T && !nxn) CKE(syrk_trapezoid(h, E, A, lda, ntr, n1 + wn, ntc - n1 - wn, J, w, T, 0));
     J = n1;
     w = wn;
     nx_cur = nxn;
@@ -1010,7 +1053,7 @@ static hipError_t cholesky_enqueue(mi_gp_handle* h, double* A, long lda, int ntr
 
 // Kernels of one evaluation: assembly, factorisation of the augmented trapezoid [[K],[y^T]] (L ends
 // up in K_dev, beta = L^-1 y in row np), reduction.
-static int enqueue_factor(mi_gp_handle* h, int noise_form, bool prof) {
+static int enqueue_factor(mi_gp_handle* h, const Eval& E, int noise_form, bool prof) {
   // Two-stream evaluations (round 6): the evaluation's first two kernels go to the PANEL stream, so that the first leaf follows the
   // assembly in stream order instead of behind a cross-stream edge (~10 us: N = 1024 0.335 -> 0.308 ms, 2048 0.651 -> 0.605; from 32
   // tile columns on, where a panel and not a column comes first, it is 0.1-0.4 %: N = 4096 1.411 -> 1.405, LML + gradient 2.515 -> 2.473).
@@ -1018,7 +1061,7 @@ static int enqueue_factor(mi_gp_handle* h, int noise_form, bool prof) {
   // end otherwise), and every API call ends with both streams drained.  Same launches: scheduling only.  (The rule is
   // cholesky_enqueue's.)
   {
-    const int nb_ = h->btp ? h->btp->nb : 1;
+    const int nb_ = E.bt.nb;
     const bool la_ = h->lookahead == 2 || (h->lookahead == 1 && h->ntc >= lookahead_min_tiles(h, h->ntc)) ||
                      (h->lookahead == 1 && nb_ >= 2 && h->ntc >= (nb_ >= 8 ? 20 : 24));
     h->asm_on_panel = la_ && h->start_on_panel;
@@ -1026,35 +1069,35 @@ static int enqueue_factor(mi_gp_handle* h, int noise_form, bool prof) {
   const hipStream_t s0 = h->asm_on_panel ? h->pstream : h->stream;
   if (prof) (void)hipEventRecord(h->ev[0], s0);
   // first kernel of the evaluation: y rows, the bad-pivot word, and theta from the pinned host buffer to theta_dev
-  HCK(launch_set_yrows(h->buf.K_dev, h->buf.lda, h->np, h->np, h->buf.y_dev, h->n, s0, h->info_dev, h->theta_host,
-                       h->theta_dev, h->ntheta, h->btp), "set_yrows");
+  HCK(launch_set_yrows(E.K, h->buf.lda, h->np, h->np, h->buf.y_dev, h->n, s0, E.s.info_dev, E.s.theta_host,
+                       E.s.theta_dev, h->ntheta, E.lb()), "set_yrows");
   // (Until round 6 evaluations of 96 tile columns and more assembled the first super-panel's columns first and the rest one
   // workgroup per CU beside its factorisation, option 24: with the faster assembly it measured level to 0.5 % behind one launch at
   // N = 12288 .. 20480 and 0.8 % behind at N = 8192, profiles/NOTES_r06.md -- removed.)
-  HCK(launch_assemble(h->spec, h->theta_dev, h->buf.X_dev, h->n, h->buf.X_dev, h->n, h->buf.K_dev, h->buf.lda, h->np,
-                      h->np, 1, noise_form, s0, 0, h->diag_dev, h->btp), "assemble");
+  HCK(launch_assemble(h->spec, E.s.theta_dev, h->buf.X_dev, h->n, h->buf.X_dev, h->n, E.K, h->buf.lda, h->np,
+                      h->np, 1, noise_form, s0, 0, h->diag_dev, E.lb()), "assemble");
   if (prof) (void)hipEventRecord(h->ev[1], s0);
-  HCK(cholesky(h, h->buf.K_dev, h->buf.lda, h->ntc + 1, h->ntc), "cholesky");
+  HCK(cholesky(h, E, E.K, h->buf.lda, h->ntc + 1, h->ntc), "cholesky");
   if (prof) (void)hipEventRecord(h->ev[2], h->stream);
   // the scalars go straight to the pinned host buffer (device-visible): no download launch behind the reduction
   h->eval_seq += 1.0;  // (exact in a double for 2^53 evaluations)
-  HCK(launch_lml_reduce(h->buf.K_dev, h->buf.lda, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, h->out_host, h->stream, h->info_dev,
-                        h->btp, h->lr_part_dev, h->lr_sync_dev, h->eval_seq), "lml_reduce");
+  HCK(launch_lml_reduce(E.K, h->buf.lda, E.K + (long)h->np * h->buf.lda, h->n, E.s.out_host, h->stream, E.s.info_dev,
+                        E.lb(), E.s.lr_part_dev, E.s.lr_sync_dev, h->eval_seq), "lml_reduce");
   if (prof) (void)hipEventRecord(h->ev[3], h->stream);
   return 0;
 }
 
-static int enqueue_gradient(mi_gp_handle* h, bool prof);
-static hipError_t inverse_transpose(mi_gp_handle* h);
+static int enqueue_gradient(mi_gp_handle* h, const Eval& E, bool prof);
+static hipError_t inverse_transpose(mi_gp_handle* h, const Eval& E);
 
-static int enqueue_all(mi_gp_handle* h, int what, bool prof) {
+static int enqueue_all(mi_gp_handle* h, const Eval& E, int what, bool prof) {
   h->u_leaf_done = 0;
   for (int& v : h->u_node_done) v = 0;
   // (from 64 tile columns on: N = 8192 LML + gradient 11.17 -> 10.98 ms, N = 16384 69.81 -> 69.40; at N = 4096 the main stream
   // has no idle time to fill in those steps: 2.74 -> 2.81)
-  h->u_early = what == 2 && !h->btp && h->u_early_max_s > 0 && h->ntc >= 64 && h->buf.Z_dev && h->buf.W_dev;
-  if (int r = enqueue_factor(h, what == 1 ? 1 : 0, prof)) return r;
-  if (what == 2) return enqueue_gradient(h, prof);
+  h->u_early = what == 2 && !E.batched && h->u_early_max_s > 0 && h->ntc >= 64 && E.Z && E.W;
+  if (int r = enqueue_factor(h, E, what == 1 ? 1 : 0, prof)) return r;
+  if (what == 2) return enqueue_gradient(h, E, prof);
   return 0;
 }
 
@@ -1064,13 +1107,13 @@ static int enqueue_all(mi_gp_handle* h, int what, bool prof) {
 // heuristic made the timing depend on the instantiation, and the HIP runtime of this stack crashes in
 // hip::Graph::UpdateStreams when executable graphs of two-stream captures come and go
 // (profiles/r02_hipgraph_updatestreams_segv.txt; tools/stress_handles.py reproduced it in seconds) -- removed.
-static int run_evaluation(mi_gp_handle* h, int what) {
-  const bool prof = h->prof_level >= 1;
+static int run_evaluation(mi_gp_handle* h, const Eval& E, int what) {
+  const bool prof = E.prof >= 1;
   h->gemm_ev_used = 0;
   h->gemm_flops_acc = 0.0;
   // theta travels inside the first kernel (set_yrows_kernel); the scalars and the gradient are written to pinned host
   // memory by the kernels that produce them: no copy launches
-  return enqueue_all(h, what, prof);
+  return enqueue_all(h, E, what, prof);
 }
 
 // A poll of the last evaluation ran into its limit: the factor is unsynchronised garbage.  The reference's evaluations never
@@ -1103,16 +1146,17 @@ static int poll_timeout(mi_gp_handle* h, int attempt) {
 // the same stream (in order); the paths that need idle streams (time-outs, the epoch wrap, profiling events, destruction)
 // synchronise them themselves; every 256th spin synchronises the stream all the same (keeps the runtime's bookkeeping of
 // completed launches short).  The panel stream is idle by then: the main stream's last kernels wait for it.
-static hipError_t wait_evaluation(mi_gp_handle* h, int what, int k, bool prof) {
+static hipError_t wait_evaluation(mi_gp_handle* h, const Eval& E, int what) {
   bool seen = false;
-  if (h->spin_us > 0 && !prof && h->spin_backoff == 0) {
+  const int k = E.bt.nb;
+  if (h->spin_us > 0 && E.prof < 1 && h->spin_backoff == 0) {
     long long want;
     memcpy(&want, &h->eval_seq, sizeof(want));
-    const double* f = h->out_host + (what == 2 ? 5 : 4);
+    const double* f = E.s.out_host + (what == 2 ? 5 : 4);
     const auto t0 = std::chrono::steady_clock::now();
     int p = 0;
     for (unsigned it = 1;; ++it) {
-      while (p < k && __atomic_load_n(reinterpret_cast<const long long*>(f + 16 * p), __ATOMIC_ACQUIRE) == want) ++p;
+      while (p < k && __atomic_load_n(reinterpret_cast<const long long*>(f + (long)E.bt.sout * p), __ATOMIC_ACQUIRE) == want) ++p;
       if (p == k) { seen = true; break; }
       __builtin_ia32_pause();
       if ((it & 63u) == 0 && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > h->spin_us) break;
@@ -1138,18 +1182,18 @@ static int factor_internal(mi_gp_handle* h, const double* theta, int what) {
   HCK(hipSetDevice(h->device), "hipSetDevice");
   for (int i = 0; i < h->ntheta; ++i) {
     if (!std::isfinite(theta[i])) { snprintf(h->err, sizeof(h->err), "theta[%d] is not finite", i); return -1; }
-    h->theta_host[i] = theta[i];
+    h->one.theta_host[i] = theta[i];
   }
-  const bool prof = h->prof_level >= 1;
+  const Eval E = one_eval(h);
   for (int attempt = 0;; ++attempt) {
     const auto t_enq0 = std::chrono::steady_clock::now();
-    if (int r = run_evaluation(h, what)) return r;
+    if (int r = run_evaluation(h, E, what)) return r;
     h->t_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enq0).count();
-    HCK(wait_evaluation(h, what, 1, prof), "stream sync");
-    if ((int)h->out_host[3] != SIGNAL_TIMEOUT_INFO) break;
+    HCK(wait_evaluation(h, E, what), "stream sync");
+    if ((int)h->one.out_host[3] != SIGNAL_TIMEOUT_INFO) break;
     if (int r = poll_timeout(h, attempt)) return r;
   }
-  if (prof) {
+  if (E.prof >= 1) {
     float ms;
     (void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]); h->t_assemble_ms = ms;
     (void)hipEventElapsedTime(&ms, h->ev[1], h->ev[2]); h->t_chol_ms = ms;
@@ -1173,7 +1217,7 @@ static int factor_internal(mi_gp_handle* h, const double* theta, int what) {
       (void)hipEventElapsedTime(&ms, h->ev[6], h->ev[7]); h->t_contract_ms = ms;
     }
   }
-  const int info = (int)h->out_host[3];  // forwarded by lml_reduce_kernel (reset by set_yrows_kernel)
+  const int info = (int)h->one.out_host[3];  // forwarded by lml_reduce_kernel (reset by set_yrows_kernel)
   if (info != 0x7f7f7f7f) return info;  // 1-based index of the first bad pivot
   return 0;
 }
@@ -1183,14 +1227,14 @@ extern "C" int mi_gp_lml(mi_gp_handle* h, const double* theta, double* lml_out) 
   const int r = factor_internal(h, theta, 0);
   if (r < 0) return r;
   if (r > 0) { *lml_out = -INFINITY; return r; }
-  *lml_out = h->out_host[0];
+  *lml_out = h->one.out_host[0];
   return 0;
 }
 
 extern "C" int mi_gp_lml_parts(mi_gp_handle* h, double* logdet, double* quad) {
   if (!h) return -1;
-  if (logdet) *logdet = h->out_host[1];
-  if (quad) *quad = h->out_host[2];
+  if (logdet) *logdet = h->one.out_host[1];
+  if (quad) *quad = h->one.out_host[2];
   return 0;
 }
 
@@ -1211,7 +1255,7 @@ extern "C" int mi_gp_timers(mi_gp_handle* h, double* out, int n) {
 // then Kinv = U U^T (lower tiles, W_dev), alpha = U beta, and the contraction kernel.
 // single_form: a batched launch takes the tile form (64x64 / 128x128) that the same product of ONE problem takes -- a rule of the
 // shape, not of the batch size (gemm_uses_small_tiles counts tiles x batch)
-static hipError_t gemm_call(mi_gp_handle* h, int ak, int bk, const double* A, long lda, long sA, const double* B, long ldb,
+static hipError_t gemm_call(mi_gp_handle* h, const Eval& E, int ak, int bk, const double* A, long lda, long sA, const double* B, long ldb,
                             long sB, double* C, long ldc, long sC, int mt, int nt, int k, int tri, int kmode,
                             double alpha, double beta, int batch, long zA = 0, long zB = 0, long zC = 0, bool single_form = false) {
   GemmParams p;
@@ -1219,11 +1263,11 @@ static hipError_t gemm_call(mi_gp_handle* h, int ak, int bk, const double* A, lo
   p.strideA = sA; p.strideB = sB; p.strideC = sC;
   p.mt = mt; p.nt = nt; p.k = k; p.tri = tri; p.kmode = kmode; p.alpha = alpha; p.beta = beta;
   p.small_below = h->small_below; p.band = h->band_rows; p.tail_small = h->tail_small;
-  if (h->btp && single_form) p.small_below = gemm_uses_small_tiles(p, batch) ? 0x7fffffff : 0;
-  if (h->btp) {  // batched evaluation: the problems are the second batch level (zA / zB / zC: the strides of the matrices A, B, C live in)
+  if (E.batched && single_form) p.small_below = gemm_uses_small_tiles(p, batch) ? 0x7fffffff : 0;
+  if (E.batched) {  // batched evaluation: the problems are the second batch level (zA / zB / zC: the strides of the matrices A, B, C live in)
     p.batch1 = batch;
     p.strideA2 = zA; p.strideB2 = zB; p.strideC2 = zC;
-    batch *= h->btp->nb;
+    batch *= E.bt.nb;
   }
   return launch_gemm_f64(p, ak, bk, batch, h->stream);
 }
@@ -1232,24 +1276,24 @@ static hipError_t gemm_call(mi_gp_handle* h, int ak, int bk, const double* A, lo
 // not done yet (u_leaf_done / u_node_done): level s (nodes of 2 s tiles, li = log2 s) needs its nodes' halves -- full nodes of
 // level s / 2 -- done.  Called with growing final_cols inside the factorisation's tail (cholesky()) and once with everything
 // from inverse_transpose(); the node batches are split differently, the per-tile arithmetic is the same.
-static hipError_t u_levels(mi_gp_handle* h, int final_cols, int max_s) {
-  const double* L = h->buf.K_dev;
-  double* U = h->buf.Z_dev;
-  double* T = h->buf.W_dev;
+static hipError_t u_levels(mi_gp_handle* h, const Eval& E, int final_cols, int max_s) {
+  const double* L = E.K;
+  double* U = E.Z;
+  double* T = E.W;
   const long ld = h->buf.lda;
   const int ntc = h->ntc;
-  const long zK = h->btp ? h->btp->sK : 0, zZ = h->btp ? h->btp->sZ : 0, zW = h->btp ? h->btp->sW : 0;
+  const long zK = E.bt.sK, zZ = E.bt.sZ, zW = E.bt.sW;
   hipError_t e;
   if (final_cols > ntc) final_cols = ntc;
   if (final_cols > h->u_leaf_done) {
     if (h->u_leaf_done == 0) {
-      e = launch_set_identity_blocks(U, ld, ntc, h->stream, h->btp);
+      e = launch_set_identity_blocks(U, ld, ntc, h->stream, E.lb());
       if (e != hipSuccess) return e;
     }
     // leaves: X L_kk^T = I  ->  X = L_kk^-T
     const int c0 = h->u_leaf_done;
-    e = launch_trsm_strip128_batched(h->dinv_dev + (size_t)c0 * MINV_ELEMS, U + (long)c0 * (128 * ld + 128), ld, 128 * ld + 128, 128,
-                                     final_cols - c0, h->stream, h->btp, zZ);
+    e = launch_trsm_strip128_batched(E.s.dinv_dev + (size_t)c0 * MINV_ELEMS, U + (long)c0 * (128 * ld + 128), ld, 128 * ld + 128, 128,
+                                     final_cols - c0, h->stream, E.lb(), zZ);
     if (e != hipSuccess) return e;
     h->u_leaf_done = final_cols;
   }
@@ -1268,27 +1312,27 @@ static hipError_t u_levels(mi_gp_handle* h, int final_cols, int max_s) {
     double* P = T + off + (long)s * 128;
     double* U12 = U + off + (long)s * 128;
     // P = U11 L21^T   (U11 upper triangular: k >= row tile)
-    e = gemm_call(h, 0, 0, U11, ld, node, L21, ld, node, P, ld, node, s, s, s * 128, 0, 3, 1.0, 0.0, batch, zZ, zK, zW);
+    e = gemm_call(h, E, 0, 0, U11, ld, node, L21, ld, node, P, ld, node, s, s, s * 128, 0, 3, 1.0, 0.0, batch, zZ, zK, zW);
     if (e != hipSuccess) return e;
     // U12 = -P U22    (U22 upper triangular: k <= column tile)
-    e = gemm_call(h, 0, 1, P, ld, node, U22, ld, node, U12, ld, node, s, s, s * 128, 0, 4, -1.0, 0.0, batch, zW, zZ, zZ);
+    e = gemm_call(h, E, 0, 1, P, ld, node, U22, ld, node, U12, ld, node, s, s, s * 128, 0, 4, -1.0, 0.0, batch, zW, zZ, zZ);
     if (e != hipSuccess) return e;
     h->u_node_done[li] = avail;
   }
   return hipSuccess;
 }
 
-static hipError_t inverse_transpose(mi_gp_handle* h) {
-  const double* L = h->buf.K_dev;
-  double* U = h->buf.Z_dev;
-  double* T = h->buf.W_dev;
+static hipError_t inverse_transpose(mi_gp_handle* h, const Eval& E) {
+  const double* L = E.K;
+  double* U = E.Z;
+  double* T = E.W;
   const long ld = h->buf.lda;
   const int ntc = h->ntc;
-  const long zK = h->btp ? h->btp->sK : 0, zZ = h->btp ? h->btp->sZ : 0, zW = h->btp ? h->btp->sW : 0;
+  const long zK = E.bt.sK, zZ = E.bt.sZ, zW = E.bt.sW;
   // every full node of every level (what the factorisation's tail has not done already), then the trailing partial nodes
   // level by level: a partial node's first half is a full node of the level below, its second half is built by the partial
   // nodes of the levels below
-  hipError_t e = u_levels(h, ntc, 1 << 30);
+  hipError_t e = u_levels(h, E, ntc, 1 << 30);
   if (e != hipSuccess) return e;
   for (int s = 1; s < ntc; s *= 2) {
     const int nfull = ntc / (2 * s);             // nodes whose second half is complete
@@ -1302,29 +1346,29 @@ static hipError_t inverse_transpose(mi_gp_handle* h) {
     const double* L21 = L + off + (long)s * 128 * ld;
     double* P = T + off + (long)s * 128;
     double* U12 = U + off + (long)s * 128;
-    e = gemm_call(h, 0, 0, U11, ld, node, L21, ld, node, P, ld, node, s, s2, s * 128, 0, 3, 1.0, 0.0, 1, zZ, zK, zW);
+    e = gemm_call(h, E, 0, 0, U11, ld, node, L21, ld, node, P, ld, node, s, s2, s * 128, 0, 3, 1.0, 0.0, 1, zZ, zK, zW);
     if (e != hipSuccess) return e;
-    e = gemm_call(h, 0, 1, P, ld, node, U22, ld, node, U12, ld, node, s, s2, s2 * 128, 0, 4, -1.0, 0.0, 1, zW, zZ, zZ);
+    e = gemm_call(h, E, 0, 1, P, ld, node, U22, ld, node, U12, ld, node, s, s2, s2 * 128, 0, 4, -1.0, 0.0, 1, zW, zZ, zZ);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
 // everything after the factorisation: U = L^-T, Kinv = U U^T, alpha = U beta, contraction, download
-static int enqueue_gradient(mi_gp_handle* h, bool prof) {
+static int enqueue_gradient(mi_gp_handle* h, const Eval& E, bool prof) {
   if (prof) (void)hipEventRecord(h->ev[4], h->stream);
-  HCK(inverse_transpose(h), "inverse_transpose");
+  HCK(inverse_transpose(h, E), "inverse_transpose");
   if (prof) (void)hipEventRecord(h->ev[5], h->stream);
   const long ld = h->buf.lda;
   // Kinv = U U^T, lower tiles only, k >= row tile
-  const long zZ = h->btp ? h->btp->sZ : 0, zW = h->btp ? h->btp->sW : 0;
-  HCK(gemm_call(h, 0, 0, h->buf.Z_dev, ld, 0, h->buf.Z_dev, ld, 0, h->buf.W_dev, ld, 0, h->ntc, h->ntc, h->np, 1, 3, 1.0,
+  const long zZ = E.bt.sZ, zW = E.bt.sW;
+  HCK(gemm_call(h, E, 0, 0, E.Z, ld, 0, E.Z, ld, 0, E.W, ld, 0, h->ntc, h->ntc, h->np, 1, 3, 1.0,
                 0.0, 1, zZ, zZ, zW), "lauum");
   if (prof) (void)hipEventRecord(h->ev[6], h->stream);
-  HCK(launch_trmv_upper(h->buf.Z_dev, ld, h->buf.K_dev + (long)h->np * ld, h->n, h->alpha_dev, h->stream, h->btp), "trmv");
+  HCK(launch_trmv_upper(E.Z, ld, E.K + (long)h->np * ld, h->n, E.s.alpha_dev, h->stream, E.lb()), "trmv");
   // the final reduction writes the gradient straight into the handle's pinned host buffer (device-visible)
-  HCK(launch_grad_contract(h->spec, h->theta_dev, h->buf.X_dev, h->n, h->buf.W_dev, ld, h->alpha_dev, h->part_dev,
-                           h->grad_host, h->stream, h->btp, h->lr_sync_dev + (h->btp ? h->btp->nb : 1), h->out_host + 5, h->eval_seq),
+  HCK(launch_grad_contract(h->spec, E.s.theta_dev, h->buf.X_dev, h->n, E.W, ld, E.s.alpha_dev, E.s.part_dev,
+                           E.s.grad_host, h->stream, E.lb(), E.s.lr_sync_dev + E.bt.nb, E.s.out_host + 5, h->eval_seq),
       "grad_contract");
   if (prof) (void)hipEventRecord(h->ev[7], h->stream);
   return 0;
@@ -1342,8 +1386,8 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
   if (r < 0) return r;
   for (int i = 0; i < h->ntheta; ++i) grad_out[i] = 0.0;
   if (r > 0) { *lml_out = -INFINITY; return r; }
-  *lml_out = h->out_host[0];
-  for (int i = 0; i < h->ntheta; ++i) grad_out[i] = h->grad_host[i];
+  *lml_out = h->one.out_host[0];
+  for (int i = 0; i < h->ntheta; ++i) grad_out[i] = h->one.grad_host[i];
   h->have_kinv = true;
   return 0;
 }
@@ -1356,7 +1400,7 @@ extern "C" int mi_gp_alpha(mi_gp_handle* h, double* alpha_host) {
   if (!h || !alpha_host) return -1;
   if (!h->have_kinv) { snprintf(h->err, sizeof(h->err), "mi_gp_alpha: call mi_gp_lml_grad first"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  HCK(hipMemcpyAsync(alpha_host, h->alpha_dev, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream), "alpha download");
+  HCK(hipMemcpyAsync(alpha_host, h->one.alpha_dev, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream), "alpha download");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
   return 0;
 }
@@ -1374,7 +1418,7 @@ extern "C" int mi_gp_grad_x(mi_gp_handle* h, double* gx_dev) {
     HCK(hipMalloc(&h->gxs_dev, sizeof(double) * gxs_need), "grad_x scratch");
     h->gxs_elems = gxs_need;
   }
-  HCK(launch_grad_x(h->spec, h->theta_dev, h->buf.X_dev, h->n, h->buf.W_dev, h->buf.lda, h->alpha_dev, gx_dev,
+  HCK(launch_grad_x(h->spec, h->one.theta_dev, h->buf.X_dev, h->n, h->buf.W_dev, h->buf.lda, h->one.alpha_dev, gx_dev,
                     nsplit > 1 ? h->gxs_dev : nullptr, h->stream), "grad_x");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
   return 0;
@@ -1406,106 +1450,48 @@ extern "C" int mi_gp_set_batch(mi_gp_handle* h, const mi_gp_batch_buffers* b) {
     return -1;
   }
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  if (b->count > h->batch_cap) {
+  if (b->count > h->batch.k) {
     (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(h->b_theta_dev); (void)hipFree(h->b_dinv_dev); (void)hipFree(h->b_alpha_dev); (void)hipFree(h->b_part_dev);
-    (void)hipFree(h->b_info_dev); (void)hipFree(h->b_lr_part_dev); (void)hipFree(h->b_lr_sync_dev);
-    h->b_lr_part_dev = nullptr; h->b_lr_sync_dev = nullptr;
-    if (h->b_grad_host) (void)hipHostFree(h->b_grad_host);
-    if (h->b_out_host) (void)hipHostFree(h->b_out_host);
-    if (h->b_theta_host) (void)hipHostFree(h->b_theta_host);
-    h->b_theta_dev = h->b_dinv_dev = h->b_alpha_dev = h->b_part_dev = h->b_grad_host = h->b_out_host = h->b_theta_host = nullptr;
-    h->b_info_dev = nullptr;
-    h->batch_cap = 0;
-    const size_t k = (size_t)b->count;
-    HCK(hipMalloc(&h->b_theta_dev, sizeof(double) * k * h->ntheta), "batch scratch");
-    HCK(hipMalloc(&h->b_dinv_dev, sizeof(double) * k * MINV_ELEMS * (size_t)(h->ntc + 4)), "batch scratch");
-    HCK(hipMalloc(&h->b_alpha_dev, sizeof(double) * k * h->np), "batch scratch");
-    HCK(hipMalloc(&h->b_part_dev, sizeof(double) * k * (size_t)grad_contract_blocks(h->n) * h->ntheta), "batch scratch");
-    HCK(hipMalloc(&h->b_info_dev, sizeof(int) * 4 * k), "batch scratch");
-    HCK(hipMalloc(&h->b_lr_part_dev, sizeof(double) * 2 * LML_REDUCE_BLOCKS * k), "batch scratch");
-    HCK(hipMalloc(&h->b_lr_sync_dev, sizeof(unsigned) * 2 * k), "batch scratch");  // [0, k) lml_reduce's tickets, [k, 2k) grad_final's
-    HCK(hipMemset(h->b_lr_sync_dev, 0, sizeof(unsigned) * 2 * k), "batch scratch");
-    HCK(hipHostMalloc(&h->b_grad_host, sizeof(double) * k * h->ntheta), "batch scratch");
-    HCK(hipHostMalloc(&h->b_out_host, sizeof(double) * 16 * k), "batch scratch");
-    memset(h->b_out_host, 0, sizeof(double) * 16 * k);
-    HCK(hipHostMalloc(&h->b_theta_host, sizeof(double) * k * h->ntheta), "batch scratch");
-    h->batch_cap = b->count;
+    free_scratch(h->batch);
+    HCK(alloc_scratch(h, h->batch, b->count, h->n), "batch scratch");
   }
   h->bbuf = *b;
   h->b_cond_k = 0;
   return 0;
 }
 
-// strides of a batch of k problems in the batch buffers / scratch (h->bt; swork is the caller's, mi_gp_predict_batch)
-static void set_batch_strides(mi_gp_handle* h, int k) {
-  h->bt = Batch();
-  h->bt.nb = k;
-  h->bt.sK = h->bbuf.stride_k; h->bt.sZ = h->bt.sW = h->bbuf.stride_zw;
-  h->bt.sdinv = (long)MINV_ELEMS * (h->ntc + 4); h->bt.salpha = h->np;
-  h->bt.spart = (long)grad_contract_blocks(h->n) * h->ntheta;
-  h->bt.stheta = h->ntheta; h->bt.sinfo = 4; h->bt.sout = 16;
-}
-
 // what: 0 LML, 1 the conditional's factors (mi_gp_factor_batch: they stay in the batch buffers), 2 LML + gradient.
 // info_out[p]: 0, or the 1-based index of problem p's first bad pivot (its LML is -inf then).  lml_out may be null.
 static int batch_internal(mi_gp_handle* h, int k, const double* thetas, int what, double* lml_out, double* grad_out, int* info_out) {
-  if (!h->have_data || h->batch_cap < 1) { snprintf(h->err, sizeof(h->err), "call mi_gp_set_data and mi_gp_set_batch first"); return -1; }
+  if (!h->have_data || h->batch.k < 1) { snprintf(h->err, sizeof(h->err), "call mi_gp_set_data and mi_gp_set_batch first"); return -1; }
   if (k < 1 || k > h->bbuf.count) { snprintf(h->err, sizeof(h->err), "batch of %d problems, buffers for %d", k, h->bbuf.count); return -1; }
   if (what == 2 && (!h->bbuf.Z_dev || !h->bbuf.W_dev)) { snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad_batch needs Z_dev and W_dev in mi_gp_set_batch"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
+  const Scratch& s = h->batch;
   for (int i = 0; i < k * h->ntheta; ++i) {
     if (!std::isfinite(thetas[i])) { snprintf(h->err, sizeof(h->err), "theta[%d] of problem %d is not finite", i % h->ntheta, i / h->ntheta); return -1; }
-    h->b_theta_host[i] = thetas[i];
+    s.theta_host[i] = thetas[i];
   }
   h->factored = h->have_kinv = h->have_u = false;  // the single-evaluation state of the handle is not touched, but K_dev may alias
   h->b_cond_k = 0;
-  // point the evaluation at the batch's arrays, run the ordinary enqueue code with blockIdx.z = problem, restore
-  const mi_gp_buffers buf0 = h->buf;
-  double *theta_dev0 = h->theta_dev, *dinv0 = h->dinv_dev, *alpha0 = h->alpha_dev, *part0 = h->part_dev, *grad0 = h->grad_host,
-         *out0 = h->out_host, *thost0 = h->theta_host;
-  int* info0 = h->info_dev;
-  double* lrp0 = h->lr_part_dev;
-  unsigned* lrs0 = h->lr_sync_dev;
-  h->lr_part_dev = h->b_lr_part_dev; h->lr_sync_dev = h->b_lr_sync_dev;
-  h->buf.K_dev = h->bbuf.K_dev; h->buf.Z_dev = h->bbuf.Z_dev; h->buf.W_dev = h->bbuf.W_dev;
-  h->theta_dev = h->b_theta_dev; h->dinv_dev = h->b_dinv_dev; h->alpha_dev = h->b_alpha_dev; h->part_dev = h->b_part_dev;
-  h->grad_host = h->b_grad_host; h->out_host = h->b_out_host; h->theta_host = h->b_theta_host; h->info_dev = h->b_info_dev;
-  set_batch_strides(h, k);
-  h->btp = &h->bt;
-  const int prof0 = h->prof_level;
-  h->prof_level = 0;
-  int r = 0;
+  const Eval E = batch_eval(h, k);
   for (int attempt = 0;; ++attempt) {
-    r = run_evaluation(h, what);
-    if (r == 0) {
-      const hipError_t e = wait_evaluation(h, what, k, false);
-      if (e != hipSuccess) r = hfail(h, e, "stream sync");
-    }
-    if (r != 0) break;
+    if (int r = run_evaluation(h, E, what)) return r;
+    HCK(wait_evaluation(h, E, what), "stream sync");
     // a cross-stream poll that gave up leaves unsynchronised data behind in EVERY problem: the whole batch is evaluated again
     // with event edges (poll_timeout), or fails as a whole
     bool timed_out = false;
-    for (int p = 0; p < k; ++p) timed_out = timed_out || (int)h->out_host[16 * p + 3] == SIGNAL_TIMEOUT_INFO;
+    for (int p = 0; p < k; ++p) timed_out = timed_out || (int)s.out_host[E.bt.sout * p + 3] == SIGNAL_TIMEOUT_INFO;
     if (!timed_out) break;
-    r = poll_timeout(h, attempt);
-    if (r != 0) break;
+    if (int r = poll_timeout(h, attempt)) return r;
   }
-  h->prof_level = prof0;
-  h->btp = nullptr;
-  h->bt = Batch();
-  h->buf = buf0;
-  h->theta_dev = theta_dev0; h->dinv_dev = dinv0; h->alpha_dev = alpha0; h->part_dev = part0; h->grad_host = grad0;
-  h->out_host = out0; h->theta_host = thost0; h->info_dev = info0;
-  h->lr_part_dev = lrp0; h->lr_sync_dev = lrs0;
-  if (r != 0) return r;
   for (int p = 0; p < k; ++p) {
-    const int info = (int)h->b_out_host[16 * p + 3];
+    const int info = (int)s.out_host[E.bt.sout * p + 3];
     const bool ok = info == 0x7f7f7f7f;
     if (info_out) info_out[p] = ok ? 0 : info;
-    if (lml_out) lml_out[p] = ok ? h->b_out_host[16 * p] : -INFINITY;
+    if (lml_out) lml_out[p] = ok ? s.out_host[E.bt.sout * p] : -INFINITY;
     if (grad_out)
-      for (int i = 0; i < h->ntheta; ++i) grad_out[(size_t)p * h->ntheta + i] = ok ? h->b_grad_host[(size_t)p * h->ntheta + i] : 0.0;
+      for (int i = 0; i < h->ntheta; ++i) grad_out[(size_t)p * h->ntheta + i] = ok ? s.grad_host[(size_t)p * h->ntheta + i] : 0.0;
   }
   if (what == 1) h->b_cond_k = k;
   return 0;
@@ -1529,23 +1515,36 @@ extern "C" int mi_gp_factor(mi_gp_handle* h, const double* theta) {
   return r;
 }
 
-// solve X L^T = B in place for tile columns [c0, c0+w) of the mp x np work matrix (a batch, h->btp: every problem's, work
+// solve X L^T = B in place for tile columns [c0, c0+w) of the mp x np work matrix (a batch: every problem's, work
 // blocks bt.swork apart, L_p and its leaf inverses in the batch buffers; the GEMMs take the single problem's tile form)
-static hipError_t trsm_rec(mi_gp_handle* h, double* Bw, long ldw, int mp, int c0, int w) {
-  const double* L = h->buf.K_dev;
+static hipError_t trsm_rec(mi_gp_handle* h, const Eval& E, double* Bw, long ldw, int mp, int c0, int w) {
+  const double* L = E.K;
   const long lda = h->buf.lda;
-  const long zW = h->btp ? h->btp->swork : 0, zK = h->btp ? h->btp->sK : 0;
+  const long zW = E.bt.swork, zK = E.bt.sK;
   if (w == 1) {
-    return launch_trsm_strip128(h->dinv_dev + (size_t)c0 * MINV_ELEMS, Bw + (long)c0 * 128, ldw, mp, h->stream, h->btp, zW);
+    return launch_trsm_strip128(E.s.dinv_dev + (size_t)c0 * MINV_ELEMS, Bw + (long)c0 * 128, ldw, mp, h->stream, E.lb(), zW);
   }
   const int w1 = w / 2, w2 = w - w1;
-  hipError_t e = trsm_rec(h, Bw, ldw, mp, c0, w1);
+  hipError_t e = trsm_rec(h, E, Bw, ldw, mp, c0, w1);
   if (e != hipSuccess) return e;
   // B[:, c0+w1 : c0+w) -= X[:, c0 : c0+w1) * L[c0+w1 : c0+w, c0 : c0+w1)^T
-  e = gemm_call(h, 0, 0, Bw + (long)c0 * 128, ldw, 0, L + (long)(c0 + w1) * 128 * lda + (long)c0 * 128, lda, 0,
+  e = gemm_call(h, E, 0, 0, Bw + (long)c0 * 128, ldw, 0, L + (long)(c0 + w1) * 128 * lda + (long)c0 * 128, lda, 0,
                 Bw + (long)(c0 + w1) * 128, ldw, 0, mp / 128, w2, w1 * 128, 0, 0, -1.0, 1.0, 1, zW, zK, zW, true);
   if (e != hipSuccess) return e;
-  return trsm_rec(h, Bw, ldw, mp, c0 + w1, w2);
+  return trsm_rec(h, E, Bw, ldw, mp, c0 + w1, w2);
+}
+
+// mi_gp_predict's reduction over A (one row per point in work_dev) with the single problem's beta.  Stationary.diag == 1: the
+// composite diagonal is the +/* fold of kv; pred_noise adds sqrt(gv)^2
+static hipError_t predict_reduce(const mi_gp_handle* h, const double* work_dev, long ldw, int m, double* mean_dev, double* var_dev,
+                                 int pred_noise) {
+  const int nk = h->spec.nkern, d = h->spec.d;
+  const double* th = h->one.theta_host;
+  double kd = th[nk * d];
+  for (int c = 1; c < nk; ++c) kd = (h->spec.op[c - 1] == 0) ? kd + th[nk * d + c] : kd * th[nk * d + c];
+  const double sg = std::sqrt(th[nk * d + 2 * nk]);
+  return launch_predict_reduce(work_dev, ldw, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, m, kd, pred_noise ? sg * sg : 0.0,
+                               mean_dev, var_dev, h->stream);
 }
 
 extern "C" int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw,
@@ -1556,17 +1555,10 @@ extern "C" int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, dou
   HCK(hipSetDevice(h->device), "hipSetDevice");
   const int mp = (m + 127) / 128 * 128;
   // K(Xnew, X): one prediction point per row, zeros in the padding
-  HCK(launch_assemble(h->spec, h->theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, mp, h->np, 0, 0, h->stream),
+  HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, mp, h->np, 0, 0, h->stream),
       "assemble cross");
-  HCK(trsm_rec(h, work_dev, ldw, mp, 0, h->ntc), "trsm");
-  // Stationary.diag == 1: the composite diagonal is the +/* fold of kv; pred_noise adds sqrt(gv)^2
-  const int nk = h->spec.nkern, d = h->spec.d;
-  const double* th = h->theta_host;
-  double kd = th[nk * d];
-  for (int c = 1; c < nk; ++c) kd = (h->spec.op[c - 1] == 0) ? kd + th[nk * d + c] : kd * th[nk * d + c];
-  const double sg = std::sqrt(th[nk * d + 2 * nk]);
-  HCK(launch_predict_reduce(work_dev, ldw, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, m, kd,
-                            pred_noise ? sg * sg : 0.0, mean_dev, var_dev, h->stream), "predict_reduce");
+  HCK(trsm_rec(h, one_eval(h), work_dev, ldw, mp, 0, h->ntc), "trsm");
+  HCK(predict_reduce(h, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "predict_reduce");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
   return 0;
 }
@@ -1609,35 +1601,48 @@ extern "C" int mi_gp_predict_batch(mi_gp_handle* h, int k, const double* Xnew_de
     return -1;
   }
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  // point the solve at the batch's factors (as batch_internal does), run the single-problem code with blockIdx.z = problem, restore
-  const mi_gp_buffers buf0 = h->buf;
-  double* dinv0 = h->dinv_dev;
-  h->buf.K_dev = h->bbuf.K_dev;
-  h->dinv_dev = h->b_dinv_dev;
-  set_batch_strides(h, k);
-  h->bt.swork = stride_work;
-  h->btp = &h->bt;
-  Batch bw = h->bt;
+  // mi_gp_predict's steps on the batch's factors, blockIdx.z = problem
+  Eval E = batch_eval(h, k);
+  E.bt.swork = stride_work;
+  Batch bw = E.bt;
   bw.sK = stride_work;  // (the assembly writes the cross-covariance blocks: its output stride is the work blocks')
-  hipError_t e = launch_assemble(h->spec, h->b_theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, mp, h->np, 0, 0, h->stream,
-                                 -2147483647 - 1, nullptr, &bw);
-  const char* where = "assemble cross";
-  if (e == hipSuccess) { e = trsm_rec(h, work_dev, ldw, mp, 0, h->ntc); where = "trsm"; }
-  if (e == hipSuccess) {
-    e = launch_predict_reduce_batched(h->spec, h->b_theta_dev, work_dev, ldw, h->buf.K_dev + (long)h->np * h->buf.lda, h->b_info_dev,
-                                      h->n, m, pred_noise ? 1 : 0, mean_dev, var_dev, h->stream, h->bt);
-    where = "predict_reduce";
-  }
-  if (e == hipSuccess && mix_mean_dev) {
-    e = launch_mixture_moments(mean_dev, var_dev, m, k, h->b_info_dev, h->bt.sinfo, mix_mean_dev, mix_var_dev, h->stream);
-    where = "mixture";
-  }
-  h->btp = nullptr;
-  h->bt = Batch();
-  h->buf = buf0;
-  h->dinv_dev = dinv0;
-  if (e != hipSuccess) return hfail(h, e, where);
+  HCK(launch_assemble(h->spec, E.s.theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, mp, h->np, 0, 0, h->stream,
+                      -2147483647 - 1, nullptr, &bw), "assemble cross");
+  HCK(trsm_rec(h, E, work_dev, ldw, mp, 0, h->ntc), "trsm");
+  HCK(launch_predict_reduce_batched(h->spec, E.s.theta_dev, work_dev, ldw, E.K + (long)h->np * h->buf.lda, E.s.info_dev, h->n, m,
+                                    pred_noise ? 1 : 0, mean_dev, var_dev, h->stream, E.bt), "predict_reduce");
+  if (mix_mean_dev)
+    HCK(launch_mixture_moments(mean_dev, var_dev, m, k, E.s.info_dev, E.bt.sinfo, mix_mean_dev, mix_var_dev, h->stream), "mixture");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
+  return 0;
+}
+
+// U = L^-T in Z_dev and alpha = U beta, formed once per mi_gp_factor (mi_gp_predict_u / mi_gp_predict_grad)
+static int make_u_resident(mi_gp_handle* h) {
+  if (h->have_u) return 0;
+  HCK(inverse_transpose(h, one_eval(h)), "inverse_transpose");
+  HCK(launch_trmv_upper(h->buf.Z_dev, h->buf.lda, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, h->one.alpha_dev, h->stream), "trmv");
+  h->have_u = true;
+  return 0;
+}
+
+// mean / var at m points through U: K(X*, X) rows into the second ceil(m/128)*128 rows of work_dev, A = K(X*, X) U into the
+// first -- one triangular-k GEMM, or (per_point) one pass over U per point, A_p = U^T k*_p -- then mi_gp_predict's reduction
+static int predict_via_u(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw, double* mean_dev,
+                         double* var_dev, int pred_noise, bool per_point) {
+  const long ld = h->buf.lda;
+  const int mp = (m + 127) / 128 * 128;
+  double* krows = work_dev + (long)mp * ldw;
+  HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, krows, ldw, mp, h->np, 0, 0, h->stream),
+      "assemble cross");
+  if (per_point) {
+    for (int p = 0; p < m; ++p)
+      HCK(launch_trmv_upper_t(h->buf.Z_dev, ld, krows + (long)p * ldw, h->n, work_dev + (long)p * ldw, h->stream), "trmv_t");
+  } else {
+    HCK(gemm_call(h, one_eval(h), 0, 1, krows, ldw, 0, h->buf.Z_dev, ld, 0, work_dev, ldw, 0, mp / 128, h->ntc, h->np, 0, 4, 1.0,
+                  0.0, 1), "K* U");
+  }
+  HCK(predict_reduce(h, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "predict_reduce");
   return 0;
 }
 
@@ -1655,30 +1660,8 @@ extern "C" int mi_gp_predict_u(mi_gp_handle* h, const double* Xnew_dev, int m, d
   }
   if (ldw < h->np || (ldw & 1)) { snprintf(h->err, sizeof(h->err), "mi_gp_predict_u: ldw must be even and >= padded n"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  const long ld = h->buf.lda;
-  if (!h->have_u) {
-    HCK(inverse_transpose(h), "inverse_transpose");
-    HCK(launch_trmv_upper(h->buf.Z_dev, ld, h->buf.K_dev + (long)h->np * ld, h->n, h->alpha_dev, h->stream), "trmv");
-    h->have_u = true;
-  }
-  const int mp = (m + 127) / 128 * 128;
-  double* krows = work_dev + (long)mp * ldw;
-  HCK(launch_assemble(h->spec, h->theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, krows, ldw, mp, h->np, 0, 0, h->stream),
-      "assemble cross");
-  GemmParams p;
-  p.A = krows; p.B = h->buf.Z_dev; p.C = work_dev;
-  p.lda = ldw; p.ldb = ld; p.ldc = ldw;
-  p.strideA = p.strideB = p.strideC = 0;
-  p.mt = mp / 128; p.nt = h->ntc; p.k = h->np; p.tri = 0; p.kmode = 4; p.alpha = 1.0; p.beta = 0.0;
-  p.small_below = h->small_below; p.band = h->band_rows; p.tail_small = h->tail_small;
-  HCK(launch_gemm_f64(p, 0, 1, 1, h->stream), "K* U");
-  const int nk = h->spec.nkern, d = h->spec.d;
-  const double* th = h->theta_host;
-  double kd = th[nk * d];
-  for (int c = 1; c < nk; ++c) kd = (h->spec.op[c - 1] == 0) ? kd + th[nk * d + c] : kd * th[nk * d + c];
-  const double sg = std::sqrt(th[nk * d + 2 * nk]);
-  HCK(launch_predict_reduce(work_dev, ldw, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, m, kd,
-                            pred_noise ? sg * sg : 0.0, mean_dev, var_dev, h->stream), "predict_reduce");
+  if (int r = make_u_resident(h)) return r;
+  if (int r = predict_via_u(h, Xnew_dev, m, work_dev, ldw, mean_dev, var_dev, pred_noise, false)) return r;
   HCK(hipStreamSynchronize(h->stream), "stream sync");
   return 0;
 }
@@ -1703,37 +1686,18 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
   if (!Xnew_dev || !work_dev || !mean_dev || !var_dev || m <= 0) return -1;
   if (ldw < h->np || (ldw & 1)) { snprintf(h->err, sizeof(h->err), "mi_gp_predict_grad: ldw must be even and >= padded n"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
+  if (int r = make_u_resident(h)) return r;
+  // few points (BO refinement): with U resident, A_p = L^-1 k*_p = U^T k*_p is one pass over U per point instead of the
+  // ~250-launch blocked triangular solve
+  const int r = m <= 16 ? predict_via_u(h, Xnew_dev, m, work_dev, ldw, mean_dev, var_dev, pred_noise, true)
+                        : mi_gp_predict(h, Xnew_dev, m, work_dev, ldw, mean_dev, var_dev, pred_noise);
+  if (r != 0) return r;
   const long ld = h->buf.lda;
-  if (!h->have_u) {
-    HCK(inverse_transpose(h), "inverse_transpose");
-    HCK(launch_trmv_upper(h->buf.Z_dev, ld, h->buf.K_dev + (long)h->np * ld, h->n, h->alpha_dev, h->stream), "trmv");
-    h->have_u = true;
-  }
-  if (m <= 16) {
-    // few points (BO refinement): with U resident, A_p = L^-1 k*_p = U^T k*_p is one pass over U per point instead
-    // of the ~250-launch blocked triangular solve
-    const int mp = (m + 127) / 128 * 128;
-    double* krows = work_dev + (long)mp * ldw;  // K(X*, X) rows; overwritten by the w rows below
-    HCK(launch_assemble(h->spec, h->theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, krows, ldw, mp, h->np, 0, 0, h->stream),
-        "assemble cross");
-    for (int p = 0; p < m; ++p)
-      HCK(launch_trmv_upper_t(h->buf.Z_dev, ld, krows + (long)p * ldw, h->n, work_dev + (long)p * ldw, h->stream), "trmv_t");
-    const int nk = h->spec.nkern, d = h->spec.d;
-    const double* th = h->theta_host;
-    double kd = th[nk * d];
-    for (int c = 1; c < nk; ++c) kd = (h->spec.op[c - 1] == 0) ? kd + th[nk * d + c] : kd * th[nk * d + c];
-    const double sg = std::sqrt(th[nk * d + 2 * nk]);
-    HCK(launch_predict_reduce(work_dev, ldw, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, m, kd,
-                              pred_noise ? sg * sg : 0.0, mean_dev, var_dev, h->stream), "predict_reduce");
-  } else {
-    const int r = mi_gp_predict(h, Xnew_dev, m, work_dev, ldw, mean_dev, var_dev, pred_noise);
-    if (r != 0) return r;
-  }
   const int mp = (m + 127) / 128 * 128;
-  double* wrows = work_dev + (long)mp * ldw;
+  double* wrows = work_dev + (long)mp * ldw;  // (over predict_via_u's K(X*, X) rows)
   for (int p = 0; p < m; ++p)
     HCK(launch_trmv_upper(h->buf.Z_dev, ld, work_dev + (long)p * ldw, h->n, wrows + (long)p * ldw, h->stream), "trmv w");
-  HCK(launch_predict_grad(h->spec, h->theta_dev, h->buf.X_dev, h->n, Xnew_dev, m, h->alpha_dev, wrows, ldw, dmean_dev,
+  HCK(launch_predict_grad(h->spec, h->one.theta_dev, h->buf.X_dev, h->n, Xnew_dev, m, h->one.alpha_dev, wrows, ldw, dmean_dev,
                           dvar_dev, h->stream), "predict_grad");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
   return 0;
@@ -1752,19 +1716,21 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   if (capacity <= h->cap) return 0;
   HCK(hipSetDevice(h->device), "hipSetDevice");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
-  const int cap_ntc = cap_np / 128;
+  // (the single scratch's point-dependent arrays, as alloc_scratch sizes them; the rest does not depend on n)
+  const Batch z = scratch_strides(h, capacity);
+  Scratch& s = h->one;
   double *dinv = nullptr, *alpha = nullptr, *part = nullptr;
-  hipError_t e = hipMalloc(&dinv, sizeof(double) * MINV_ELEMS * (size_t)(cap_ntc + 4));
-  if (e == hipSuccess) e = hipMalloc(&alpha, sizeof(double) * cap_np);
-  if (e == hipSuccess) e = hipMalloc(&part, sizeof(double) * (size_t)grad_contract_blocks(capacity) * h->ntheta);
-  if (e == hipSuccess) e = hipMemcpy(dinv, h->dinv_dev, sizeof(double) * MINV_ELEMS * (size_t)h->ntc, hipMemcpyDeviceToDevice);
-  if (e == hipSuccess) e = hipMemcpy(alpha, h->alpha_dev, sizeof(double) * h->np, hipMemcpyDeviceToDevice);
+  hipError_t e = hipMalloc(&dinv, sizeof(double) * z.sdinv);
+  if (e == hipSuccess) e = hipMalloc(&alpha, sizeof(double) * z.salpha);
+  if (e == hipSuccess) e = hipMalloc(&part, sizeof(double) * z.spart);
+  if (e == hipSuccess) e = hipMemcpy(dinv, s.dinv_dev, sizeof(double) * MINV_ELEMS * (size_t)h->ntc, hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipMemcpy(alpha, s.alpha_dev, sizeof(double) * h->np, hipMemcpyDeviceToDevice);
   if (e != hipSuccess) {
     (void)hipFree(dinv); (void)hipFree(alpha); (void)hipFree(part);
     return hfail(h, e, "mi_gp_reserve");
   }
-  (void)hipFree(h->dinv_dev); (void)hipFree(h->alpha_dev); (void)hipFree(h->part_dev);
-  h->dinv_dev = dinv; h->alpha_dev = alpha; h->part_dev = part;
+  (void)hipFree(s.dinv_dev); (void)hipFree(s.alpha_dev); (void)hipFree(s.part_dev);
+  s.dinv_dev = dinv; s.alpha_dev = alpha; s.part_dev = part;
   h->cap = capacity;
   return 0;
 }
@@ -1801,30 +1767,31 @@ extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const doubl
   double *Sinv = S + 2 * MINV_ELEMS, *Linv22 = Sinv + MINV_ELEMS;
   const hipStream_t st = h->stream;
   const double* beta1 = h->buf.K_dev + (long)np * ld;
+  const Eval E = one_eval(h);
   // ---- phase 1: scratch only
   if (h->have_u) {  // L21 = K21 U11: one GEMM against the resident inverse (mi_gp_predict_u's route)
-    HCK(launch_assemble(h->spec, h->theta_dev, Xnew_dev, k, h->buf.X_dev, n, W1, ldw, 128, np, 0, 0, st), "assemble K21");
-    HCK(gemm_call(h, 0, 1, W1, ldw, 0, h->buf.Z_dev, ld, 0, L21, ldw, 0, 1, ntc, np, 0, 4, 1.0, 0.0, 1), "K21 U11");
+    HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, k, h->buf.X_dev, n, W1, ldw, 128, np, 0, 0, st), "assemble K21");
+    HCK(gemm_call(h, E, 0, 1, W1, ldw, 0, h->buf.Z_dev, ld, 0, L21, ldw, 0, 1, ntc, np, 0, 4, 1.0, 0.0, 1), "K21 U11");
   } else {
-    HCK(launch_assemble(h->spec, h->theta_dev, Xnew_dev, k, h->buf.X_dev, n, L21, ldw, 128, np, 0, 0, st), "assemble K21");
-    HCK(trsm_rec(h, L21, ldw, 128, 0, ntc), "trsm L21");
+    HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, k, h->buf.X_dev, n, L21, ldw, 128, np, 0, 0, st), "assemble K21");
+    HCK(trsm_rec(h, E, L21, ldw, 128, 0, ntc), "trsm L21");
   }
   // L21 L21^T in k segments of st_tiles tile columns (a single 128 x 128 output over k = n would run on 4 workgroups)
   const int st_tiles = (ntc + 63) / 64, nfull = ntc / st_tiles, rem = ntc - nfull * st_tiles;
-  HCK(gemm_call(h, 0, 0, L21, ldw, st_tiles * 128L, L21, ldw, st_tiles * 128L, parts, 128, MINV_ELEMS, 1, 1, st_tiles * 128, 0, 0,
+  HCK(gemm_call(h, E, 0, 0, L21, ldw, st_tiles * 128L, L21, ldw, st_tiles * 128L, parts, 128, MINV_ELEMS, 1, 1, st_tiles * 128, 0, 0,
                 1.0, 0.0, nfull), "syrk segments");
   if (rem > 0) {
     const long off = (long)nfull * st_tiles * 128;
-    HCK(gemm_call(h, 0, 0, L21 + off, ldw, 0, L21 + off, ldw, 0, parts + (long)nfull * MINV_ELEMS, 128, 0, 1, 1, rem * 128, 0, 0,
+    HCK(gemm_call(h, E, 0, 0, L21 + off, ldw, 0, L21 + off, ldw, 0, parts + (long)nfull * MINV_ELEMS, 128, 0, 1, 1, rem * 128, 0, 0,
                   1.0, 0.0, 1), "syrk tail");
   }
   HCK(hipMemsetAsync(S, 0, sizeof(double) * 2 * MINV_ELEMS, st), "S clear");
-  HCK(launch_assemble(h->spec, h->theta_dev, Xnew_dev, k, Xnew_dev, k, S, 128, 128, 128, 1, 1, st, -2147483647 - 1, diag_new_dev),
+  HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, k, Xnew_dev, k, S, 128, 128, 128, 1, 1, st, -2147483647 - 1, diag_new_dev),
       "assemble K22");
   HCK(launch_append_schur(S, parts, nfull + (rem > 0 ? 1 : 0), L21, ldw, beta1, np, ynew_dev, k, st), "schur");
-  HCK(hipMemsetAsync(h->info_dev, 0x7f, sizeof(int), st), "info reset");
-  HCK(launch_potrf_leaf128(S, 128, Sinv, n, h->info_dev, st, S + MINV_ELEMS), "leaf S");
-  HCK(launch_append_stats(S, k, h->info_dev, h->app_stats_dev, st), "append stats");
+  HCK(hipMemsetAsync(h->one.info_dev, 0x7f, sizeof(int), st), "info reset");
+  HCK(launch_potrf_leaf128(S, 128, Sinv, n, h->one.info_dev, st, S + MINV_ELEMS), "leaf S");
+  HCK(launch_append_stats(S, k, h->one.info_dev, h->app_stats_dev, st), "append stats");
   double stats[3];
   HCK(hipMemcpyAsync(stats, h->app_stats_dev, sizeof(stats), hipMemcpyDeviceToHost, st), "stats download");
   HCK(hipStreamSynchronize(st), "stream sync");
@@ -1840,29 +1807,29 @@ extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const doubl
   if (h->diag_dev)
     HCK(hipMemcpyAsync(const_cast<double*>(h->diag_dev) + n, diag_new_dev, sizeof(double) * k, hipMemcpyDeviceToDevice, st), "diag rows");
   if (h->have_u)  // P = L21 U11^T (U11 upper: k >= column tile), read before U grows
-    HCK(gemm_call(h, 0, 0, L21, ldw, 0, h->buf.Z_dev, ld, 0, W1, ldw, 0, 1, ntc, np, 0, 1, 1.0, 0.0, 1), "L21 U11^T");
+    HCK(gemm_call(h, E, 0, 0, L21, ldw, 0, h->buf.Z_dev, ld, 0, W1, ldw, 0, 1, ntc, np, 0, 1, 1.0, 0.0, 1), "L21 U11^T");
   HCK(launch_append_commit(h->buf.K_dev, ld, n, k, np, np2, L21, ldw, S, st), "commit rows");
   const int t0 = n / 128, t1 = (n2 - 1) / 128;
-  HCK(launch_tile_inverse_rows(h->buf.K_dev + (long)t0 * 128 * (ld + 1), ld, 128 * (ld + 1), h->dinv_dev + (size_t)t0 * MINV_ELEMS,
+  HCK(launch_tile_inverse_rows(h->buf.K_dev + (long)t0 * 128 * (ld + 1), ld, 128 * (ld + 1), h->one.dinv_dev + (size_t)t0 * MINV_ELEMS,
                                MINV_ELEMS, n - t0 * 128, t1 - t0 + 1, 0, st), "leaf inverses");
   if (h->have_u) {
     HCK(launch_tile_inverse_rows(S, 128, 0, Linv22, 0, 0, 1, 1, st), "L22 inverse");
-    HCK(gemm_call(h, 0, 1, Linv22, 128, 0, W1, ldw, 0, L21, ldw, 0, 1, ntc, 128, 0, 0, -1.0, 0.0, 1), "U12^T");
+    HCK(gemm_call(h, E, 0, 1, Linv22, 128, 0, W1, ldw, 0, L21, ldw, 0, 1, ntc, 128, 0, 0, -1.0, 0.0, 1), "U12^T");
     HCK(launch_append_u(h->buf.Z_dev, ld, n, k, np, np2, L21, ldw, Linv22, st), "U columns");
-    HCK(launch_trmv_upper(h->buf.Z_dev, ld, h->buf.K_dev + (long)np2 * ld, n2, h->alpha_dev, st), "trmv");
+    HCK(launch_trmv_upper(h->buf.Z_dev, ld, h->buf.K_dev + (long)np2 * ld, n2, h->one.alpha_dev, st), "trmv");
   }
   HCK(hipStreamSynchronize(st), "stream sync");
   h->n = n2;
   h->np = np2;
   h->ntc = np2 / 128;
-  h->out_host[1] += stats[0];
-  h->out_host[2] += stats[1];
-  h->out_host[0] = -0.5 * (double)n2 * 1.8378770664093453 - 0.5 * h->out_host[2] - h->out_host[1];
+  h->one.out_host[1] += stats[0];
+  h->one.out_host[2] += stats[1];
+  h->one.out_host[0] = -0.5 * (double)n2 * 1.8378770664093453 - 0.5 * h->one.out_host[2] - h->one.out_host[1];
   h->have_kinv = false;
   // the caller's batch buffers were sized for the old n: every batch call is refused until mi_gp_set_batch (which re-sizes the
   // batch scratch for the new n)
   h->b_cond_k = 0;
   h->bbuf = mi_gp_batch_buffers();
-  h->batch_cap = 0;
+  free_scratch(h->batch);
   return 0;
 }
