@@ -5,10 +5,13 @@ A "step" is one LML evaluation at a fresh theta: covariance assembly -> blocked 
 the forward solve folded in -> log-det / quadratic-form reduction, with X and y resident in HBM.
 Ranks are independent chains (SURVEY.md section 8e "replicas only": MAP restarts / MCMC chains,
 gpmcmc.py:328-343,351), so there is no data-path collective in the timed region and scaling is weak.
-The same JSON line carries a ``sharded`` sub-record: ONE covariance (BASELINE config 4: RBF, N=65536,
-d=32) column-panel sharded over all ranks with one RCCL broadcast per panel (strong scaling).
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+Everything else moves behind ``--full``: the LML + gradient rate, concurrent chains, the roofline pass, the ``sharded``
+sub-record (ONE covariance, BASELINE config 4: RBF, N=65536, d=32, column-panel sharded over all ranks with one RCCL
+broadcast per panel: strong scaling) and the CPU baseline with its parity record.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full   # the headline and every extra record
     python bench.py --gpus N ...        # starts N ranks itself (torch.distributed.run) when WORLD_SIZE is unset
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py ... --dump-outputs DIR  # rank 0's results of the last timed step as DIR/<name>.npy (float64)
@@ -333,6 +336,63 @@ def sharded_forms(args, rank, world, dev, N, d, kernel, steps, warmup, on_partia
     return out
 
 
+def roofline_records(N, d, acc, insitu, rsteps):
+    """--full: the roofline pass's records (look-ahead off, and in situ with look-ahead on) next to the counter traffic
+    of profiles/gemm_traffic.json (hash-guarded against the kernel sources)."""
+    # dominant kernel = gemm_f64_kernel_b (128x128 tiles); the 64x64-tile kernel that serves the small
+    # in-panel updates is reported next to it
+    gemm_avg_ms = acc["gemm_b_ms"] / max(acc["gemm_b_launches"], 1.0)
+    achieved = acc["gemm_b_flops"] / (acc["gemm_b_ms"] * 1e-3) * 1e-12 if acc["gemm_b_ms"] > 0 else 0.0
+    all_gemm = acc["gemm_flops"] / (acc["gemm_ms"] * 1e-3) * 1e-12 if acc["gemm_ms"] > 0 else 0.0
+    traffic, traffic_note = None, "profiles/gemm_traffic.json missing"
+    tfile = os.path.join(ROOT, "profiles", "gemm_traffic.json")
+    if os.path.exists(tfile):
+        try:
+            tj = json.load(open(tfile))
+            traffic = tj.get("hbm_bytes_per_launch")
+            src = os.path.join(ROOT, "andvaranaut_amd", "csrc", "gemm_f64.hip")
+            sha = hashlib.sha256(open(src, "rb").read()).hexdigest()[:16]
+            traffic_note = ("PMC passes of tools/prof_round.sh + tools/pmc_traffic.py on this kernel source" if tj.get("gemm_src_sha16") == sha
+                            else f"STALE: measured on gemm_f64.hip {tj.get('gemm_src_sha16')}, current {sha}")
+        except Exception as e:  # noqa: BLE001
+            traffic_note = f"unreadable: {e}"
+    asm_bytes = 8.0 * (N // 64) * (N // 64 + 1) / 2 * 64 * 64 + 8.0 * N * d
+    asm_counter, asm_note = None, "no assemble record in profiles/gemm_traffic.json"
+    try:
+        aj = json.load(open(tfile)).get("assemble")
+        if aj:
+            asm_counter = aj["hbm_bytes_per_launch"]
+            asha = hashlib.sha256(open(os.path.join(ROOT, "andvaranaut_amd", "csrc", "assemble.hip"), "rb").read()).hexdigest()[:16]
+            asm_note = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this bench (tools/prof_round.sh)" if aj.get("src_sha16") == asha
+                        else f"STALE: measured on assemble.hip {aj.get('src_sha16')}, current {asha}")
+    except Exception as e:  # noqa: BLE001
+        asm_note = f"unreadable: {e}"
+    return {
+        "roofline_pass": {"steps": rsteps, "lookahead": False,
+                          "phase_ms": {"assemble": acc["assemble_ms"] / rsteps, "cholesky": acc["cholesky_ms"] / rsteps,
+                                       "gemm_in_cholesky": acc["gemm_ms"] / rsteps}},
+        # K1/K2: lower-triangle 64x64 tiles written once + X read once (8*N*d): HBM-side figure the
+        # north star asks for next to the MFMA one
+        "assembly": {"kernel": "assemble_kernel", "ms": acc["assemble_ms"] / rsteps, "algorithmic_bytes": asm_bytes,
+                     "achieved_GBps": asm_bytes / (acc["assemble_ms"] / rsteps * 1e-3) * 1e-9, "peak_GBps": 8000.0,
+                     # counter-derived: HBM bytes of one launch from the PMC passes / this run's launch time
+                     "hbm_bytes_counters": asm_counter, "hbm_bytes_source": asm_note,
+                     "counter_GBps": (asm_counter / (acc["assemble_ms"] / rsteps * 1e-3) * 1e-9) if asm_counter else None},
+        "roofline": {"kernel": "gemm_f64_kernel_b (SYRK trailing/panel updates, v_mfma_f64_16x16x4_f64)",
+                     "bound": "mfma", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_note,
+                     # the same kernel inside the timed two-stream configuration (HIP events on its own stream, look-ahead
+                     # on: the panel chain's leaf / strip / in-panel kernels share the chip -- and the DP pipe -- with it)
+                     "in_situ_frac": (insitu["gemm_b_flops"] / (insitu["gemm_b_ms"] * 1e-3) * 1e-12 / FP64_PEAK_TFLOPS
+                                      if insitu["gemm_b_ms"] > 0 else None),
+                     "in_situ_avg_launch_ms": insitu["gemm_b_ms"] / max(insitu["gemm_b_launches"], 1.0),
+                     "in_situ_source": "HIP events around every launch on the main stream, look-ahead on, same thetas",
+                     "avg_launch_ms": gemm_avg_ms, "launches_per_step": acc["gemm_b_launches"] / rsteps,
+                     "flop_share_of_all_gemm": acc["gemm_b_flops"] / max(acc["gemm_flops"], 1.0),
+                     "all_gemm_kernels_tflops": all_gemm, "all_gemm_launches_per_step": acc["gemm_launches"] / rsteps},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -342,11 +402,14 @@ def main():
     ap.add_argument("--d", type=int, default=None, help="default 16 / --sharded-d")
     ap.add_argument("--kernel", default=None, help="default Matern52 / --sharded-kernel")
     ap.add_argument("--panel-tiles", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure every extra record: LML + gradient, concurrent chains, roofline pass, "
+                         "sharded sub-record, CPU baseline (a plain run prints the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-sample", action="store_true", help="time the CPU oracle at N=4096 and extrapolate (fast)")
-    ap.add_argument("--roofline-steps", type=int, default=3)
+    ap.add_argument("--roofline-steps", type=int, default=3, help="with --full: evaluations of the roofline pass")
     ap.add_argument("--sharded", action="store_true", help="the whole line is the sharded (strong-scaling) workload")
-    ap.add_argument("--no-sharded", action="store_true", help="skip the sharded sub-record")
+    ap.add_argument("--no-sharded", action="store_true", help="with --full: skip the sharded sub-record")
     ap.add_argument("--sharded-n", type=int, default=65536)
     ap.add_argument("--sharded-d", type=int, default=32)
     ap.add_argument("--sharded-kernel", default="RBF")
@@ -355,13 +418,14 @@ def main():
     ap.add_argument("--sharded-panel-tiles", type=int, default=0,
                     help="sharded driver's panel width in 128-column tiles (0: its own rule: 8 up to two ranks, else 4)")
     ap.add_argument("--grad", action="store_true", help="with --sharded: time LML + gradient (sharded K^-1) instead of the LML")
-    ap.add_argument("--grad-steps", type=int, default=5, help="LML + gradient evaluations timed after the LML region (0: skip)")
+    ap.add_argument("--grad-steps", type=int, default=5,
+                    help="LML + gradient evaluations after the LML region (0: skip): timed with --full, run for --dump-outputs")
     ap.add_argument("--no-lookahead", action="store_true", help="disable the look-ahead stream everywhere (profiling aid)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: REHEARSAL of the multi-rank code path with every rank on GPU 0 and host-staged collectives "
                          "(tests/test_gpu_distributed.py); its timings say nothing about the links")
     ap.add_argument("--chains-per-gpu", type=int, default=3,
-                    help="extra record: this many handles evaluated side by side on every GPU (independent chains; 0/1: skip)")
+                    help="with --full: this many handles evaluated side by side on every GPU (independent chains; 0/1: skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write rank 0's results of the last timed step to DIR/<name>.npy (float64): lml, and with --grad-steps "
                          "the last LML + gradient evaluation (lml_grad_value, lml_grad_gradient)")
@@ -450,10 +514,11 @@ def main():
     elapsed = float(t.item())
     assert all(np.isfinite(v) for v in vals), "non-finite LML in the timed region"
 
-    # LML + gradient (the MAP loop of BASELINE config 3 and every NUTS leapfrog step): same handle, same thetas
+    # LML + gradient (the MAP loop of BASELINE config 3 and every NUTS leapfrog step): same handle, same thetas.  A plain
+    # run only needs it for the gradient it dumps; its rate is a --full record.
     grad_rec = None
     outputs = {"lml": vals[-1]}
-    if want_grad:
+    if want_grad and (args.full or args.dump_outputs):
         gp.lml_grad(thetas[0])
         torch.cuda.synchronize(dev)
         dist.barrier()
@@ -472,12 +537,12 @@ def main():
                     "algorithmic_flops": "N^3 (factor N^3/3 + L^-T N^3/3 + K^-1 = U U^T N^3/3)",
                     "tflops_whole_eval": N ** 3 / tg * 1e-12, "frac_of_fp64_peak": N ** 3 / tg * 1e-12 / FP64_PEAK_TFLOPS}
 
-    # Independent chains sharing a GPU (how GPMCMC.fit(method='mcmc_*') schedules more chains than GPUs): K handles
+    # --full: independent chains sharing a GPU (how GPMCMC.fit(method='mcmc_*') schedules more chains than GPUs): K handles
     # driven by K host threads; an evaluation is bound by the serial panel chain for part of its time, a second and third
     # one fill the idle CUs.  Extra record only: `value` above stays one chain per GPU (its ms_per_step is the latency a
     # single MAP optimisation or chain sees).
     conc_rec = None
-    if args.chains_per_gpu > 1:
+    if args.full and args.chains_per_gpu > 1:
         import threading
         K = args.chains_per_gpu
         others = [MiGP(X, y, args.kernel, device=local_rank, panel_tiles=args.panel_tiles, need_grad=False) for _ in range(K - 1)]
@@ -533,7 +598,7 @@ def main():
         except Exception as e:  # noqa: BLE001 - the extra record must not take the headline down
             conc_rec["batched"] = {"error": str(e)}
 
-    # Roofline pass (rank 0): the same evaluations again with HIP events on the handle's own stream
+    # --full: roofline pass (rank 0): the same evaluations again with HIP events on the handle's own stream
     # around every phase and every GEMM launch.  Look-ahead is switched off for this pass so that
     # the dominant kernel runs alone on the chip and its launch durations are not inflated by the
     # panel kernels that overlap it in the timed region.
@@ -542,7 +607,7 @@ def main():
     insitu = dict(acc)  # the same events with look-ahead ON: the dominant kernel next to the panel chain of the second stream
     rsteps = max(1, min(args.roofline_steps, args.steps))
     gpu_ref_lml = None
-    if rank == 0:
+    if args.full and rank == 0:
         gp.set_option(0, 0)
         gp.set_profiling(2)
         for i in range(rsteps):
@@ -566,34 +631,6 @@ def main():
     line = None
     if rank == 0:
         steps = args.steps
-        # dominant kernel = gemm_f64_kernel_b (128x128 tiles); the 64x64-tile kernel that serves the small
-        # in-panel updates is reported next to it
-        gemm_avg_ms = acc["gemm_b_ms"] / max(acc["gemm_b_launches"], 1.0)
-        achieved = acc["gemm_b_flops"] / (acc["gemm_b_ms"] * 1e-3) * 1e-12 if acc["gemm_b_ms"] > 0 else 0.0
-        all_gemm = acc["gemm_flops"] / (acc["gemm_ms"] * 1e-3) * 1e-12 if acc["gemm_ms"] > 0 else 0.0
-        traffic, traffic_note = None, "profiles/gemm_traffic.json missing"
-        tfile = os.path.join(ROOT, "profiles", "gemm_traffic.json")
-        if os.path.exists(tfile):
-            try:
-                tj = json.load(open(tfile))
-                traffic = tj.get("hbm_bytes_per_launch")
-                src = os.path.join(ROOT, "andvaranaut_amd", "csrc", "gemm_f64.hip")
-                sha = hashlib.sha256(open(src, "rb").read()).hexdigest()[:16]
-                traffic_note = ("PMC passes of tools/prof_round.sh + tools/pmc_traffic.py on this kernel source" if tj.get("gemm_src_sha16") == sha
-                                else f"STALE: measured on gemm_f64.hip {tj.get('gemm_src_sha16')}, current {sha}")
-            except Exception as e:  # noqa: BLE001
-                traffic_note = f"unreadable: {e}"
-        asm_bytes = 8.0 * (N // 64) * (N // 64 + 1) / 2 * 64 * 64 + 8.0 * N * d
-        asm_counter, asm_note = None, "no assemble record in profiles/gemm_traffic.json"
-        try:
-            aj = json.load(open(tfile)).get("assemble")
-            if aj:
-                asm_counter = aj["hbm_bytes_per_launch"]
-                asha = hashlib.sha256(open(os.path.join(ROOT, "andvaranaut_amd", "csrc", "assemble.hip"), "rb").read()).hexdigest()[:16]
-                asm_note = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this bench (tools/prof_round.sh)" if aj.get("src_sha16") == asha
-                            else f"STALE: measured on assemble.hip {aj.get('src_sha16')}, current {asha}")
-        except Exception as e:  # noqa: BLE001
-            asm_note = f"unreadable: {e}"
         line = {
             "metric": "gp_lml_evals_per_s",
             "value": world * steps / elapsed,
@@ -613,37 +650,15 @@ def main():
             "cholesky_tflops_whole_eval": (N ** 3 / 3.0) / (elapsed / steps) * 1e-12,
             "cholesky_frac_of_peak_whole_eval": (N ** 3 / 3.0) / (elapsed / steps) * 1e-12 / FP64_PEAK_TFLOPS,
             "launch_mode": "plain launches, look-ahead on a second stream (hipGraph replay removed in round 2: see DESIGN.md)",
-            "lml_grad": grad_rec,
-            "concurrent_chains": conc_rec,
-            "roofline_pass": {"steps": rsteps, "lookahead": False,
-                              "phase_ms": {"assemble": acc["assemble_ms"] / rsteps, "cholesky": acc["cholesky_ms"] / rsteps,
-                                           "gemm_in_cholesky": acc["gemm_ms"] / rsteps}},
-            # K1/K2: lower-triangle 64x64 tiles written once + X read once (8*N*d): HBM-side figure the
-            # north star asks for next to the MFMA one
-            "assembly": {"kernel": "assemble_kernel", "ms": acc["assemble_ms"] / rsteps, "algorithmic_bytes": asm_bytes,
-                         "achieved_GBps": asm_bytes / (acc["assemble_ms"] / rsteps * 1e-3) * 1e-9, "peak_GBps": 8000.0,
-                         # counter-derived: HBM bytes of one launch from the PMC passes / this run's launch time
-                         "hbm_bytes_counters": asm_counter, "hbm_bytes_source": asm_note,
-                         "counter_GBps": (asm_counter / (acc["assemble_ms"] / rsteps * 1e-3) * 1e-9) if asm_counter else None},
-            "roofline": {"kernel": "gemm_f64_kernel_b (SYRK trailing/panel updates, v_mfma_f64_16x16x4_f64)",
-                         "bound": "mfma", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_note,
-                         # the same kernel inside the timed two-stream configuration (HIP events on its own stream, look-ahead
-                         # on: the panel chain's leaf / strip / in-panel kernels share the chip -- and the DP pipe -- with it)
-                         "in_situ_frac": (insitu["gemm_b_flops"] / (insitu["gemm_b_ms"] * 1e-3) * 1e-12 / FP64_PEAK_TFLOPS
-                                          if insitu["gemm_b_ms"] > 0 else None),
-                         "in_situ_avg_launch_ms": insitu["gemm_b_ms"] / max(insitu["gemm_b_launches"], 1.0),
-                         "in_situ_source": "HIP events around every launch on the main stream, look-ahead on, same thetas",
-                         "avg_launch_ms": gemm_avg_ms, "launches_per_step": acc["gemm_b_launches"] / rsteps,
-                         "flop_share_of_all_gemm": acc["gemm_b_flops"] / max(acc["gemm_flops"], 1.0),
-                         "all_gemm_kernels_tflops": all_gemm, "all_gemm_launches_per_step": acc["gemm_launches"] / rsteps},
         }
+        if args.full:
+            line.update({"lml_grad": grad_rec, "concurrent_chains": conc_rec, **roofline_records(N, d, acc, insitu, rsteps)})
 
-    # sharded sub-record (strong scaling, BASELINE config 4) under a deadline: the replicas' line survives a stuck
+    # --full: sharded sub-record (strong scaling, BASELINE config 4) under a deadline: the replicas' line survives a stuck
     # exchange, but the PROCESS does not pretend to be healthy -- a watchdog or a caught failure ends with a non-zero
     # exit status once the line is out (nothing is retried or restarted in-process).
     exit_code = 0
-    if not args.no_sharded:
+    if args.full and not args.no_sharded:
         def expire():
             if rank == 0 and line is not None:
                 line["sharded"] = {"error": f"not finished after {args.sharded_timeout:.0f} s (rank 0 gave up waiting)"}
@@ -679,7 +694,7 @@ def main():
             line["sharded"] = rec
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, d, args.kernel, full=not args.cpu_baseline_sample, gpu_lml=gpu_ref_lml)
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, outputs)

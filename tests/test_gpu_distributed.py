@@ -220,7 +220,7 @@ def test_bench_measures_every_exchange_form_end_to_end(world):
 
 
 def test_bench_default_line_carries_the_exchange_forms_at_world_2():
-    """The DEFAULT bench line (replicas headline + sharded sub-record, what the driver's scaling run calls) at world 2, rehearsed with
+    """The --full bench line (replicas headline + sharded sub-record, what a scaling run calls) at world 2, rehearsed with
     gloo ranks on one GPU and small sizes: the headline survives, the sub-record holds the three forms and their bit comparison."""
     import json
 
@@ -229,7 +229,7 @@ def test_bench_default_line_carries_the_exchange_forms_at_world_2():
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), OMP_NUM_THREADS="4")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo",
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full", "--backend", "gloo",
                                        "--n", "2500", "--d", "4", "--steps", "3", "--warmup", "1", "--grad-steps", "1", "--chains-per-gpu", "0",
                                        "--roofline-steps", "1", "--sharded-n", "3000", "--sharded-d", "4", "--sharded-kernel", "Matern52",
                                        "--sharded-steps", "2", "--sharded-panel-tiles", "2", "--sharded-timeout", "300"],

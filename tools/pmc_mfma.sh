@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 C="SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY"
-rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_mfma_lml -- python3 $ROOT/bench.py --steps 2 --warmup 1 --roofline-steps 1 --no-lookahead --no-cpu-baseline --no-sharded --chains-per-gpu 0 --grad-steps 0 > $OUT/pmc_mfma_lml.log 2>&1
+rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_mfma_lml -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --roofline-steps 1 --no-lookahead --no-cpu-baseline --no-sharded --chains-per-gpu 0 --grad-steps 0 > $OUT/pmc_mfma_lml.log 2>&1
 echo "lml pass exit $?"
 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_mfma_grad -- python3 $ROOT/tools/trace_n.py 16384 16 grad > $OUT/pmc_mfma_grad.log 2>&1
 echo "grad pass exit $?"
