@@ -113,6 +113,11 @@ def load():
     lib.mi_gp_reserve.argtypes = [vp, ci]
     lib.mi_gp_append.argtypes = [vp, vp, vp, vp, ci, vp, cl]
     lib.mi_gp_predict_batch.argtypes = [vp, ci, vp, ci, vp, cl, cl, vp, vp, ci, vp, vp]
+    lib.mi_gp_predict_cov.argtypes = [vp, vp, ci, vp, cl, vp, vp, cl, ci]
+    lib.mi_gp_sample_cov_work.argtypes = [ci, ci]
+    lib.mi_gp_sample_cov_work.restype = cl
+    u64 = ctypes.c_uint64
+    lib.mi_gp_sample_cov.argtypes = [vp, vp, cl, ci, vp, cd, ci, u64, u64, vp, cl, vp, cl]
     lib.mi_gp_set_option.argtypes = [vp, ci, ci]
     lib.mi_gp_get_option.argtypes = [vp, ci, ip]
     lib.mi_gp_set_profiling.argtypes = [vp, ci]
@@ -173,6 +178,9 @@ EXPORTS = [
     "mi_gp_predict_grad",
     "mi_gp_factor_batch",
     "mi_gp_predict_batch",
+    "mi_gp_predict_cov",
+    "mi_gp_sample_cov_work",
+    "mi_gp_sample_cov",
     "mi_gp_set_option",
     "mi_gp_get_option",
     "mi_gp_set_profiling",

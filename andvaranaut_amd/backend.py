@@ -607,6 +607,102 @@ class MiGP:
         return (o[:m], o[m : 2 * m], o[2 * m : 2 * m + m * self.d].reshape(m, self.d),
                 o[2 * m + m * self.d :].reshape(m, self.d))
 
+    # ---------------------------------------------------------------- joint conditional and posterior draws
+    # One call per request, nothing chunked: device memory bounds M.  predict_cov holds Sigma (mp^2 doubles, mp = M rounded up
+    # to 128) beside the cross-covariance rows (mp x (padded n + 16)); sample_posterior adds mi_gp_sample_cov_work(M, s) =
+    # mp / 128 * 16384 + 2 * ceil(s/128)*128 * mp doubles.  At N = 4096 and one draw that is ~8 GB at M = 30 000 and ~83 GB
+    # at M = 100 000.
+
+    def _prior_variance(self):
+        """kd: the +/* fold of the components' kv, the composite prior variance (Stationary.diag == 1)."""
+        th = self._factored_theta
+        kv = th[self.nkern * self.d : self.nkern * self.d + self.nkern]
+        kd = float(kv[0])
+        for i, op in enumerate(self.ops):
+            kd = kd + float(kv[i + 1]) if op == "+" else kd * float(kv[i + 1])
+        return kd
+
+    def _joint_device(self, Xnew, pred_noise):
+        """mi_gp_predict_cov at the resident factor: (mean tensor [m], Sigma tensor [mp, mp] with its lower triangle set)."""
+        Xnew = np.ascontiguousarray(Xnew, dtype=np.float64)
+        if Xnew.ndim != 2 or Xnew.shape[1] != self.d:
+            raise ValueError("Xnew must be (m, d)")
+        if not np.isfinite(Xnew).all():
+            raise ValueError("Xnew must be finite")
+        m = Xnew.shape[0]
+        if m < 1:
+            raise ValueError("Xnew must hold at least one point")
+        mp = (m + 127) // 128 * 128
+        with torch.cuda.device(self.dev):
+            if getattr(self, "_work", None) is None or self._work.shape[0] < mp:
+                self._work = None
+                self._work = torch.empty((mp, self.lda), dtype=torch.float64, device=self.dev)
+            xn = torch.from_numpy(Xnew).to(self.dev)
+            mu_t = torch.empty(m, dtype=torch.float64, device=self.dev)
+            cov_t = torch.empty((mp, mp), dtype=torch.float64, device=self.dev)
+            torch.cuda.synchronize(self.dev)
+            self._check(self.lib.mi_gp_predict_cov(self.h, xn.data_ptr(), m, self._work.data_ptr(), self.lda, mu_t.data_ptr(),
+                                                   cov_t.data_ptr(), mp, 1 if pred_noise else 0), "mi_gp_predict_cov")
+        return mu_t, cov_t
+
+    def predict_cov(self, theta, Xnew, pred_noise=True):
+        """Posterior mean and JOINT covariance at Xnew (converted inputs): PyMC's gp.predict(Xnew, diag=False, pred_noise=...)
+        -- Sigma = K(X*, X*) - A^T A with A = L^-1 K(X, X*), plus sqrt(gv)^2 I with pred_noise, else jitter I.  Returns
+        (mu [M], cov [M, M]), cov symmetric (mirrored from the lower triangle the device computes); mu is predict()'s mean
+        through the blocked solve, bit for bit."""
+        self._ensure_factored(theta)
+        mu_t, cov_t = self._joint_device(Xnew, pred_noise)
+        m = mu_t.shape[0]
+        low = np.tril(cov_t[:m, :m].cpu().numpy())
+        return mu_t.cpu().numpy(), low + np.tril(low, -1).T
+
+    SAMPLE_JITTER_STEPS = (1e-12, 1e-10, 1e-8, 1e-6, 1e-4)  # extra diagonal (x kd) of sample_posterior's retries
+
+    def sample_posterior(self, theta, Xnew, nsamples, seed=None, pred_noise=False, offset=None):
+        """``nsamples`` joint draws of the posterior at Xnew (converted inputs), an (nsamples, M) array: mean + L_Sigma z with
+        Sigma = predict_cov's joint covariance -- of the latent f by default (pred_noise=False, the target of Thompson
+        sampling), of noisy observations with pred_noise=True.  z is the counter-based Philox stream of mi_gp_sample_cov:
+        ``seed`` None takes one from the OS once per handle; the handle keeps the stream offset and advances it by every call,
+        so repeated calls give fresh draws (``offset`` overrides it; the same seed and offset give the same bits).  If Sigma
+        is not positive definite, it is rebuilt and factored again with an extra diagonal of 1e-12 kd, 1e-10 kd, ... up to
+        1e-4 kd (kd the composite prior variance), then FloatingPointError.  ``self.sample_info`` records the seed, offset and
+        extra jitter used."""
+        nsamples = int(nsamples)
+        if nsamples < 1:
+            raise ValueError("nsamples must be >= 1")
+        self._ensure_factored(theta)
+        if seed is None:
+            if getattr(self, "_philox_seed", None) is None:
+                self._philox_seed = int(np.random.SeedSequence().entropy) & (2 ** 64 - 1)
+            seed = self._philox_seed
+        seed = int(seed) & (2 ** 64 - 1)
+        off = int(getattr(self, "_philox_offset", 0) if offset is None else offset)
+        if not 0 <= off < 2 ** 64:
+            raise ValueError("offset must lie in [0, 2^64)")
+        mu_t, cov_t = self._joint_device(Xnew, pred_noise)
+        m, mp = mu_t.shape[0], cov_t.shape[0]
+        kd = self._prior_variance()
+        need = int(self.lib.mi_gp_sample_cov_work(m, nsamples))
+        with torch.cuda.device(self.dev):
+            work = torch.empty(need, dtype=torch.float64, device=self.dev)
+            draws = torch.empty((nsamples, m), dtype=torch.float64, device=self.dev)
+            torch.cuda.synchronize(self.dev)
+            jitters = (0.0,) + tuple(f * kd for f in self.SAMPLE_JITTER_STEPS)
+            for attempt, ej in enumerate(jitters):
+                if attempt > 0:  # the failed factorisation overwrote Sigma: rebuild it
+                    mu_t, cov_t = self._joint_device(Xnew, pred_noise)
+                r = self._check(self.lib.mi_gp_sample_cov(self.h, cov_t.data_ptr(), mp, m, mu_t.data_ptr(), ej, nsamples, seed, off,
+                                                          draws.data_ptr(), m, work.data_ptr(), need), "mi_gp_sample_cov")
+                if r == 0:
+                    break
+            else:
+                raise FloatingPointError(f"joint covariance not positive definite with an extra diagonal of {jitters[-1]:.3g} "
+                                         f"(pivot {r})")
+            out = draws.cpu().numpy()
+        self._philox_offset = (off + (nsamples * m + 3) // 4) % 2 ** 64
+        self.sample_info = {"seed": seed, "offset": off, "extra_jitter": ej, "attempts": attempt + 1}
+        return out
+
     PINNED_IO_MAX_POINTS = 256  # predict / predict_grad: up to this many points travel through pinned host memory
 
     def _pinned_io(self, nelem):

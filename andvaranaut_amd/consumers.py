@@ -241,7 +241,14 @@ class ConsumersMixin:
         reference: the hyper-parameters are refitted only at every r-th iteration (and the last one); in between the
         resident GP is conditioned on the new point at the current hyper-parameters (MiGP.append, O(n^2) instead of a
         fit and an O(n^3) refactorisation).  Not with iwgp / cwgp: their warp parameters belong to the fit and change the
-        converted data themselves."""
+        converted data themselves.
+
+        ``method="TS"`` (Thompson sampling, beyond the reference): each proposal is the optimum of ONE joint posterior draw
+        of the latent function over the ``predict_samps`` LHC candidates (GPMCMC.sample_posterior); only with
+        opt_method="predict", and ``refine`` does not apply."""
+        if method == "TS" and opt_method != "predict":
+            raise ValueError("method='TS' (Thompson sampling) takes one joint posterior draw over the predict_samps candidates: "
+                             f"it needs opt_method='predict', not {opt_method!r}")
         refit_every = int(refit_every)
         if refit_every < 1:
             raise ValueError("refit_every must be >= 1")
@@ -264,8 +271,8 @@ class ConsumersMixin:
             raise Exception("Model must be fitted before running Bayesian optimisation")
         if method == "exploit":
             eps = 0.0
-        if method not in ("eps-RS", "EI", "exploit", "explore"):
-            raise Exception("method must be one of eps-RS ,EI, exploit, or explore")
+        if method not in ("eps-RS", "EI", "exploit", "explore", "TS"):
+            raise Exception("method must be one of eps-RS ,EI, exploit, explore, or TS")
         lbs = np.array([p.ppf(1e-8) for p in self.priors])
         ubs = np.array([p.isf(1e-8) for p in self.priors])
         bnds = Bounds(lbs, ubs)
@@ -288,7 +295,16 @@ class ConsumersMixin:
                         return -self.predict(x, EI=True, EIopt=opt_type)[:, 0]
 
                     roll = np.random.rand()
-                    if method != "eps-RS" or roll > eps:
+                    if method == "TS":
+                        # Thompson sampling: one joint draw of the latent function over the candidates, its optimum
+                        xsamps = latin_sample(self.priors, predict_samps, seed=int(np.random.randint(2 ** 31 - 1)),
+                                              optimization="random-cd" if predict_samps <= 2000 else None)
+                        fs = self.sample_posterior(xsamps, 1, seed=int(np.random.randint(2 ** 63 - 1)), jitter=jitter)[0]
+                        fs = fs if opt_type == "min" else -fs
+                        xsamp, fopt = np.array([xsamps[np.argmin(fs), :]]), np.min(fs)
+                        if verb:
+                            print(f"Function opt is {float(fopt):0.3f}")
+                    elif method != "eps-RS" or roll > eps:
                         if opt_method == "DE":
                             # population evaluated in one batched prediction per generation
                             res = differential_evolution(lambda xs: optf(xs.T), bnds, vectorized=True,
@@ -308,7 +324,7 @@ class ConsumersMixin:
                         xsamp = np.array([[p.rvs() for p in self.priors]])
                 finally:
                     self.verbose = verb
-            if opt_method not in ("DE", "predict") or (opt_method == "predict" and refine):
+            if opt_method not in ("DE", "predict") or (opt_method == "predict" and refine and method != "TS"):
                 imodel = InputModel([pymc_prior(p) for p in self.priors])
                 potential = self._bo_potential(method, opt_type, normvar, jitter, reuse_factor=refit_every > 1)
                 roll = np.random.rand()

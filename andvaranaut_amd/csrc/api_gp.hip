@@ -1563,6 +1563,109 @@ extern "C" int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, dou
   return 0;
 }
 
+// ---------------------------------------------------------------- joint conditional and posterior draws
+// Sigma = (K(X*, X*) + gv or jitter on the diagonal) - A A^T with mi_gp_predict's A = L^-1 K(X, X*) rows in work_dev: the
+// cross-covariance, blocked solve and reduction of mi_gp_predict (same bits for the mean), then the assembly of K** and ONE
+// lower-trapezoid GEMM with k = np.  The reduction's variance is parked in row 0 of cov_dev, which the assembly then overwrites
+// (the rest of that row is strict upper triangle: unspecified).
+extern "C" int mi_gp_predict_cov(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw, double* mean_dev,
+                                 double* cov_dev, long ldc, int pred_noise) {
+  const long mp = m > 0 ? (m + 127) / 128 * 128 : 0;
+  const char* why = (!Xnew_dev || !work_dev || !mean_dev || !cov_dev) ? "null buffer"
+                  : m <= 0 ? "m must be >= 1"
+                  : (ldc < mp || (ldc & 1)) ? "ldc must be even and >= ceil(m/128)*128"
+                  : !h ? "null handle"
+                  : !h->factored ? "call mi_gp_factor first"
+                  : (ldw < h->np || (ldw & 1)) ? "ldw must be even and >= padded n" : nullptr;
+  if (why) {
+    char text[200];
+    snprintf(text, sizeof(text), "mi_gp_predict_cov: %s", why);
+    set_global_error(text);
+    if (h) snprintf(h->err, sizeof(h->err), "%s", text);
+    return -1;
+  }
+  HCK(hipSetDevice(h->device), "hipSetDevice");
+  const Eval E = one_eval(h);
+  HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, (int)mp, h->np, 0, 0, h->stream),
+      "assemble cross");
+  HCK(trsm_rec(h, E, work_dev, ldw, (int)mp, 0, h->ntc), "trsm");
+  HCK(predict_reduce(h, work_dev, ldw, m, mean_dev, cov_dev, 1), "predict_reduce");
+  HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, m, Xnew_dev, m, cov_dev, ldc, (int)mp, (int)mp, 1, pred_noise ? 3 : 4,
+                      h->stream), "assemble K**");
+  // C -= A A^T over the lower tiles; A's padding rows are zero, so the padding of Sigma keeps the assembly's identity
+  HCK(gemm_call(h, E, 0, 0, work_dev, ldw, 0, work_dev, ldw, 0, cov_dev, ldc, 0, (int)(mp / 128), (int)(mp / 128), h->np, 1, 0,
+                -1.0, 1.0, 1), "Sigma update");
+  HCK(hipStreamSynchronize(h->stream), "stream sync");
+  return 0;
+}
+
+// scratch of mi_gp_sample_cov, in doubles: the bad-pivot word (8 doubles), the leaf inverses of L_Sigma (one per tile column),
+// Z and the product D (ceil(s/128)*128 x mp each)
+static long sample_cov_work(int m, int s) {
+  if (m <= 0 || s <= 0) return -1;
+  const long mp = (m + 127) / 128 * 128, sp = (s + 127) / 128 * 128;
+  return 8 + (mp / 128) * (long)MINV_ELEMS + 2 * sp * mp;
+}
+extern "C" long mi_gp_sample_cov_work(int m, int s) { return sample_cov_work(m, s); }
+
+constexpr int SIGMA_PANEL_TILES = 4;  // tile columns per panel of the right-looking factorisation of Sigma
+
+extern "C" int mi_gp_sample_cov(mi_gp_handle* h, double* cov_dev, long ldc, int m, const double* mean_dev, double extra_jitter,
+                                int s, unsigned long long seed, unsigned long long offset, double* draws_dev, long ldd,
+                                double* work_dev, long work_len) {
+  const long mp = m > 0 ? (m + 127) / 128 * 128 : 0;
+  const char* why = (!cov_dev || !mean_dev || !draws_dev || !work_dev) ? "null buffer"
+                  : m <= 0 ? "m must be >= 1"
+                  : s <= 0 ? "s must be >= 1"
+                  : (ldc < mp || (ldc & 1)) ? "ldc must be even and >= ceil(m/128)*128"
+                  : ldd < m ? "ldd must be >= m"
+                  : !(extra_jitter >= 0.0 && std::isfinite(extra_jitter)) ? "extra_jitter must be finite and >= 0"
+                  : work_len < sample_cov_work(m, s) ? "work_len is shorter than mi_gp_sample_cov_work(m, s)"
+                  : !h ? "null handle" : nullptr;
+  if (why) {
+    char text[200];
+    snprintf(text, sizeof(text), "mi_gp_sample_cov: %s", why);
+    set_global_error(text);
+    if (h) snprintf(h->err, sizeof(h->err), "%s", text);
+    return -1;
+  }
+  HCK(hipSetDevice(h->device), "hipSetDevice");
+  if (int r = ensure_kernel_attributes()) { snprintf(h->err, sizeof(h->err), "mi_gp_sample_cov: %s", mi_gp_last_global_error()); return r; }
+  const int mt = (int)(mp / 128), sp = (s + 127) / 128 * 128;
+  int* info_dev = reinterpret_cast<int*>(work_dev);
+  double* dinv = work_dev + 8;
+  double* Z = dinv + (long)mt * MINV_ELEMS;
+  double* D = Z + (long)sp * mp;
+  hipStream_t st = h->stream;
+  const Eval E = one_eval(h);
+  // L_Sigma in place: leaf / strip / in-panel updates per panel, then the trailing lower trapezoid on the GEMM
+  HCK(launch_cov_prepare(cov_dev, ldc, m, (int)mp, extra_jitter, st), "cov_prepare");
+  HCK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(info_dev), INFO_OK, 1, st), "info reset");
+  for (int c0 = 0; c0 < mt; c0 += SIGMA_PANEL_TILES) {
+    const int w = mt - c0 < SIGMA_PANEL_TILES ? mt - c0 : SIGMA_PANEL_TILES, rest = mt - c0 - w;
+    double* P = cov_dev + (long)c0 * 128 * ldc + (long)c0 * 128;
+    HCK(chol_panel_blocks(P, ldc, mt - c0, w, dinv + (size_t)c0 * MINV_ELEMS, info_dev, c0 * 128, st), "Sigma panel");
+    if (rest > 0)
+      HCK(gemm_call(h, E, 0, 0, P + (long)w * 128 * ldc, ldc, 0, P + (long)w * 128 * ldc, ldc, 0,
+                    P + (long)w * 128 * ldc + (long)w * 128, ldc, 0, rest, rest, w * 128, 1, 0, -1.0, 1.0, 1), "Sigma update");
+  }
+  int info = 0;
+  HCK(hipMemcpyAsync(&info, info_dev, sizeof(int), hipMemcpyDeviceToHost, st), "info download");
+  HCK(hipStreamSynchronize(st), "stream sync");
+  if (info != INFO_OK) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_sample_cov: Sigma is not positive definite (pivot %d)", info);
+    return info;
+  }
+  // draws: D = Z L_Sigma^T (kmode 4: L_Sigma^T is upper triangular, so the diagonal tiles' strict upper halves must hold zeros)
+  HCK(launch_zero_diag_upper(cov_dev, ldc, mt, st), "zero upper");
+  HCK(hipMemsetAsync(Z, 0, sizeof(double) * (size_t)sp * mp, st), "Z padding");
+  HCK(launch_philox_normals(Z, mp, m, s, seed, offset, st), "normals");
+  HCK(gemm_call(h, E, 0, 0, Z, mp, 0, cov_dev, ldc, 0, D, mp, 0, sp / 128, mt, (int)mp, 0, 4, 1.0, 0.0, 1), "Z L^T");
+  HCK(launch_draw_epilogue(D, mp, mean_dev, m, s, draws_dev, ldd, st), "draw epilogue");
+  HCK(hipStreamSynchronize(st), "stream sync");
+  return 0;
+}
+
 // ---------------------------------------------------------------- batched conditional
 // The posterior predictive over k hyper-parameter draws: k conditional-form factorisations in lockstep (batch_internal, what = 1,
 // the kernels of mi_gp_factor with blockIdx.z = problem), then mi_gp_predict's three steps -- cross-covariance, blocked

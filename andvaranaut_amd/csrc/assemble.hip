@@ -156,6 +156,8 @@ __global__ __launch_bounds__(256, (KID_STATIC >= 0 && KID_STATIC != KID_RATQUAD)
         } else if (diag_on && gi + diag_shift == gj) {
           if (noise_form == 0) { x += sg * sg; x += jitter; }       // Marginal._build_marginal_likelihood
           else if (noise_form == 1) { x += jitter; x += sg * sg; }  // Marginal._build_conditional
+          else if (noise_form == 3) { x += sg * sg; }                // joint conditional, pred_noise: + noise(Xnew)
+          else if (noise_form == 4) { x += jitter; }                 // joint conditional without it: stabilize(cov, jitter)
           else { x += jitter + gv; }                                // gpmcmc.py:312 explicit form
           if (extra_diag) x += extra_diag[gi];                      // per-point noise vector (inverse_opt, gpmcmc.py:1134-1158)
         }

@@ -164,7 +164,8 @@ inline KernSpec make_kern_spec(int d, int nkern, const int* kernel_ids, const in
   return s;
 }
 // sym=1: lower 64x64 tiles of K(X1,X1) + noise on the diagonal, identity in the padding;
-// sym=0: full K(X1,X2), zeros in the padding.  noise_form: 0 marginal, 1 conditional, 2 explicit.
+// sym=0: full K(X1,X2), zeros in the padding.  noise_form: 0 marginal, 1 conditional, 2 explicit, 3 sqrt(gv)^2 only,
+// 4 jitter only (the joint conditional's pred_noise / stabilize forms, mi_gp_predict_cov).
 hipError_t launch_assemble(const KernSpec& spec, const double* theta, const double* X1, int n1, const double* X2,
                            int n2, double* K, long ldk, int rows_pad, int cols_pad, int sym, int noise_form,
                            hipStream_t stream, int diag_shift = -2147483647 - 1, const double* extra_diag = nullptr,
@@ -242,6 +243,19 @@ hipError_t launch_tile_inverse_rows(const double* T, long ldt, long sT, double* 
 // U = L^-T extended in place by the appended columns: U12 from Qt (k rows, row p = -(L22^-1 L21 U11^T) row p), U22 = Linv22^T
 hipError_t launch_append_u(double* Z, long ld, int n, int k, int np_old, int np_new, const double* Qt, long ldw, const double* Linv22,
                            hipStream_t stream);
+
+// ---------------------------------------------------------------- joint_f64.hip (mi_gp_predict_cov / mi_gp_sample_cov)
+// Z[r * ldz + i] = normal j = r m + i (r < s, i < m) of the Philox4x64-10 + Box-Muller stream of include/mi_gp.h; the padding
+// of Z is not written
+hipError_t launch_philox_normals(double* Z, long ldz, int m, int s, unsigned long long seed, unsigned long long offset,
+                                 hipStream_t stream);
+// C (mp x mp, lower): + shift on the m leading diagonal entries, identity in the lower triangle of rows m .. mp - 1
+hipError_t launch_cov_prepare(double* C, long ldc, int m, int mp, double shift, hipStream_t stream);
+// zeros in the strict upper triangle of the ntiles diagonal 128 x 128 tiles of L
+hipError_t launch_zero_diag_upper(double* L, long ld, int ntiles, hipStream_t stream);
+// draws[r * ldd + i] = mean[i] + D[r * ldp + i] for r < s, i < m
+hipError_t launch_draw_epilogue(const double* D, long ldp, const double* mean, int m, int s, double* draws, long ldd,
+                                hipStream_t stream);
 
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)

@@ -739,6 +739,45 @@ class GPMCMC(ConsumersMixin):
             y, yv = self.__gh_stats(x, y, yv, normvar, deg, EI=EI, EIopt=EIopt)
         return (y, yv) if return_var else y
 
+    def _converted_x(self, x, convert):
+        """(converted inputs for the GP, inputs in the original space) of prediction points x, as predict() forms them."""
+        if convert:
+            xarg = np.zeros_like(x)
+            for i in range(self.nx):
+                xarg[:, i] = self.xconrevs[i].con(x[:, i])
+        else:
+            xarg = copy.deepcopy(x)
+            x = copy.deepcopy(x)
+            for i in range(self.nx):
+                x[:, i] = self.xconrevs[i].rev(x[:, i])
+        return xarg, x
+
+    def predict_joint(self, x, convert=True, pred_noise=True, jitter=1e-6):
+        """Posterior mean (M, 1) and JOINT covariance (M, M) at x in the converted output space -- PyMC's
+        gp.predict(x, point, diag=False, pred_noise=...); the diagonal agrees with predict(revert=False, return_var=True).
+        A covariance has no image under a nonlinear output reversion, so there is no ``revert`` here (sample_posterior
+        reverts draws instead)."""
+        if self._ensure_gp() is None or self.hypers is None:
+            raise Exception("Error: fit the GP before predicting")
+        xarg, _ = self._converted_x(np.asarray(x, dtype=np.float64), convert)
+        mu, cov = self.gp.predict_cov(self._theta_from_hypers(self.hypers, jitter), xarg, pred_noise=pred_noise)
+        return mu.reshape((-1, 1)), cov
+
+    def sample_posterior(self, x, nsamples=1, seed=None, convert=True, revert=True, pred_noise=False, jitter=1e-6):
+        """``nsamples`` joint posterior draws at the M points x, an (nsamples, M) array: sample paths of the latent function
+        by default (pred_noise=False), of noisy observations with pred_noise=True.  revert=True maps each draw through the
+        output reversion point by point and adds the mean function -- exact for sample paths, no quadrature.  ``seed``: see
+        MiGP.sample_posterior (None: fresh draws on every call)."""
+        if self._ensure_gp() is None or self.hypers is None:
+            raise Exception("Error: fit the GP before predicting")
+        xarg, xorig = self._converted_x(np.asarray(x, dtype=np.float64), convert)
+        draws = self.gp.sample_posterior(self._theta_from_hypers(self.hypers, jitter), xarg, nsamples, seed=seed,
+                                         pred_noise=pred_noise)
+        if revert:
+            means = self._mean_at(xorig)
+            draws = self.yconrevs[0].rev(draws) + (np.reshape(means, (1, -1)) if np.ndim(means) else means)
+        return draws
+
     @staticmethod
     def _draw_indices(total, ndraws):
         """Indices of ``ndraws`` evenly spaced draws among ``total`` (all of them for None or ndraws >= total)."""

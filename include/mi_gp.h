@@ -138,6 +138,42 @@ MI_GP_API int mi_gp_predict_u(mi_gp_handle* h, const double* Xnew_dev, int m, do
 MI_GP_API int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw, double* mean_dev,
                        double* var_dev, int pred_noise, double* dmean_dev, double* dvar_dev);
 
+/* Joint conditional and posterior function draws at m new points (PyMC's gp.predict(Xnew, point, diag=False, pred_noise=...),
+ * [3P] Marginal._build_conditional; the reference passes diag=True at gpmcmc.py:593-594).
+ *   mi_gp_predict_cov  after mi_gp_factor (or mi_gp_append): mean_dev (m doubles) = mi_gp_predict's mean bit for bit (same
+ *                      cross-covariance, blocked solve and reduction; work_dev laid out as there: ceil(m/128)*128 rows x ldw,
+ *                      ldw even and >= mi_gp_padded_n()).  cov_dev is mp x ldc row-major, mp = ceil(m/128)*128, ldc even and
+ *                      >= mp; its lower triangle, diagonal included, receives
+ *                          Sigma = K(X*, X*) - A^T A,  A = L^-1 K(X, X*),  + sqrt(gv)^2 I if pred_noise, else + jitter I,
+ *                      with the full-matrix kernel form on the diagonal (k(sqrt(1e-12)) for Matern / Exponential, not the 1 of
+ *                      diag=True).  Padding rows and columns hold the identity; the strict upper triangle is unspecified.
+ *                      Built as the assembly of K(X*, X*) + the diagonal term and one lower-trapezoid GEMM C -= A A^T (k = np):
+ *                      m^2 N + N^2 m flops.  The handle's state is not changed.
+ *   mi_gp_sample_cov   s joint draws from N(mean, Sigma) for any symmetric positive-definite Sigma in the lower triangle of
+ *                      cov_dev (mp x ldc as above; the padding need not be set):  cov_dev's lower triangle is overwritten by
+ *                      L_Sigma = chol(Sigma + extra_jitter I) (zeros above the diagonal inside the diagonal 128 x 128 tiles,
+ *                      identity in the padding) and
+ *                          draws_dev[r * ldd + i] = mean_i + (L_Sigma z_r)_i,   r < s, i < m (ldd >= m),
+ *                      z the normals j = r m + i of a counter-based stream: normal j comes from Philox block b = offset + j/4,
+ *                      Philox4x64-10 of the 256-bit counter b + 1 under the key (seed, 0) -- the four words
+ *                      numpy.random.Philox(key=seed, counter=b).random_raw(4) returns; words (w0, w1) give normals 4b, 4b+1 and
+ *                      (w2, w3) give 4b+2, 4b+3 by Box-Muller: u = ((w >> 11) + 0.5) 2^-53, rho = sqrt(-2 log u0), normals
+ *                      rho cos(2 pi u1), rho sin(2 pi u1).  A call uses ceil(s m / 4) blocks: consecutive calls with
+ *                      offset += ceil(s m / 4) never reuse a number; the same (seed, offset) gives the same bits.  work_dev:
+ *                      mi_gp_sample_cov_work(m, s) doubles (-1 for m or s < 1), work_len its length.  m^3/3 + m^2 s flops.
+ *                      Returns info > 0 (1-based pivot) if Sigma + extra_jitter I is not positive definite: draws_dev is then
+ *                      not written and cov_dev holds a partial factor (rebuild it before another attempt).  Runs on the handle's
+ *                      stream and changes NO handle state: the resident factor, U, K^-1, the batch state and the append capacity
+ *                      stay valid.
+ * Both return -1 on bad arguments, checked before any HIP call (text in mi_gp_last_error(h), and in mi_gp_last_global_error()
+ * for a null handle), -2 on a HIP failure. */
+MI_GP_API int mi_gp_predict_cov(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw, double* mean_dev,
+                                double* cov_dev, long ldc, int pred_noise);
+MI_GP_API long mi_gp_sample_cov_work(int m, int s);
+MI_GP_API int mi_gp_sample_cov(mi_gp_handle* h, double* cov_dev, long ldc, int m, const double* mean_dev, double extra_jitter, int s,
+                               unsigned long long seed, unsigned long long offset, double* draws_dev, long ldd, double* work_dev,
+                               long work_len);
+
 /* Posterior predictive over k hyper-parameter draws (the MCMC draws of GPMCMC.fit(method='mcmc_*'); PyMC's gp.conditional +
  * sample_posterior_predictive), on the buffers of mi_gp_set_batch (k <= count):
  *   mi_gp_factor_batch   factorises k covariances in the conditional form, one theta each (what mi_gp_factor does, k problems in
