@@ -1442,7 +1442,11 @@ extern "C" int mi_gp_set_diag(mi_gp_handle* h, const double* diag_dev) {
 // (gpmcmc.py:351) evaluate the same data at different theta, so their chains can run side by side inside the same launches
 // instead of on separate handles and streams (which stops paying at the fourth handle: hardware queues).
 extern "C" int mi_gp_set_batch(mi_gp_handle* h, const mi_gp_batch_buffers* b) {
-  if (!h || !b || !b->K_dev || b->count < 1) return -1;
+  if (!h) return -1;
+  if (!b || !b->K_dev || b->count < 1) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_set_batch: buffers with K_dev and count >= 1 are required");
+    return -1;
+  }
   const long need_k = (long)(h->np + 128) * h->buf.lda, need_z = (long)h->np * h->buf.lda;
   if (!h->have_data) { snprintf(h->err, sizeof(h->err), "mi_gp_set_batch: call mi_gp_set_data first (lda is taken from it)"); return -1; }
   if (b->stride_k < need_k || ((b->Z_dev || b->W_dev) && b->stride_zw < need_z) || (b->stride_k & 1) || (b->stride_zw & 1)) {

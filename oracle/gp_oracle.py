@@ -190,15 +190,16 @@ def lml(X, y, kerns, ops, theta, form="marginal", return_parts=False, extra_diag
     return val
 
 
-def lml_grad(X, y, kerns, ops, theta, form="marginal"):
+def lml_grad(X, y, kerns, ops, theta, form="marginal", extra_diag=None):
     """K7.  Analytic  dLML/dtheta_k = 1/2 tr((alpha alpha^T - K^-1) dK/dtheta_k)  for the
     natural parameters in the C-ABI layout (d/d jitter is returned too; it equals d/d gv).
     The reference gets the same quantity by reverse-mode autodiff inside pm.find_MAP /
-    pm.sample (gpmcmc.py:345,351)."""
+    pm.sample (gpmcmc.py:345,351).  ``extra_diag`` (a per-point diagonal, as in lml) does not
+    depend on theta: it enters through K, hence W, alone."""
     d = X.shape[1]
     nk = len(kerns)
     ls, kv, alpha, gv, jitter = split_theta(theta, d, nk)
-    val, L, beta = lml(X, y, kerns, ops, theta, form, return_parts=True)
+    val, L, beta = lml(X, y, kerns, ops, theta, form, return_parts=True, extra_diag=extra_diag)
     g = np.zeros(nk * d + 2 * nk + 2)
     if L is None:
         return val, g

@@ -107,6 +107,12 @@ def test_extra_diagonal(N, kernel):
     assert np.abs(gy - gy_ref).max() <= 1e-8 * np.abs(gy_ref).max()
     assert np.abs(gX - gX_ref).max() <= 1e-8 * np.abs(gX_ref).max()
     assert abs(gp.lml(theta) - ref) <= 1e-9 * abs(ref)
+    # the theta gradient under the diagonal, per component with the 1e-3 floor and the cond-scaled bound of
+    # test_gpu_random_sweep.py (the diagonal enters W = alpha alpha^T - K^-1 only)
+    _, g_ref = orc.lml_grad(X, y, kerns, ops, theta, extra_diag=v)
+    cond = np.linalg.cond(orc.noisy_cov(X, kerns, ops, theta, extra_diag=v))
+    scale = np.maximum(np.abs(g_ref), 1e-3 * np.abs(g_ref).max())
+    assert np.max(np.abs(g - g_ref) / scale) <= max(1e-7, 500.0 * cond * 2.2e-16), (g, g_ref)
     gp.set_diag(None)
     theta2 = orc.synth_theta(d, nkern=len(kerns))
     assert abs(gp.lml(theta2) - orc.lml(X, y, kerns, ops, theta2)) <= 1e-9 * abs(ref)

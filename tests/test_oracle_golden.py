@@ -114,6 +114,32 @@ def test_grad_finite_difference_composite():
         assert abs(fd - g[i]) <= 1e-5 * max(1.0, abs(fd)), (i, fd, g[i])
 
 
+@pytest.mark.parametrize("kerns,ops", [(["RBF"], []), (["Matern52", "RBF"], ["+"]), (["RatQuad"], [])])
+def test_grad_with_extra_diagonal_finite_difference(kerns, ops):
+    """lml_grad(..., extra_diag=v) is the derivative of lml(..., extra_diag=v): the per-point diagonal does not depend on
+    theta but changes K^-1, hence every component -- and it is large enough here that ignoring it would fail."""
+    N, d = 50, 2
+    nk = len(kerns)
+    X, y = orc.synth_problem(N, d, seed=11)
+    theta = orc.synth_theta(d, nkern=nk, gv=2e-3, jitter=1e-3)
+    if kerns == ["RatQuad"]:
+        theta[nk * d + nk] = 0.8
+    v = 10.0 ** np.random.default_rng(3).uniform(-3, -1, N)
+    val, g = orc.lml_grad(X, y, kerns, ops, theta, extra_diag=v)
+    assert val == orc.lml(X, y, kerns, ops, theta, extra_diag=v)
+    _, g0 = orc.lml_grad(X, y, kerns, ops, theta)
+    assert np.abs(g - g0).max() > 1e-3 * np.abs(g0).max()
+    for i in range(len(theta)):
+        if kerns != ["RatQuad"] and nk * d + nk <= i < nk * d + 2 * nk:
+            continue  # alpha of a non-RatQuad component: no dependence
+        h = 1e-6 * max(1.0, abs(theta[i])) if i < nk * d + 2 * nk else 1e-7
+        tp, tm = theta.copy(), theta.copy()
+        tp[i] += h
+        tm[i] -= h
+        fd = (orc.lml(X, y, kerns, ops, tp, extra_diag=v) - orc.lml(X, y, kerns, ops, tm, extra_diag=v)) / (2 * h)
+        assert abs(fd - g[i]) <= 1e-5 * max(1.0, abs(fd)), (i, fd, g[i])
+
+
 def test_non_pd_gives_minus_inf():
     X = np.zeros((4, 1))
     y = np.ones(4)
