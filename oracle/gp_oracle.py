@@ -24,6 +24,8 @@ oracle is therefore pinned by (tests/test_oracle_golden.py):
 That is "parity unpinned" in the strict sense of the task contract (no reference-run
 outputs exist to compare with); DESIGN.md says so too.
 """
+import os
+
 import numpy as np
 import scipy.linalg as sla
 
@@ -332,6 +334,217 @@ def predict(X, y, Xnew, kerns, ops, theta, pred_noise=True):
         s = np.sqrt(gv)
         var = var + s * s
     return mu, var
+
+
+def sigma_joint(X, Xn, kerns, ops, theta, pred_noise=True, L=None):
+    """Sigma of [3P] Marginal._build_conditional(diag=False): Kss - A^T A (+ sqrt(gv)^2 I | + jitter I), A = L^-1 K(X, Xn),
+    Kss in the full-matrix form (its diagonal is k(sqrt(1e-12)) for the Matern / Exponential kernels).  ``L``: the lower
+    Cholesky factor of the noisy covariance, if the caller has it (conditional form otherwise)."""
+    _, _, _, gv, jitter = split_theta(theta, X.shape[1], len(kerns))
+    if L is None:
+        L = sla.cholesky(noisy_cov(X, kerns, ops, theta, form="conditional"), lower=True)
+    A = sla.solve_triangular(L, kernel_matrix(X, Xn, kerns, ops, theta), lower=True)
+    S = kernel_matrix(Xn, None, kerns, ops, theta) - A.T @ A
+    S[np.diag_indices_from(S)] += np.sqrt(gv) ** 2 if pred_noise else jitter
+    return S
+
+
+# ------------------------------------------------------------- row-blocked form
+def _blas_limit(n):
+    """threadpoolctl's limit on the BLAS threads (a no-op context without threadpoolctl)."""
+    try:
+        import threadpoolctl
+
+        return threadpoolctl.threadpool_limits(limits=n)
+    except Exception:
+        import contextlib
+
+        return contextlib.nullcontext()
+
+
+def _host_workers():
+    try:
+        from bench import host_cores
+
+        return max(1, min(host_cores(), 16))
+    except Exception:
+        return max(1, min(os.cpu_count() or 1, 16))
+
+
+def _cross_r2(Xa, Xb, ls):
+    """square_dist(Xa, Xb, ls) for a block of rows Xa against all points Xb (the expansion form + clip)."""
+    A, B = Xa * (1.0 / ls), Xb * (1.0 / ls)
+    sqd = -2.0 * np.dot(A, B.T) + (np.sum(np.square(A), 1).reshape(-1, 1) + np.sum(np.square(B), 1).reshape(1, -1))
+    return np.clip(sqd, 0.0, np.inf)
+
+
+def _fold_coefs(comps, ops):
+    """dK/dK_c of the left-to-right +/* fold for every component c (arrays, or the scalar 1.0 for a pure sum)."""
+    nk = len(comps)
+    pref, T = [1.0], comps[0]
+    for i in range(1, nk):
+        pref.append(1.0 if ops[i - 1] == "+" else T)
+        T = T + comps[i] if ops[i - 1] == "+" else T * comps[i]
+    coefs = []
+    for c in range(nk):
+        coef = pref[c]
+        for i in range(c + 1, nk):
+            if ops[i - 1] == "*":
+                coef = coef * comps[i]
+        coefs.append(coef)
+    return coefs
+
+
+def lml_all_blocked(X, y, kerns, ops, theta, extra_diag=None, Xnew=None, Xgrad=None, Xcov=None, pred_noise=True,
+                    form="marginal", block=64, workers=None):
+    """Everything ``lml`` / ``lml_grad`` / ``lml_grad_data`` / ``predict`` / ``predict_grad`` / ``sigma_joint`` return,
+    from ONE Cholesky factorisation and without their N x N temporaries, for N up to ~16k.
+
+    The formulas are theirs, evaluated over blocks of ``block`` rows of W = alpha alpha^T - K^-1 against all columns (the
+    squared distances in the expansion form of square_dist, K bit for bit the whole-matrix oracle's, the explicit differences (x_im - x_jm) of the gradients kept per
+    block: a G @ X rewrite would cancel).  K is assembled by row blocks, factored in place, and K^-1 formed in place from a
+    copy of L (LAPACK dpotri), so that the peak stays at about three N x N arrays (K and one component's Gram matrix; then L, K^-1 and the
+    blocks in flight).  The
+    blocks run on a thread pool of min(host cores, 16) workers (NumPy's ufuncs release the GIL) with one BLAS thread each.
+
+    Returns a dict: lml, logdet (sum log diag L), quad (y^T K^-1 y), grad (theta, the C-ABI layout), gy, gX; with ``Xnew``
+    mu / var (predict, ``pred_noise``); with ``Xgrad`` dmu / dvar (predict_grad); with ``Xcov`` cov (sigma_joint,
+    ``pred_noise``); L, the factor itself (for cond2_spd).  Predictions come from this factor of ``form`` ('conditional' is
+    predict's order of the two diagonal additions; the other differs from it by rounding)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    n, d = X.shape
+    nk = len(kerns)
+    ls, kv, alpha, gv, jitter = split_theta(theta, d, nk)
+    workers = workers or _host_workers()
+    blocks = [(r0, min(r0 + block, n)) for r0 in range(0, n, block)]
+    K = np.empty((n, n))
+    for c in range(nk):
+        # the Gram matrix as square_dist forms it (one N x N product: a row-blocked product rounds differently, and the
+        # blocked form is to return the whole-matrix oracle's K bit for bit), then the kernel and the fold by row blocks
+        Xa = X * (1.0 / ls[c])
+        X2 = np.sum(np.square(Xa), 1)
+        with _blas_limit(workers):
+            gram = np.dot(Xa, Xa.T)
+
+        def fold(rs, c=c, gram=gram, X2=X2):
+            r0, r1 = rs
+            r2 = np.clip(-2.0 * gram[r0:r1] + (X2[r0:r1].reshape(-1, 1) + X2.reshape(1, -1)), 0.0, np.inf)
+            kc = kv[c] * base_kernel(kerns[c], r2, alpha[c])
+            if c == 0:
+                K[r0:r1] = kc
+            elif ops[c - 1] == "+":
+                K[r0:r1] += kc
+            else:
+                K[r0:r1] *= kc
+
+        with _blas_limit(1), ThreadPoolExecutor(workers) as pool:
+            list(pool.map(fold, blocks))
+        del gram
+    idx = np.arange(n)
+    s = np.sqrt(gv)
+    first, second = (s * s, jitter) if form == "marginal" else (jitter, s * s)
+    K[idx, idx] += first
+    K[idx, idx] += second
+    if extra_diag is not None:
+        K[idx, idx] += np.asarray(extra_diag, dtype=np.float64)
+    with _blas_limit(workers):
+        L = sla.cholesky(K, lower=True, overwrite_a=True, check_finite=False)
+        del K
+        beta = sla.solve_triangular(L, y, lower=True)
+        a = sla.solve_triangular(L, beta, lower=True, trans="T")
+        Kinv, info = sla.lapack.dpotri(L, lower=1, overwrite_c=0)
+        if info != 0:
+            raise np.linalg.LinAlgError(f"dpotri: info {info}")
+    for r0, r1 in blocks:  # symmetrise in place: the upper triangle from the lower, one block of rows at a time
+        Kinv[r0:r1, r1:] = Kinv[r1:, r0:r1].T
+        t = Kinv[r0:r1, r0:r1]
+        t[np.triu_indices(r1 - r0, 1)] = t.T[np.triu_indices(r1 - r0, 1)]
+    quad = float(beta @ beta)
+    logdet = float(np.sum(np.log(np.diag(L))))
+
+    def grads(rs):
+        r0, r1 = rs
+        Xr = X[r0:r1]
+        W = np.outer(a[r0:r1], a) - Kinv[r0:r1]
+        r2s = [_cross_r2(Xr, X, ls[c]) for c in range(nk)]
+        comps = [kv[c] * base_kernel(kerns[c], r2s[c], alpha[c]) for c in range(nk)]
+        coefs = _fold_coefs(comps, ops)
+        g = np.zeros(nk * d + 2 * nk + 2)
+        gX = np.zeros((r1 - r0, d))
+        for c in range(nk):
+            WC = W * coefs[c]
+            dk = kv[c] * base_kernel_dr2(kerns[c], r2s[c], alpha[c])
+            dk = np.where(r2s[c] > 0.0, dk, 0.0)
+            G = WC * dk
+            for m in range(d):
+                diff = Xr[:, m : m + 1] - X[:, m].reshape(1, -1)
+                ds = diff * (1.0 / ls[c, m])
+                g[c * d + m] = 0.5 * np.sum(G * (-2.0 * ds ** 2 / ls[c, m]))
+                gX[:, m] += np.sum(G * diff, axis=1) * (2.0 / ls[c, m] ** 2)
+            g[nk * d + c] = 0.5 * np.sum(WC * comps[c]) / kv[c]
+            if kerns[c] == "RatQuad":
+                u = 0.5 * r2s[c] / alpha[c]
+                g[nk * d + nk + c] = 0.5 * np.sum(WC * (comps[c] * (-np.log1p(u) + u / (1.0 + u))))
+        g[nk * d + 2 * nk] = g[nk * d + 2 * nk + 1] = 0.5 * np.sum(W[np.arange(r1 - r0), np.arange(r0, r1)])
+        return g, gX
+
+    with _blas_limit(1), ThreadPoolExecutor(workers) as pool:
+        parts = list(pool.map(grads, blocks))
+    del Kinv
+    out = {"lml": -0.5 * n * np.log(2.0 * np.pi) - 0.5 * quad - logdet, "logdet": logdet, "quad": quad,
+           "grad": np.sum([p[0] for p in parts], axis=0), "gy": -a, "gX": np.concatenate([p[1] for p in parts]), "L": L}
+    with _blas_limit(workers):
+        if Xnew is not None:
+            A = sla.solve_triangular(L, kernel_matrix(X, Xnew, kerns, ops, theta), lower=True)
+            out["mu"] = A.T @ beta
+            var = kernel_diag(kerns, ops, theta, d) - np.sum(np.square(A), 0)
+            out["var"] = var + s * s if pred_noise else var
+        if Xgrad is not None:
+            dmu, dvar = np.zeros(Xgrad.shape), np.zeros(Xgrad.shape)
+            for p in range(Xgrad.shape[0]):
+                xs = Xgrad[p : p + 1]
+                comps, r2s = component_matrices(X, xs, kerns, ls, kv, alpha)
+                w = sla.cho_solve((L, True), combine(comps, ops)[:, 0])
+                coefs = _fold_coefs(comps, ops)
+                for c in range(nk):
+                    dk = kv[c] * base_kernel_dr2(kerns[c], r2s[c], alpha[c])
+                    gcol = (coefs[c] * np.where(r2s[c] > 0.0, dk, 0.0))[:, 0]
+                    for m in range(d):
+                        dkx = gcol * 2.0 * (xs[0, m] - X[:, m]) / ls[c, m] ** 2
+                        dmu[p, m] += a @ dkx
+                        dvar[p, m] += -2.0 * (w @ dkx)
+            out["dmu"], out["dvar"] = dmu, dvar
+        if Xcov is not None:
+            out["cov"] = sigma_joint(X, Xcov, kerns, ops, theta, pred_noise, L=L)
+    return out
+
+
+def cond2_spd(L, iters=300, rtol=1e-3, seed=0):
+    """2-norm condition number of K = L L^T: lambda_max by power iteration on K, lambda_min by inverse power iteration through
+    the two triangular solves with L (Rayleigh quotients, O(N^2) per step; np.linalg.cond's SVD is impractical above ~5k).
+    Both quotients approach their eigenvalue from inside the spectrum, so the estimate is at most the true condition number."""
+    n = L.shape[0]
+    rng = np.random.default_rng(seed)
+
+    def extreme(apply):
+        v = rng.standard_normal(n)
+        v /= np.linalg.norm(v)
+        lam = 0.0
+        for _ in range(iters):
+            w = apply(v)
+            new = float(v @ w)
+            v = w / np.linalg.norm(w)
+            if abs(new - lam) <= rtol * abs(new):
+                return new
+            lam = new
+        return lam
+
+    lmax = extreme(lambda v: L @ (L.T @ v))
+    inv = extreme(lambda v: sla.solve_triangular(L, sla.solve_triangular(L, v, lower=True), lower=True, trans="T"))
+    return lmax * inv
 
 
 # ---------------------------------------------------------- synthetic workloads

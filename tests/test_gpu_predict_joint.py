@@ -34,14 +34,8 @@ def _kd(orc, kerns, ops, theta, d):
 
 def _sigma_ref(orc, X, Xn, kerns, ops, theta, pred_noise):
     """Sigma of [3P] Marginal._build_conditional(diag=False): Kss - A^T A (+ sqrt(gv)^2 I | + jitter I), Kss in the
-    full-matrix form (its diagonal is k(sqrt(1e-12)) for the Matern / Exponential kernels)."""
-    _, _, _, gv, jitter = orc.split_theta(theta, X.shape[1], len(kerns))
-    K = orc.noisy_cov(X, kerns, ops, theta, form="conditional")
-    L = sla.cholesky(K, lower=True)
-    A = sla.solve_triangular(L, orc.kernel_matrix(X, Xn, kerns, ops, theta), lower=True)
-    S = orc.kernel_matrix(Xn, None, kerns, ops, theta) - A.T @ A
-    S[np.diag_indices_from(S)] += np.sqrt(gv) ** 2 if pred_noise else jitter
-    return S
+    full-matrix form (its diagonal is k(sqrt(1e-12)) for the Matern / Exponential kernels): oracle.sigma_joint."""
+    return orc.sigma_joint(X, Xn, kerns, ops, theta, pred_noise)
 
 
 def _low(gp, torch, Xn, pred_noise, ldc_extra=0):
