@@ -9,12 +9,14 @@
 //
 // Two kernels, one design:
 //   gemm_f64_kernel_b : 128x128 output tile per 256-thread workgroup (4 waves as 2x2, 64x64 per wave = 4x4 MFMA tiles =
-//                       64 accumulator doubles per lane), K consumed in chunks of 16 through a double-buffered LDS image
-//                       stored k-major ([k][x], leading dimension 144 doubles so both halves of a ds_read_b64 wave access
-//                       hit disjoint banks), 72 KiB of LDS -> two workgroups per CU.  Global -> register prefetch runs
-//                       two chunks ahead, registers -> LDS one chunk ahead, MFMA operand fragments are double-buffered in
-//                       registers one k4-step ahead, and sched_group_barrier spreads the memory instructions between
-//                       the 64 MFMAs of a chunk.
+//                       64 accumulator doubles per lane).  NT form (both operands row-major, the Cholesky's bulk updates):
+//                       K in chunks of 8 filled global -> LDS by LDS-DMA (global_load_lds, 16 bytes per lane, no VGPR
+//                       staging) into four LDS stages of a row-major, XOR-swizzled image (64 KiB), requested three
+//                       chunks ahead so that one stays in flight across every chunk barrier.  Forms with a k-major operand: K in chunks of 16 through a double-
+//                       buffered k-major LDS image ([k][x], leading dimension 144 doubles so both halves of a ds_read_b64
+//                       wave access hit disjoint banks, 72 KiB), global -> register prefetch two chunks ahead, registers ->
+//                       LDS one chunk ahead.  Both: two workgroups per CU, MFMA operand fragments double-buffered in
+//                       registers one k4-step ahead, sched_group_barrier spreads the memory instructions between the MFMAs.
 //   gemm_f64_kernel_s : the same schedule on 64x64 tiles for launches with too few 128x128 tiles to fill the chip; its
 //                       row-major operands are fetched as whole 128-byte row segments and stored XOR-swizzled (round 4).
 //
@@ -131,14 +133,6 @@ constexpr int BKB = 16;
 constexpr int OPER_B = BKB * LDS_LD;
 constexpr int NT_B = 256;
 constexpr int NQB = TILE * BKB / 2 / NT_B;  // 4
-// Coalesced row-major operand loads + XOR-swizzled LDS image (chunk_offsets), as in the 64x64-tile kernel, where they are
-// worth 1.3 % of an N = 16384 evaluation.  OFF here: this kernel needs half the bytes per flop and is not bound by what a CU
-// can fetch -- with the swizzle an evaluation measures 25.72-25.89 ms against 25.81-25.84 without (same box, alternating),
-// and the eight fragment bases instead of two cost 6 more spilled VGPRs (10 instead of 4) at the 256-register ceiling.
-#ifndef MIGP_SWZ_B
-#define MIGP_SWZ_B 0
-#endif
-constexpr bool SWZ = MIGP_SWZ_B != 0;
 
 template <bool KMAJOR>
 __device__ __forceinline__ void chunk_offsets(long ld, int tid, unsigned& goff, unsigned& loff, long& gstride) {
@@ -147,12 +141,6 @@ __device__ __forceinline__ void chunk_offsets(long ld, int tid, unsigned& goff, 
     goff = (unsigned)((k * ld + 2 * xc) * 8);
     loff = (unsigned)((k * LDS_LD + 2 * xc) * 8);
     gstride = 4 * ld * 8;
-  } else if (SWZ) {
-    // coalesced row segments + XOR-swizzled image, as in the 64x64-tile kernel (vs::chunk_offsets has the reasoning)
-    const int kc = tid & 7, row = tid >> 3;  // x = 32q + (t>>3), k = 2 (t&7)
-    goff = (unsigned)((row * ld + 2 * kc) * 8);
-    loff = (unsigned)(((2 * kc) * LDS_LD + (row ^ (2 * kc))) * 8);
-    gstride = 32 * ld * 8;
   } else {
     const int xl = tid & 15, kc = (tid >> 4) & 7, xh = tid >> 7;  // x = 32q + 16*(t>>7) + (t&15)
     goff = (unsigned)(((xh * 16 + xl) * ld + 2 * kc) * 8);
@@ -176,6 +164,43 @@ __device__ __forceinline__ void chunk_store(char* __restrict__ lds, unsigned lof
       *reinterpret_cast<double*>(lds + loff + q * (32 * 8) + LDS_LD * 8) = r[q].y;
     }
   }
+}
+
+// NT form: LDS-DMA operand path.  A stage holds one chunk of BKD = 8 k of both operands, each a row-major image of 128 rows x
+// 64 bytes in 16-byte (row, k pair) units, unit (x, kp) at byte 64 x + 16 (kp ^ ((x >> 2) & 3)).  An LDS-DMA writes 64 lanes x
+// 16 bytes contiguously (1 KiB = 16 rows), so the swizzle goes on the global source address: lane l of a wave instruction
+// fetches k pair (l & 3) ^ ((l >> 4) & 3) of row l >> 2 and lands at unit l.  A fragment read (16 consecutive rows at one k
+// pair, 8 bytes per lane, two k of the pair in each 32-lane half) then covers all 64 banks once.  Four stages (64 KiB): the
+// chunk c + 3 is requested at the start of chunk c and stays in flight across the barrier that ends it.
+constexpr int BKD = 8;
+constexpr int NSTG = 4;
+constexpr int STG_OPER = TILE * BKD * 8;           // bytes of one operand's stage (8 KiB)
+constexpr int STG_B = NSTG * STG_OPER;              // byte offset of B's stages
+constexpr int DMA_PER_CHUNK = 2 * (STG_OPER / (NT_B * 16));  // LDS-DMA instructions per wave and chunk (A and B): 4
+constexpr size_t LDS_DMA = 2 * NSTG * STG_OPER;      // 64 KiB
+
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef __attribute__((address_space(1))) void* gbl_ptr_t;
+
+// per-lane source offset of this thread's first piece (rows 16 (4 q + wave) + (lane >> 2)) and the stride between its pieces
+__device__ __forceinline__ void dma_offsets(long ld, int tid, unsigned& goff, long& gstride) {
+  const int l = tid & 63, w = tid >> 6;
+  const int row = 16 * w + (l >> 2), kp = (l & 3) ^ ((l >> 4) & 3);
+  goff = (unsigned)((row * ld + 2 * kp) * 8);
+  gstride = 64 * ld * 8;
+}
+// one operand's chunk into the stage at `lds_stage`: two wave instructions of 16 rows (1 KiB) each, pieces 4 q + wave
+__device__ __forceinline__ void dma_chunk(const char* __restrict__ g, unsigned goff, long gstride, char* lds_stage, int wave) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(g + q * gstride + goff), (lds_ptr_t)(lds_stage + (4 * q + wave) * 1024), 16, 0, 0);
+}
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  static_assert(N == 4 || N == 16 || N == 20, "vmcnt");
+  if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
 }
 }  // namespace vb
 
@@ -232,68 +257,9 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
 #pragma unroll
     for (int b = 0; b < 4; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
 
-  const int nchunk = (kend - kbeg) / BKB;
-  unsigned gA, lA, gB, lB;
-  long sA, sB;
-  vb::chunk_offsets<A_KMAJOR>(p.lda, tid, gA, lA, sA);
-  vb::chunk_offsets<B_KMAJOR>(p.ldb, tid, gB, lB, sB);
-  const char* Ag = reinterpret_cast<const char*>(A_KMAJOR ? A + (long)kbeg * p.lda + i0 : A + (long)i0 * p.lda + kbeg);
-  const char* Bg = reinterpret_cast<const char*>(B_KMAJOR ? B + (long)kbeg * p.ldb + j0 : B + (long)j0 * p.ldb + kbeg);
-  const long stepA = (A_KMAJOR ? (long)BKB * p.lda : (long)BKB) * 8;
-  const long stepB = (B_KMAJOR ? (long)BKB * p.ldb : (long)BKB) * 8;
-  // k-segmented operands: the step INTO chunk n is a jump to the next segment's base when n is a multiple of kseg / BKB
-  const int segmask = p.kseg > 0 ? p.kseg / BKB - 1 : 0x7fffffff;
-  const long segjump = (p.kseg_stride - (long)(p.kseg - BKB)) * 8;
-  char* Asb = reinterpret_cast<char*>(As);
-  char* Bsb = reinterpret_cast<char*>(Bs);
-  // Global -> register prefetch runs TWO chunks ahead (register set c & 1 holds chunk c until it is written to
-  // LDS buffer c & 1 during chunk c - 1): ~7k cycles of latency tolerance instead of ~3k, enough for an
-  // HBM / MALL miss under load while two workgroups share the CU.
-  double2_t ra[2][NQB], rb[2][NQB];
-  if (nchunk > 0) {
-    vb::chunk_load(Ag, gA, sA, ra[0]);
-    vb::chunk_load(Bg, gB, sB, rb[0]);
-    if (nchunk > 1) {
-      Ag += stepA;
-      Bg += stepB;
-      vb::chunk_load(Ag, gA, sA, ra[1]);
-      vb::chunk_load(Bg, gB, sB, rb[1]);
-    }
-    vb::chunk_store<A_KMAJOR>(Asb, lA, ra[0]);
-    vb::chunk_store<B_KMAJOR>(Bsb, lB, rb[0]);
-  }
-  __syncthreads();
-
   const int kq = lane >> 4, l15 = lane & 15;
-  const double* a_ptr[4];  // per k4-step: the row-major operands' images are swizzled by the k pair, k & 14 = 4 kk + (kq & 2)
-  const double* b_ptr[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    const int sa = (vb::SWZ && !A_KMAJOR) ? (4 * kk + (kq & 2)) : 0, sb = (vb::SWZ && !B_KMAJOR) ? (4 * kk + (kq & 2)) : 0;
-    a_ptr[kk] = As + kq * LDS_LD + wr * 64 + (l15 ^ sa);
-    b_ptr[kk] = Bs + kq * LDS_LD + wc * 64 + (l15 ^ sb);
-  }
   double af[2][4], bf[2][4];
-  auto load_frags = [&](int set, int boff, int kk) {
-    const double* ap = a_ptr[kk] + boff + kk * 4 * LDS_LD;
-    const double* bp = b_ptr[kk] + boff + kk * 4 * LDS_LD;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) af[set][a] = ap[16 * a];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) bf[set][b] = bp[16 * b];
-  };
-  if (nchunk > 0) load_frags(0, 0, 0);
-
-  // one chunk; S = c & 1 selects both the LDS buffer being consumed and the register set being refilled.
-  // The body is branch-free (loads / stores of the last chunks are redundant instead of skipped) so that it is
-  // one scheduling region, and sched_group_barrier spreads the memory instructions between the 64 MFMAs:
-  //   k4-step 0: 8 global loads (chunk c+2) + the 4 ds_read2 of step 1     step 1, 2: the 4 ds_read2 of the next step
-  //   k4-step 3: the 8 ds_write2 of chunk c+1
-  // A burst of LDS / VMEM issue in both co-resident workgroups at once left the MFMA pipe 88 % busy; spread out
-  // it is 93 % (8192^3: 70.3 -> 73.3 TFLOP/s, rocBLAS 72.9).
-  // C read-modify-write: the first two of its four row groups are requested during the LAST two chunks of the k loop (in
-  // place of those chunks' global prefetches, which would be redundant reloads), so that their round trip hides under
-  // 128 MFMAs instead of following the loop
+  // C read-modify-write: the first two of its four row groups are requested inside the last chunks of the k loop
   const double alpha = p.alpha, beta = p.beta;
   double* cbase = C + (long)(rc * TILE + wr * 64 + kq) * p.ldc + cc * TILE + wc * 64 + l15;
   double4_t cv[2][4];
@@ -303,75 +269,249 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) cv[set][b][r] = cbase[(long)(16 * a + 4 * r) * p.ldc + 16 * b];
   };
-  auto chunk_body = [&](int c, auto S, auto LASTC) {
-    constexpr int s = decltype(S)::value;
-    constexpr int lastc = decltype(LASTC)::value;  // 0: inside the loop; 1 / 2: second-to-last / last chunk
-    constexpr int boff = s * OPER_B;
-    const bool adv = (c + 2 < nchunk);
-    const bool seg = ((c + 2) & segmask) == 0;
-    Ag += adv ? (seg ? segjump : stepA) : 0;
-    Bg += adv ? (seg ? segjump : stepB) : 0;
+  if constexpr (!A_KMAJOR && !B_KMAJOR) {
+    // LDS-DMA operand path (vb::dma_offsets has the image).  Chunk c (BKD = 8 k: two k4-steps of 16 MFMAs per wave) is read from
+    // stage c & 3; at its start the chunk c + 3 is requested into stage (c + 3) & 3, which chunk c - 1 has left at the last
+    // barrier.  At its end each wave waits for ITS part of chunk c + 2 (a counted vmcnt: chunk c + 3 stays in flight) and the
+    // barrier makes every wave's part visible; chunk c + 1's first fragments are read during chunk c's second k4-step, one
+    // barrier after the wait that retired them.  The last four chunks request no operands: chunk n - 4 requests C row group 0
+    // (after its DMA, so that the counts hold), chunk n - 2 row group 1.
+    using vb::BKD; using vb::STG_OPER; using vb::STG_B;
+    char* lds = reinterpret_cast<char*>(smem);
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const int nchunk = (kend - kbeg) / BKD;  // a multiple of 4 and >= 4 (k and the triangular k ranges are multiples of 32)
+    unsigned gA, gB;
+    long sA, sB;
+    vb::dma_offsets(p.lda, tid, gA, sA);
+    vb::dma_offsets(p.ldb, tid, gB, sB);
+    const char* Ag = reinterpret_cast<const char*>(A + (long)i0 * p.lda + kbeg);
+    const char* Bg = reinterpret_cast<const char*>(B + (long)j0 * p.ldb + kbeg);
+    // k-segmented operands: the step INTO chunk n is a jump to the next segment's base when n is a multiple of kseg / BKD
+    const int segmask = p.kseg > 0 ? p.kseg / BKD - 1 : 0x7fffffff;
+    const long segjump = (p.kseg_stride - (long)(p.kseg - BKD)) * 8;
+    auto advance = [&](int next_chunk) {
+      const long d = (next_chunk & segmask) == 0 ? segjump : (long)BKD * 8;
+      Ag += d;
+      Bg += d;
+    };
+    auto request = [&](int stg) {
+      vb::dma_chunk(Ag, gA, sA, lds + stg * STG_OPER, wv);
+      vb::dma_chunk(Bg, gB, sB, lds + STG_B + stg * STG_OPER, wv);
+    };
+    // fragment offsets of k4-steps 0 / 1: row l15 of a 16-row block, k = 4 kk + kq -> k pair 2 kk + (kq >> 1), half kq & 1
+    unsigned foff[2];
 #pragma unroll
-    for (int kk = 0; kk < BKB / 4; ++kk) {
-      const int cur = kk & 1;
-      __builtin_amdgcn_sched_barrier(0);
-      if (kk == 0) {
-        if (lastc == 0) {
-          vb::chunk_load(Ag, gA, sA, ra[s]);
-          vb::chunk_load(Bg, gB, sB, rb[s]);
+    for (int kk = 0; kk < 2; ++kk) foff[kk] = (unsigned)(l15 * 64 + (((2 * kk + (kq >> 1)) ^ (l15 >> 2)) * 16) + (kq & 1) * 8);
+    const char* a_lds = lds + wr * 64 * 64;
+    const char* b_lds = lds + STG_B + wc * 64 * 64;
+    auto load_frags = [&](int set, int stg, int kk) {
+      const char* ap = a_lds + stg * STG_OPER + foff[kk];
+      const char* bp = b_lds + stg * STG_OPER + foff[kk];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) af[set][a] = *reinterpret_cast<const double*>(ap + 1024 * a);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) bf[set][b] = *reinterpret_cast<const double*>(bp + 1024 * b);
+    };
+    request(0);
+    advance(1);
+    request(1);
+    advance(2);
+    request(2);
+    advance(3);
+    vb::wait_vm<vb::DMA_PER_CHUNK>();  // chunks 0 and 1
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    load_frags(0, 0, 0);
+    // MODE 0: inside the loop; 1 .. 4: chunk n - 4 .. n - 1
+    auto chunk_body = [&](int c, auto S, auto MODE) {
+      constexpr int s = decltype(S)::value;
+      constexpr int mode = decltype(MODE)::value;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (kk == 0 && mode <= 1) {
+          request((s + 3) & 3);
+          advance(c + 4);
+        }
+        if (kk == 1 && mode == 1) load_group(0, 0);
+        if (kk == 0 && mode == 3) load_group(1, 1);
+        if (kk == 0) load_frags(1, s, 1);
+        else if (mode != 4) load_frags(0, (s + 1) & 3, 0);
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[kk][a], bf[kk][b], acc[a][b], 0, 0, 0);
+        if (kk == 0 && mode <= 1) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+          }
+        } else if (mode == 1 || (kk == 0 && mode == 3)) {
+#pragma unroll
+          for (int g = 0; g < 8; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
         } else {
-          load_group(lastc - 1, lastc - 1);
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+          }
         }
       }
-      if (kk + 1 < BKB / 4) load_frags(cur ^ 1, boff, kk + 1);
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[cur][a], bf[cur][b], acc[a][b], 0, 0, 0);
-      if (kk == BKB / 4 - 1) {
-        constexpr int noff = (boff ^ OPER_B) * 8;
-        vb::chunk_store<A_KMAJOR>(Asb + noff, lA, ra[s ^ 1]);
-        vb::chunk_store<B_KMAJOR>(Bsb + noff, lB, rb[s ^ 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (mode <= 2) {
+        // this wave's part of chunk c + 2 has landed (chunk c + 3 and C row group 0 may be in flight), then the barrier
+        vb::wait_vm<mode == 0 ? vb::DMA_PER_CHUNK : mode == 1 ? vb::DMA_PER_CHUNK + 16 : 16>();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
       }
-      if (kk == 0) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-      } else if (kk + 1 < BKB / 4) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-      } else {
-        constexpr int nw = (A_KMAJOR ? NQB : 2 * NQB) + (B_KMAJOR ? NQB : 2 * NQB);  // ds_write instructions
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if (g < nw) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        }
-      }
+    };
+    int c = 0;
+    for (; c + 4 < nchunk; c += 4) {
+      chunk_body(c, std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
+      chunk_body(c + 1, std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
+      chunk_body(c + 2, std::integral_constant<int, 2>(), std::integral_constant<int, 0>());
+      chunk_body(c + 3, std::integral_constant<int, 3>(), std::integral_constant<int, 0>());
     }
-    __builtin_amdgcn_sched_barrier(0);
+    chunk_body(c, std::integral_constant<int, 0>(), std::integral_constant<int, 1>());
+    chunk_body(c + 1, std::integral_constant<int, 1>(), std::integral_constant<int, 2>());
+    chunk_body(c + 2, std::integral_constant<int, 2>(), std::integral_constant<int, 3>());
+    chunk_body(c + 3, std::integral_constant<int, 3>(), std::integral_constant<int, 4>());
+  } else {
+    const int nchunk = (kend - kbeg) / BKB;
+    unsigned gA, lA, gB, lB;
+    long sA, sB;
+    vb::chunk_offsets<A_KMAJOR>(p.lda, tid, gA, lA, sA);
+    vb::chunk_offsets<B_KMAJOR>(p.ldb, tid, gB, lB, sB);
+    const char* Ag = reinterpret_cast<const char*>(A_KMAJOR ? A + (long)kbeg * p.lda + i0 : A + (long)i0 * p.lda + kbeg);
+    const char* Bg = reinterpret_cast<const char*>(B_KMAJOR ? B + (long)kbeg * p.ldb + j0 : B + (long)j0 * p.ldb + kbeg);
+    const long stepA = (A_KMAJOR ? (long)BKB * p.lda : (long)BKB) * 8;
+    const long stepB = (B_KMAJOR ? (long)BKB * p.ldb : (long)BKB) * 8;
+    // k-segmented operands: the step INTO chunk n is a jump to the next segment's base when n is a multiple of kseg / BKB
+    const int segmask = p.kseg > 0 ? p.kseg / BKB - 1 : 0x7fffffff;
+    const long segjump = (p.kseg_stride - (long)(p.kseg - BKB)) * 8;
+    char* Asb = reinterpret_cast<char*>(As);
+    char* Bsb = reinterpret_cast<char*>(Bs);
+    // Global -> register prefetch runs TWO chunks ahead (register set c & 1 holds chunk c until it is written to
+    // LDS buffer c & 1 during chunk c - 1): ~7k cycles of latency tolerance instead of ~3k, enough for an
+    // HBM / MALL miss under load while two workgroups share the CU.
+    double2_t ra[2][NQB], rb[2][NQB];
+    if (nchunk > 0) {
+      vb::chunk_load(Ag, gA, sA, ra[0]);
+      vb::chunk_load(Bg, gB, sB, rb[0]);
+      if (nchunk > 1) {
+        Ag += stepA;
+        Bg += stepB;
+        vb::chunk_load(Ag, gA, sA, ra[1]);
+        vb::chunk_load(Bg, gB, sB, rb[1]);
+      }
+      vb::chunk_store<A_KMAJOR>(Asb, lA, ra[0]);
+      vb::chunk_store<B_KMAJOR>(Bsb, lB, rb[0]);
+    }
     __syncthreads();
-    load_frags(0, boff ^ OPER_B, 0);
-  };
-  int c = 0;
-  for (; c + 2 < nchunk; c += 2) {  // k is a multiple of 128, so nchunk is even and >= 8
-    chunk_body(c, std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
-    chunk_body(c + 1, std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
+
+    const double* a_ptr = As + kq * LDS_LD + wr * 64 + l15;
+    const double* b_ptr = Bs + kq * LDS_LD + wc * 64 + l15;
+    auto load_frags = [&](int set, int boff, int kk) {
+      const double* ap = a_ptr + boff + kk * 4 * LDS_LD;
+      const double* bp = b_ptr + boff + kk * 4 * LDS_LD;
+  #pragma unroll
+      for (int a = 0; a < 4; ++a) af[set][a] = ap[16 * a];
+  #pragma unroll
+      for (int b = 0; b < 4; ++b) bf[set][b] = bp[16 * b];
+    };
+    if (nchunk > 0) load_frags(0, 0, 0);
+
+    // one chunk; S = c & 1 selects both the LDS buffer being consumed and the register set being refilled.
+    // The body is branch-free (loads / stores of the last chunks are redundant instead of skipped) so that it is
+    // one scheduling region, and sched_group_barrier spreads the memory instructions between the 64 MFMAs:
+    //   k4-step 0: 8 global loads (chunk c+2) + the 4 ds_read2 of step 1     step 1, 2: the 4 ds_read2 of the next step
+    //   k4-step 3: the 8 ds_write2 of chunk c+1
+    // A burst of LDS / VMEM issue in both co-resident workgroups at once left the MFMA pipe 88 % busy; spread out
+    // it is 93 % (8192^3: 70.3 -> 73.3 TFLOP/s, rocBLAS 72.9).
+    // C row groups 0 and 1 are requested during the LAST two chunks of the k loop (in place of those chunks' global prefetches,
+    // which would be redundant reloads), so that their round trip hides under 128 MFMAs instead of following the loop
+    auto chunk_body = [&](int c, auto S, auto LASTC) {
+      constexpr int s = decltype(S)::value;
+      constexpr int lastc = decltype(LASTC)::value;  // 0: inside the loop; 1 / 2: second-to-last / last chunk
+      constexpr int boff = s * OPER_B;
+      const bool adv = (c + 2 < nchunk);
+      const bool seg = ((c + 2) & segmask) == 0;
+      Ag += adv ? (seg ? segjump : stepA) : 0;
+      Bg += adv ? (seg ? segjump : stepB) : 0;
+  #pragma unroll
+      for (int kk = 0; kk < BKB / 4; ++kk) {
+        const int cur = kk & 1;
+        __builtin_amdgcn_sched_barrier(0);
+        if (kk == 0) {
+          if (lastc == 0) {
+            vb::chunk_load(Ag, gA, sA, ra[s]);
+            vb::chunk_load(Bg, gB, sB, rb[s]);
+          } else {
+            load_group(lastc - 1, lastc - 1);
+          }
+        }
+        if (kk + 1 < BKB / 4) load_frags(cur ^ 1, boff, kk + 1);
+  #pragma unroll
+        for (int a = 0; a < 4; ++a)
+  #pragma unroll
+          for (int b = 0; b < 4; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[cur][a], bf[cur][b], acc[a][b], 0, 0, 0);
+        if (kk == BKB / 4 - 1) {
+          constexpr int noff = (boff ^ OPER_B) * 8;
+          vb::chunk_store<A_KMAJOR>(Asb + noff, lA, ra[s ^ 1]);
+          vb::chunk_store<B_KMAJOR>(Bsb + noff, lB, rb[s ^ 1]);
+        }
+        if (kk == 0) {
+  #pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          }
+        } else if (kk + 1 < BKB / 4) {
+  #pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          }
+        } else {
+          constexpr int nw = (A_KMAJOR ? NQB : 2 * NQB) + (B_KMAJOR ? NQB : 2 * NQB);  // ds_write instructions
+  #pragma unroll
+          for (int g = 0; g < 16; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (g < nw) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      __syncthreads();
+      load_frags(0, boff ^ OPER_B, 0);
+    };
+    int c = 0;
+    for (; c + 2 < nchunk; c += 2) {  // k is a multiple of 128, so nchunk is even and >= 8
+      chunk_body(c, std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
+      chunk_body(c + 1, std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
+    }
+    chunk_body(c, std::integral_constant<int, 0>(), std::integral_constant<int, 1>());
+    chunk_body(c + 1, std::integral_constant<int, 1>(), std::integral_constant<int, 2>());
   }
-  chunk_body(c, std::integral_constant<int, 0>(), std::integral_constant<int, 1>());
-  chunk_body(c + 1, std::integral_constant<int, 1>(), std::integral_constant<int, 2>());
 
   if (beta != 0.0) {
     // row groups 0 and 1 are in registers; groups 2 and 3 are requested while 0 and 1 are stored
@@ -777,7 +917,8 @@ hipError_t launch_gemm_f64(const GemmParams& p_in, int opA_kmajor, int opB_kmajo
   const int big_end = t1 < nblk - tail ? t1 : nblk - tail;
   if (part != 2 && big_end > t0) {
     dim3 grid(big_end - t0, 1, batch), block(vb::NT_B);
-    const size_t lds = p.one_per_cu ? LDS_ONE_PER_CU : sizeof(double) * 4 * vb::OPER_B;
+    const bool dma = !opA_kmajor && !opB_kmajor;  // the NT form stages its operands by LDS-DMA (64 KiB), the others by registers
+    const size_t lds = p.one_per_cu ? LDS_ONE_PER_CU : dma ? vb::LDS_DMA : sizeof(double) * 4 * vb::OPER_B;
     if (!opA_kmajor && !opB_kmajor) gemm_f64_kernel_b<false, false><<<grid, block, lds, stream>>>(p);
     else if (!opA_kmajor && opB_kmajor) gemm_f64_kernel_b<false, true><<<grid, block, lds, stream>>>(p);
     else if (opA_kmajor && opB_kmajor) gemm_f64_kernel_b<true, true><<<grid, block, lds, stream>>>(p);
