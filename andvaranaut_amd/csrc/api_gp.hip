@@ -371,6 +371,9 @@ extern "C" int mi_gp_set_data(mi_gp_handle* h, const mi_gp_buffers* b) {
   }
   h->buf = *b;
   h->have_data = true;
+  // (the resident factor, U and K^-1 belong to the buffers they were computed in: mi_gp_predict* behind a rebind would read an
+  // unfactored K, mi_gp_alpha / mi_gp_grad_x another W)
+  h->factored = h->have_kinv = h->have_u = false;
   h->b_cond_k = 0;
   return 0;
 }

@@ -64,6 +64,9 @@ MI_GP_API int mi_gp_destroy(mi_gp_handle* h);
 MI_GP_API long mi_gp_padded_n(const mi_gp_handle* h);   /* n rounded up to a multiple of 128 */
 MI_GP_API int mi_gp_num_theta(const mi_gp_handle* h);   /* nkern*d + 2*nkern + 2 */
 MI_GP_API void* mi_gp_stream(const mi_gp_handle* h);    /* the handle's hipStream_t */
+/* Binds the buffers.  Every call ends the handle's resident state -- the factor of mi_gp_factor, U = L^-T and the K^-1 of
+ * mi_gp_lml_grad live in the buffers they were computed in -- whether or not the pointers changed: mi_gp_predict*, mi_gp_predict_cov
+ * and mi_gp_append return -1 until the next mi_gp_factor, mi_gp_alpha and mi_gp_grad_x until the next mi_gp_lml_grad. */
 MI_GP_API int mi_gp_set_data(mi_gp_handle* h, const mi_gp_buffers* buffers);
 
 /* LML(theta) = -1/2 |L^-1 y|^2 - sum log L_ii - n/2 log 2pi with L = chol(K(theta) + gv I + jitter I).
@@ -225,7 +228,7 @@ MI_GP_API int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const double
  *      columns = N > 384 on for problems that run in column mode from the start, options 37 and 45), 2 always
  *   2  super-panel width in 128-column tiles (default 0 = by trailing size, options 4-6)
  *   4-6  trailing sizes (tile columns) above which the super-panel is 16 / 8 / 4 tiles wide (below the last: 2);
- *        defaults: never 16, else 8; with look-ahead active, problems of up to 64 tile columns use at most 4
+ *        defaults: never 16, else 8; with look-ahead active, problems of up to 60 tile columns use at most 4
  *   7  GEMM launches with fewer 128x128 tiles than this run on 64x64 tiles (default 1024)
  *   8  trailing size at or below which look-ahead bulk updates run one workgroup per CU (default: always)
  *   9  128x128-tile GEMM launches with uniform k hand the tiles beyond their last full round of 512 to the 64x64-tile
