@@ -337,7 +337,7 @@ static hipError_t update_bulk(mi_gp_shard* s, int li0, int j, const double* buf,
   p.pl_rows = s->ntr;
   p.pl_tiles = s->table[s->nown].x - s->table[li0].x;
   // beside this rank's own chain only the first split_tiles tiles run one workgroup per CU, the rest two per CU once the
-  // chain is through (the single-GPU driver's split, api_gp.hip cholesky(); same tiles, same kernels)
+  // chain is through (the single-GPU driver's split, gp_sched.hip cholesky(); same tiles, same kernels)
   if (one_per_cu && s->split_tiles > 0 && p.pl_tiles >= s->split_tiles + 1024) {
     p.tile_cnt = s->split_tiles;
     hipError_t e = launch_gemm_f64(p, 0, 0, 1, st);

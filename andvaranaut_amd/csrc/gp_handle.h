@@ -1,0 +1,188 @@
+// Private to the handle-level C-ABI: the GP handle, what an evaluation is made of, and what api_gp.hip and the
+// factorisation scheduler (gp_sched.hip) share.
+#pragma once
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "migp_kernels.h"
+#include "../../include/mi_gp.h"
+
+using namespace migp;
+
+constexpr int SIG_SLOTS = 1024;  // cross-stream edges of one evaluation (a 16384-point factorisation has ~60)
+
+// Per-problem scratch of an evaluation, for k problems (the single evaluation's k = 1, a batch's k = its count); problem p's
+// part of an array starts p per-problem sizes in (scratch_strides()).
+struct Scratch {
+  int k = 0;                    // problems it is sized for (0: none)
+  double* theta_dev = nullptr;  // [k][ntheta]
+  double* dinv_dev = nullptr;   // [k][ntc + 4][MINV_ELEMS] explicit inverses of the diagonal blocks of L (leaf output, strip operand)
+  double* alpha_dev = nullptr;  // [k][np] K^-1 y
+  double* part_dev = nullptr;   // [k][grad_contract_blocks(n)][ntheta]
+  int* info_dev = nullptr;      // [k][4] bad-pivot words
+  double* lr_part_dev = nullptr;    // [k][2 * LML_REDUCE_BLOCKS] slice sums of lml_reduce_kernel
+  unsigned* lr_sync_dev = nullptr;  // [2k]: [0, k) lml_reduce's tickets, [k, 2k) grad_final's (zero between evaluations)
+  double* grad_host = nullptr;  // pinned [k][ntheta]
+  double* out_host = nullptr;   // pinned [k][16] scalar records
+  double* theta_host = nullptr; // pinned [k][ntheta]
+};
+
+struct mi_gp_handle {
+  mi_gp_config cfg;
+  KernSpec spec;
+  int n, np, ntc;       // points, padded points, 128-column tiles
+  int ntheta;
+  int device;
+  hipStream_t stream;    // trailing updates, assembly, reductions
+  hipStream_t pstream;   // look-ahead panel factorisation (higher priority)
+  std::vector<hipEvent_t> ev_pool;  // one event per cross-stream hand-off of an evaluation (never re-recorded inside one
+                                    // evaluation: a captured DAG then holds one node pair per hand-off); Sched::ev_next draws from it
+  // Cross-stream edges as stream memory operations (round 4, option 26): `from` writes the evaluation's epoch into a slot of
+  // sig_dev behind its work (hipStreamWriteValue32), `to` waits for slot >= epoch (hipStreamWaitValue32).  Measured on
+  // MI355X (ping-pong of short kernels over two streams): +4-5 us per edge against +11-12 us with hipEventRecord +
+  // hipStreamWaitEvent.  One slot per edge of an evaluation, never re-used inside it; the epoch grows by one per
+  // factorisation, so a slot's old value never satisfies a new wait.
+  unsigned* sig_dev;                // [SIG_SLOTS]
+  unsigned sig_epoch;
+  bool smo_supported;               // hipDeviceAttributeCanUseStreamWaitValue
+  int poll_limit_log2;              // option 27: an in-kernel poll gives up after 2^this sleeps (default 22: seconds)
+  int test_drop_signal;             // option 28 (tests): the next evaluation leaves one main-stream signal unwritten
+  bool demoted;                     // a poll ran into its limit (or mi_gp_create's probe found kernel dispatch serialised): the edges
+                                    // are events from then on (use_smo = 0) -- mi_gp_get_option(40)
+  int u_early_max_s;                // option 30: block-doubling levels of U = L^-T (node sizes up to this many tiles) that start inside the
+                                    // factorisation's chain-bound tail on the main stream (gradient evaluations; 0: none)
+  int u_early_cols;                 // option 31: ... from this many trailing tile columns on, and at most this many new columns per step
+  int thin_max_wg;                  // option 32: in-panel updates of at most this many 16-row x 128-column slices (k = 128, at most
+                                    // THIN_MAX_COLS tile columns) run on the thin kernel (thin_f64.hip); 0: never
+  int start_on_panel;               // option 45: see enqueue_factor (default 1; scheduling only)
+  int spin_us;                      // option 47: wait_evaluation() spins on the evaluation's sequence word for up to this many us (0: never)
+  double eval_seq;                  // sequence number of the evaluation in flight (published by its last kernel)
+  int spin_backoff;                 // evaluations left that go straight to hipStreamSynchronize (the last spin ran into its budget)
+  unsigned spin_hits;               // spin waits that saw the word (every 256th synchronises the stream all the same)
+  int rl_group;                     // option 38: column mode of a BATCH applies the main stream's k = 128 updates to the far columns in
+                                    // k-segmented launches of this many columns (same bits, the trailing matrices read and written once per group)
+  int rl_cols;                      // option 37: the last rl_cols tile columns are factored COLUMN BY COLUMN (cholesky(): column mode); 0: never
+  int rl_whole;                     // option 46: problems of up to this many tile columns run in column mode from the start (whole_columns())
+  int ext_rows;                     // option 35: a super-panel with at most this many tile rows below it also applies its updates to
+                                    // the NEXT super-panel's first tile column, level by level (chol_panel's nx); 0: never
+  int use_smo;                      // option 26: 0 events, 1 runtime stream memory operations, 2 (default) the panel stream's
+                                    // halves folded into one-lane launches of the library / the end of a leaf
+  // tuning options (mi_gp_set_option), all per handle
+  int tail_small;   // option 9: 128x128-tile launches finish their last partial round on 64x64 tiles (default 1)
+  int chain_prio;   // s_setprio(3) in the GEMM launches of the panel stream (option 16; the leaf and strip kernels always raise it)
+  int lookahead;    // 0 never, 1 by size (default: from LOOKAHEAD_MIN_TILES tile columns on), 2 always
+  int lowocc_thr;   // trailing sizes (tile columns) at or below which bulk updates run one workgroup per CU
+  int w_thr[3];     // trailing sizes (tile columns) above which the super-panel is 16 / 8 / 4 tiles wide
+  int small_below;  // GEMM launches with fewer 128x128 tiles than this run on 64x64 tiles
+  int band_rows;    // band height of the band-column-major tile order of uniform-k trapezoid launches
+  int split_tiles;  // option 18: tiles of a bulk update that run one workgroup per CU beside the chain; the rest two per CU (0: no split)
+  int split_min_rest;  // option 19: ... only when at least this many tiles remain for the second part
+  int single_below;    // option 21: trailing tile columns at or below which a two-stream factorisation continues on one stream (0: never)
+  int merge_min_tiles; // option 20: trailing sizes (tile columns) from which the next super-panel's update rides at the head of the
+                       // trailing update's enumeration instead of in launches of its own (0: never)
+  mi_gp_buffers buf;
+  bool have_data;
+  Scratch one;          // the single evaluation's scratch (k = 1, sized for cap points)
+  double* gxs_dev;      // [grad_x_splits][n][d] partial dLML/dX (allocated on first mi_gp_grad_x)
+  // profiling
+  int prof_level;
+  hipEvent_t ev[8];
+  std::vector<hipEvent_t> gemm_ev;  // pairs
+  std::vector<char> gemm_ev_big;    // per pair: 1 if the 128x128-tile kernel ran
+  std::vector<double> gemm_ev_flops;
+  size_t gemm_ev_used;
+  double gemm_flops_acc;
+  double t_assemble_ms, t_chol_ms, t_reduce_ms, t_gemm_ms, t_total_ms, gemm_flops, n_gemm;
+  double t_trtri_ms, t_lauum_ms, t_contract_ms;
+  double t_enqueue_ms;  // host time of enqueueing the last single evaluation (always measured: two clock reads)
+  double t_gemm_big_ms, gemm_big_flops, n_gemm_big;  // the 128x128-tile kernel only
+  // batched evaluation (mi_gp_set_batch / mi_gp_lml_batch / mi_gp_lml_grad_batch): the caller's K / Z / W and the batch's
+  // scratch (k = bbuf.count or more, sized for n points); batch_eval() hands both to the enqueue code
+  mi_gp_batch_buffers bbuf;
+  Scratch batch;
+  int b_cond_k;            // problems whose conditional factors (L_p, beta_p, leaf inverses) the last batch call left in the batch
+                           // buffers: mi_gp_factor_batch sets it, every other batch call, mi_gp_set_batch / _set_data / _set_diag,
+                           // mi_gp_append and a single evaluation into the batch's K (factor_internal) clear it (0)
+  bool factored;
+  bool have_u;             // Z_dev holds U = L^-T and alpha_dev = K^-1 y of the last mi_gp_factor (mi_gp_predict_grad)
+  bool have_kinv;          // W_dev holds K^-1 (lower) and alpha_dev = K^-1 y of the last mi_gp_lml_grad
+  const double* diag_dev;  // optional per-point diagonal added at assembly (mi_gp_set_diag)
+  int cap;                 // points the n-dependent scratch above is sized for (mi_gp_reserve; n until it is called)
+  size_t gxs_elems;        // doubles gxs_dev holds
+  double* app_stats_dev;   // [4] mi_gp_append's scalar increments and bad-pivot word
+  char err[256];
+};
+
+inline int hfail(mi_gp_handle* h, hipError_t e, const char* where) {
+  snprintf(h->err, sizeof(h->err), "%s: %s", where, hipGetErrorString(e));
+  return -2;
+}
+#define HCK(call, where)                          \
+  do {                                            \
+    hipError_t e__ = (call);                      \
+    if (e__ != hipSuccess) return hfail(h, e__, where); \
+  } while (0)
+
+// What the enqueue code evaluates: the single problem (one_eval) or a batch of problems (batch_eval) -- its K / Z / W, its
+// scratch and its per-problem strides.  X, y and lda are the handle's (h->buf) either way.  Built by each call, never stored:
+// the handle itself always describes the single problem.
+struct Eval {
+  double *K, *Z, *W;
+  const Scratch& s;
+  Batch bt;         // nb = 1 and every stride 0 for the single problem
+  bool batched;
+  int prof;         // profiling level (a batch: 0)
+  const Batch* lb() const { return batched ? &bt : nullptr; }  // what the launchers get (nullptr: one problem)
+};
+
+// A cross-stream edge of one evaluation: a slot of sig_dev that is raised to the evaluation's epoch (by a runtime
+// hipStreamWriteValue32 or by a kernel), an event of ev_pool, or nothing.  Only the edge functions of gp_sched.hip tell the
+// forms apart.
+struct Edge {
+  int slot = -1;
+  hipEvent_t ev = nullptr;
+  bool armed() const { return slot >= 0 || ev != nullptr; }
+};
+
+// The scheduling state of ONE evaluation: made by run_evaluation() on its stack, passed down by reference, gone with it.
+struct Sched {
+  // the two-streams decision (plan_streams(), once per evaluation)
+  bool la_single = false;  // the size alone asks for two streams (the narrow super-panels go with it)
+  bool two = false;        // this evaluation runs on two streams
+  bool asm_on_panel = false;  // its set_yrows + assembly were queued on the PANEL stream (two streams, option 45: the first leaf
+                              // follows them in stream order, no cross-stream edge in front of the chain)
+  int sig_next = 0;        // next free slot of sig_dev / event of ev_pool: the ORDER in which edges take them is part of the
+  size_t ev_next = 0;      // schedule (one slot or event per edge, never re-used inside the evaluation)
+  // Edges armed for the leaf of one tile column.  Armed by cholesky_enqueue (the step that queues the panel), consumed -- and
+  // disarmed -- by chol_panel at that column's leaf (take_armed(), the only reader).
+  struct Armed { int col = -1; Edge edge; };
+  Armed wait;   // behind the leaf + strip of column wait.col the panel stream waits for the main stream's (a2) update of the
+                // columns wait.col + 1 .. (option 26 = 2: the leaf itself polls before it ends)
+  Armed wait2;  // the leaf of column wait2.col ends only once this slot is written (everything queued on the main stream before
+                // the super-panel's chain: the first in-panel update behind that leaf writes the next super-panel's first column)
+  Armed done;   // the update behind the strip of column done.col raises this slot ("super-panel done")
+  // U = L^-T inside the factorisation's tail (options 30 / 31)
+  bool u_early = false;                      // this evaluation takes part (set by enqueue_all)
+  int u_leaf_done = 0, u_node_done[12] = {}; // tile columns whose leaf block of U is done / full nodes done per level
+};
+
+// One operand of gemm_call: pointer, leading dimension, stride between the nodes of a node-batched launch, stride between the
+// problems of a batched evaluation
+template <class T>
+struct Operand {
+  T* p;
+  long ld;
+  long node = 0;
+  long z = 0;
+};
+using In = Operand<const double>;
+using Out = Operand<double>;
+
+// gp_sched.hip
+int run_evaluation(mi_gp_handle* h, const Eval& E, int what);
+hipError_t inverse_transpose(mi_gp_handle* h, const Eval& E);  // all of U = L^-T behind a factorisation that started none of it
+hipError_t gemm_call(mi_gp_handle* h, const Eval& E, int ak, int bk, In A, In B, Out C, int mt, int nt, int k, int tri, int kmode,
+                     double alpha, double beta, int batch, bool single_form = false);

@@ -919,7 +919,7 @@ __global__ __launch_bounds__(512, 1) void potrf_leaf128_kernel(double* __restric
   __builtin_amdgcn_s_setprio(3);  // the leaf is the panel chain: win the issue arbitration against bulk GEMM waves on its CU
   const long z = blockIdx.x;  // batched evaluation: one workgroup per problem
   // start_wr (optional): "everything queued on this stream before me is done, and I have my CU" -- the main stream's next
-  // update waits for it, so that it does not fill the chip in front of this workgroup (column mode, api_gp.hip)
+  // update waits for it, so that it does not fill the chip in front of this workgroup (column mode, gp_sched.hip)
   if (start_wr != nullptr && z == 0 && threadIdx.x == 0) __hip_atomic_store(start_wr, wait_val, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   potrf_leaf128_body(Ablk + z * sA, lda, minv + z * sminv, col0, info + z * sinfo, smem, yrow ? yrow + z * sA : nullptr);
   if (wait_ptr != nullptr && threadIdx.x == 0) poll_signal(wait_ptr, wait_val, info + z * sinfo, poll_log2);

@@ -593,7 +593,7 @@ class GPMCMC(ConsumersMixin):
                     # the caller's own handle gets its previous settings back afterwards (library defaults: look-ahead by
                     # size = 1, super-panel width by size = 0)
                     before = (h.get_option(2, 0), h.get_option(0, 1))
-                    if 20 <= ntc <= 60:  # (api_gp.hip NARROW_PANELS_MAX_TILES: above it both schedules use 8-tile super-panels;
+                    if 20 <= ntc <= 60:  # (gp_sched.hip NARROW_PANELS_MAX_TILES: above it both schedules use 8-tile super-panels;
                         h.set_option(2, 4)  # up to 31 tile columns the whole problem runs in column mode: no panels at all)
                     h.set_option(0, 0)
                 try:

@@ -20,7 +20,7 @@ KERNS, OPS = ["Matern52"], []
 D = 4
 
 # ------------------------------------------------------------------------------------------------- the schedule, as a model
-# Thresholds of csrc/api_gp.hip that are NOT options (include/mi_gp.h states them in the text of options 0, 4-6, 30, 35 and 37):
+# Thresholds of csrc/gp_sched.hip that are NOT options (include/mi_gp.h states them in the text of options 0, 4-6, 30, 35 and 37):
 LOOKAHEAD_MIN_TILES = 20      # two streams with look-ahead from this many tile columns on (option 0 = 1)
 COLUMN_MODE_MIN_TILES = 4     # ... and from this many on when the whole problem runs in column mode
 NARROW_PANELS_MAX_TILES = 60  # with look-ahead active, problems of up to this many tile columns use super-panels of at most 4 tiles
@@ -32,7 +32,7 @@ DEFAULT_OPTIONS = {0: 1, 2: 0, 4: 1 << 20, 5: 0, 6: 0, 20: 72, 21: 8, 30: 16, 35
 
 
 def schedule(ntc, o):
-    """What cholesky_enqueue (csrc/api_gp.hip) does with one evaluation of `ntc` tile columns under the option values `o`:
+    """What cholesky_enqueue (csrc/gp_sched.hip) does with one evaluation of `ntc` tile columns under the option values `o`:
     {"two": two streams, "panels": [(first tile column, width, extended, its update rides in the bulk update)], "tail": first tile
     column of column mode (None: no column mode), "early": option 30's early start of U = L^-T in a gradient evaluation}."""
     whole = o[37] > 0 and (ntc <= o[37] or ntc <= o[46])

@@ -87,7 +87,7 @@ def test_predict_at_n8192_through_both_routes_matches_the_oracle():
 
 
 def test_ragged_large_size_through_the_split_and_merged_launches():
-    """The round-4 driver paths that only large problems reach (api_gp.hip cholesky(): merged head from 72 trailing tile
+    """The round-4 driver paths that only large problems reach (gp_sched.hip cholesky(): merged head from 72 trailing tile
     columns, split bulk update, single-stream tail) at a size that is NOT a multiple of anything: N = 10300 (81 tile columns,
     ragged last super-panel).  LML against the oracle at the north star's 1e-10, and the scheduling-only options
     (include/mi_gp.h: 18, 19, 21, 24, 26 bit-identical; 20 same k order per tile) must not change a bit.  gpmcmc.py:313."""

@@ -1,6 +1,6 @@
 """Every entry point of one handle against the row-blocked oracle (oracle.gp_oracle.lml_all_blocked) at 34-130 tile columns,
 where the factorisation's schedule changes with the size (ntc = ceil(N / 128) tile columns; cholesky_enqueue in
-andvaranaut_amd/csrc/api_gp.hip).  The bit-identity tests compare one schedule with another: an error both share passes them.
+andvaranaut_amd/csrc/gp_sched.hip).  The bit-identity tests compare one schedule with another: an error both share passes them.
 
 Which shape rules each default size reaches (single evaluation, default options; the factor has ntr = ntc + 1 tile rows):
 
