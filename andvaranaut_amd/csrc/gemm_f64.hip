@@ -7,18 +7,23 @@
 // Lane maps of the 16x16x4 form (one f64 of A and of B per lane, 4 f64 of C/D per lane):
 //   A[i = l&15][k = l>>4]   B[k = l>>4][j = l&15]   D[row = (l>>4) + 4r][col = l&15], r = 0..3
 //
-// Two kernels, one design:
-//   gemm_f64_kernel_b : 128x128 output tile per 256-thread workgroup (4 waves as 2x2, 64x64 per wave = 4x4 MFMA tiles =
-//                       64 accumulator doubles per lane).  NT form (both operands row-major, the Cholesky's bulk updates):
-//                       K in chunks of 8 filled global -> LDS by LDS-DMA (global_load_lds, 16 bytes per lane, no VGPR
-//                       staging) into four LDS stages of a row-major, XOR-swizzled image (64 KiB), requested three
-//                       chunks ahead so that one stays in flight across every chunk barrier.  Forms with a k-major operand: K in chunks of 16 through a double-
-//                       buffered k-major LDS image ([k][x], leading dimension 144 doubles so both halves of a ds_read_b64
-//                       wave access hit disjoint banks, 72 KiB), global -> register prefetch two chunks ahead, registers ->
-//                       LDS one chunk ahead.  Both: two workgroups per CU, MFMA operand fragments double-buffered in
-//                       registers one k4-step ahead, sched_group_barrier spreads the memory instructions between the MFMAs.
-//   gemm_f64_kernel_s : the same schedule on 64x64 tiles for launches with too few 128x128 tiles to fill the chip; its
-//                       row-major operands are fetched as whole 128-byte row segments and stored XOR-swizzled (round 4).
+// Two kernels, one design (256 threads = 4 waves as 2x2; MFMA operand fragments double-buffered in registers one k4-step
+// ahead; branch-free chunk bodies in which sched_group_barrier spreads the memory instructions between the MFMAs; two
+// workgroups per CU).  What they share is written once, ahead of them: which k range and batch member a workgroup takes
+// (k_range, batch_ptrs), the register-staged operand path (chunk_offsets / chunk_load / chunk_store over
+// StageB / StageS) and the k-segment step (kseg_mask, kseg_jump); the host finds every instantiation in GEMM_KERNELS.
+//   gemm_f64_kernel_b : 128x128 output tile per workgroup (64x64 per wave = 4x4 MFMA tiles = 64 accumulator doubles per
+//                       lane), with two operand paths.
+//                       NT form (both operands row-major, the Cholesky's bulk updates): K in chunks of 8 filled global ->
+//                       LDS by LDS-DMA (global_load_lds, 16 bytes per lane, no VGPR staging) into four LDS stages of a
+//                       row-major, XOR-swizzled image (64 KiB), requested three chunks ahead so that one stays in flight
+//                       across every chunk barrier.
+//                       Forms with a k-major operand: K in chunks of 16 through a double-buffered k-major LDS image
+//                       ([k][x], leading dimension 144 doubles so both halves of a ds_read_b64 wave access hit disjoint
+//                       banks, 72 KiB), global -> register prefetch two chunks ahead, registers -> LDS one chunk ahead.
+//   gemm_f64_kernel_s : the register-staged schedule on 64x64 tiles (three LDS buffers, 60 KiB) for launches with too few
+//                       128x128 tiles to fill the chip; its row-major operands are fetched as whole 128-byte row segments
+//                       and stored XOR-swizzled (round 4).
 //
 // They serve: K3 Cholesky trailing / panel updates (NT, lower), K7 triangular
 // inverse levels (NN with triangular k-ranges) and L^-T L^-1 (TN), K8 predict triangular-solve updates (NT).
@@ -125,46 +130,110 @@ __device__ __forceinline__ void list_tile(const GemmParams& p, int idx, int& ra,
 }
 
 // ---------------------------------------------------------------------------------------------
+// What both kernels share of "which k range, which batch member".  The block -> tile decode (XCD-aware map, the choice
+// between the fc / banded / plain orders, the kmode 2 / 4 reversal) stands in each kernel, each copy naming the other: as
+// shared functions these moved the scalar code and the scalar register numbering of gemm_f64_kernel_s, whatever the spelling
+// (profiles/NOTES_gemm_refactor.md).
+
+// kmode -> the k range [beg, end) of the tile at rows i0, columns j0 (T: tile edge): 0 all of k; 1 / 3 from the tile's own
+// column / row on (lower-triangular B / A); 2 / 4 up to the end of the tile's own row / column (lower-triangular A / B^T)
+struct KRange { int end, beg; };  // (in this order the kernels' scalar code is the one they had with two locals)
+template <int T>
+__device__ __forceinline__ KRange k_range(const GemmParams& p, int i0, int j0) {
+  KRange r = {p.k, 0};
+  if (p.kmode == 1) r.beg = j0;
+  else if (p.kmode == 2) r.end = i0 + T;
+  else if (p.kmode == 3) r.beg = i0;
+  else if (p.kmode == 4) r.end = j0 + T;
+  return r;
+}
+
+// blockIdx.z = z1 + batch1 * z2 (two-level batch: nodes of a triangular-inverse level x problems of a batched evaluation)
+struct BatchPtrs { const double* A; const double* B; double* C; };
+__device__ __forceinline__ BatchPtrs batch_ptrs(const GemmParams& p) {
+  const long z1 = p.batch1 > 0 ? (long)(blockIdx.z % p.batch1) : (long)blockIdx.z, z2 = p.batch1 > 0 ? (long)(blockIdx.z / p.batch1) : 0;
+  return {p.A + z1 * p.strideA + z2 * p.strideA2, p.B + z1 * p.strideB + z2 * p.strideB2, p.C + z1 * p.strideC + z2 * p.strideC2};
+}
+
+// A run of sched_group_barrier: (instruction class, count) pairs in issue order -- how a chunk body spreads its memory
+// instructions between its MFMAs
+constexpr int SG_MFMA = 0x008, SG_VMEM_READ = 0x020, SG_DS_READ = 0x100, SG_DS_WRITE = 0x200;
+template <int MASK, int N, int... REST>
+__device__ __forceinline__ void sched_groups() {
+  __builtin_amdgcn_sched_group_barrier(MASK, N, 0);
+  if constexpr (sizeof...(REST) > 0) sched_groups<REST...>();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Register-staged operand path of both kernels: a chunk of 16 k of one operand goes global -> registers (double2 pieces,
+// 256 threads) -> a k-major LDS image [k][x] of leading dimension S::LD.  S names what differs between the kernels:
+//   S::T    tile edge: x extent of the chunk (a k-major operand has T / 2 threads per k row, 512 / T k rows per piece)
+//   S::LD   leading dimension of the LDS image in doubles
+//   S::SWZ  row-major operands: fetch whole 128-byte row segments and XOR-swizzle the image's columns (below)
+struct StageB { static constexpr int T = TILE, LD = LDS_LD; static constexpr bool SWZ = false; };
+// LD 80 = 64 + 16: odd k rows land 16 bank-pairs away from even ones
+struct StageS { static constexpr int T = 64, LD = 80; static constexpr bool SWZ = true; };
+
+template <class S, bool KMAJOR>
+__device__ __forceinline__ void chunk_offsets(long ld, int tid, unsigned& goff, unsigned& loff, long& gstride) {
+  if (KMAJOR) {
+    constexpr int XT = S::T / 2, KR = 256 / XT;  // threads per k row, k rows per piece: k = KR q + tid / XT
+    const int k = tid / XT, xc = tid % XT;
+    goff = (unsigned)((k * ld + 2 * xc) * 8);
+    loff = (unsigned)((k * S::LD + 2 * xc) * 8);
+    gstride = KR * ld * 8;
+  } else if (S::SWZ) {
+    // Eight consecutive lanes fetch ONE row's 128-byte chunk segment (a whole cache line per row, 8 rows per wave
+    // instruction) instead of sixteen lanes fetching 16 bytes of sixteen different rows.  The k-major LDS image is then
+    // written with the column XOR-swizzled by the k pair, col = x ^ (k & 14): a wave's 16-lane write groups (8 k pairs x 2
+    // rows) hit 16 distinct bank pairs, and a fragment read (16 consecutive x at one k, XORed with a constant below 16)
+    // stays a permutation of its aligned 16-column block, so the read side keeps its conflict-free pattern.
+    const int kc = tid & 7, row = tid >> 3;  // x = 32q + (t>>3), k = 2 (t&7)
+    goff = (unsigned)((row * ld + 2 * kc) * 8);
+    loff = (unsigned)(((2 * kc) * S::LD + (row ^ (2 * kc))) * 8);
+    gstride = 32 * ld * 8;
+  } else {
+    const int xl = tid & 15, kc = (tid >> 4) & 7, xh = tid >> 7;  // x = 32q + 16*(t>>7) + (t&15)
+    goff = (unsigned)(((xh * 16 + xl) * ld + 2 * kc) * 8);
+    loff = (unsigned)(((2 * kc) * S::LD + xh * 16 + xl) * 8);
+    gstride = 32 * ld * 8;
+  }
+}
+template <int NQ>
+__device__ __forceinline__ void chunk_load(const char* __restrict__ base, unsigned goff, long gstride, double2_t (&r)[NQ]) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) r[q] = *reinterpret_cast<const double2_t*>(base + q * gstride + goff);
+}
+template <class S, bool KMAJOR, int NQ>
+__device__ __forceinline__ void chunk_store(char* __restrict__ lds, unsigned loff, const double2_t (&r)[NQ]) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    if (KMAJOR) {
+      *reinterpret_cast<double2_t*>(lds + loff + q * (512 / S::T * S::LD * 8)) = r[q];
+    } else {
+      *reinterpret_cast<double*>(lds + loff + q * (32 * 8)) = r[q].x;
+      *reinterpret_cast<double*>(lds + loff + q * (32 * 8) + S::LD * 8) = r[q].y;
+    }
+  }
+}
+
+// k-segmented operands (GemmParams::kseg; row-major operands only): the byte step INTO chunk n of BK k is kseg_jump, to the
+// next segment's base, when n & kseg_mask is 0 (n a multiple of kseg / BK), else the step inside a segment
+template <int BK>
+__device__ __forceinline__ int kseg_mask(const GemmParams& p) { return p.kseg > 0 ? p.kseg / BK - 1 : 0x7fffffff; }
+template <int BK>
+__device__ __forceinline__ long kseg_jump(const GemmParams& p) { return (p.kseg_stride - (long)(p.kseg - BK)) * 8; }
+
+// ---------------------------------------------------------------------------------------------
 // 128x128 tiles: 256-thread workgroups (4 waves as 2x2, 64x64 per wave = 4x4 MFMA tiles, 64 accumulator
-// doubles per lane), K chunks of 16, 72 KiB of LDS -> TWO workgroups per CU whose barriers, prologues
-// and C read-modify-write epilogues overlap each other's MFMA loops.
+// doubles per lane).  Register path (a k-major operand): K chunks of 16 (BKB), 72 KiB of LDS; LDS-DMA path (NT form): K
+// chunks of 8 (BKD), four stages, 64 KiB.  Either way TWO workgroups per CU, whose barriers, prologues and C
+// read-modify-write epilogues overlap each other's MFMA loops.
 namespace vb {
 constexpr int BKB = 16;
 constexpr int OPER_B = BKB * LDS_LD;
 constexpr int NT_B = 256;
 constexpr int NQB = TILE * BKB / 2 / NT_B;  // 4
-
-template <bool KMAJOR>
-__device__ __forceinline__ void chunk_offsets(long ld, int tid, unsigned& goff, unsigned& loff, long& gstride) {
-  if (KMAJOR) {
-    const int k = tid >> 6, xc = tid & 63;  // k = 4q + (t>>6)
-    goff = (unsigned)((k * ld + 2 * xc) * 8);
-    loff = (unsigned)((k * LDS_LD + 2 * xc) * 8);
-    gstride = 4 * ld * 8;
-  } else {
-    const int xl = tid & 15, kc = (tid >> 4) & 7, xh = tid >> 7;  // x = 32q + 16*(t>>7) + (t&15)
-    goff = (unsigned)(((xh * 16 + xl) * ld + 2 * kc) * 8);
-    loff = (unsigned)(((2 * kc) * LDS_LD + xh * 16 + xl) * 8);
-    gstride = 32 * ld * 8;
-  }
-}
-__device__ __forceinline__ void chunk_load(const char* __restrict__ base, unsigned goff, long gstride,
-                                           double2_t (&r)[NQB]) {
-#pragma unroll
-  for (int q = 0; q < NQB; ++q) r[q] = *reinterpret_cast<const double2_t*>(base + q * gstride + goff);
-}
-template <bool KMAJOR>
-__device__ __forceinline__ void chunk_store(char* __restrict__ lds, unsigned loff, const double2_t (&r)[NQB]) {
-#pragma unroll
-  for (int q = 0; q < NQB; ++q) {
-    if (KMAJOR) {
-      *reinterpret_cast<double2_t*>(lds + loff + q * (4 * LDS_LD * 8)) = r[q];
-    } else {
-      *reinterpret_cast<double*>(lds + loff + q * (32 * 8)) = r[q].x;
-      *reinterpret_cast<double*>(lds + loff + q * (32 * 8) + LDS_LD * 8) = r[q].y;
-    }
-  }
-}
 
 // NT form: LDS-DMA operand path.  A stage holds one chunk of BKD = 8 k of both operands, each a row-major image of 128 rows x
 // 64 bytes in 16-byte (row, k pair) units, unit (x, kp) at byte 64 x + 16 (kp ^ ((x >> 2) & 3)).  An LDS-DMA writes 64 lanes x
@@ -198,9 +267,7 @@ __device__ __forceinline__ void dma_chunk(const char* __restrict__ g, unsigned g
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   static_assert(N == 4 || N == 16 || N == 20, "vmcnt");
-  if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 }  // namespace vb
 
@@ -215,6 +282,9 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
   const int wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
 
+  // XCD-aware block -> tile map for uniform-k launches (the same map stands in gemm_f64_kernel_s: keep the two in step):
+  // workgroup b runs on XCD b % 8, and each XCD takes a CONTIGUOUS range of the enumeration, so the tiles of one tile row
+  // (consecutive indices: they share their A rows) meet in one L2 instead of eight.
   const int nblk = gridDim.x;
   int idx = blockIdx.x;
   if (p.kmode == 0) {
@@ -228,6 +298,8 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
     bool diag;
     list_tile(p, idx, ti, tj, rc, cc, diag);
   } else {
+    // The same choice and reversal stand in gemm_f64_kernel_s (its tail form): keep the two in step.  Here the banded order
+    // is taken only under the XCD-aware map (kmode 0); there kmode is always 0.
     // (full rectangles measured neutral: 8192^3 75.2 vs 75.7 TFLOP/s -- the row-major order stays for them)
     if (p.fc > 0) tile_from_index_fc(p.mt, p.nt, p.fc, p.band, idx, ti, tj);
     else if (p.band > 0 && p.tri && p.kmode == 0) tile_from_index_banded(p, idx, p.band, ti, tj);
@@ -239,17 +311,13 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
     cc = tj;
   }
   const int i0 = ti * TILE, j0 = tj * TILE;
-  int kbeg = 0, kend = p.k;
-  if (p.kmode == 1) kbeg = j0;
-  else if (p.kmode == 2) kend = i0 + TILE;
-  else if (p.kmode == 3) kbeg = i0;
-  else if (p.kmode == 4) kend = j0 + TILE;
+  const KRange kr = k_range<TILE>(p, i0, j0);
+  const int kbeg = kr.beg, kend = kr.end;
 
-  // blockIdx.z = z1 + batch1 * z2 (two-level batch: nodes of a triangular-inverse level x problems of a batched evaluation)
-  const long z1 = p.batch1 > 0 ? (long)(blockIdx.z % p.batch1) : (long)blockIdx.z, z2 = p.batch1 > 0 ? (long)(blockIdx.z / p.batch1) : 0;
-  const double* A = p.A + z1 * p.strideA + z2 * p.strideA2;
-  const double* B = p.B + z1 * p.strideB + z2 * p.strideB2;
-  double* C = p.C + z1 * p.strideC + z2 * p.strideC2;
+  const BatchPtrs bp = batch_ptrs(p);
+  const double* A = bp.A;
+  const double* B = bp.B;
+  double* C = bp.C;
 
   double4_t acc[4][4];
 #pragma unroll
@@ -279,16 +347,17 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
     using vb::BKD; using vb::STG_OPER; using vb::STG_B;
     char* lds = reinterpret_cast<char*>(smem);
     const int wv = __builtin_amdgcn_readfirstlane(wave);
-    const int nchunk = (kend - kbeg) / BKD;  // a multiple of 4 and >= 4 (k and the triangular k ranges are multiples of 32)
+    // A multiple of 4 and >= 4, which the three-chunk prologue and the four peeled last chunks rely on: k and the triangular k
+    // ranges are multiples of 32 (gemm_args_error in api_blocks.hip; kseg a multiple of 128 in launch_gemm_f64).
+    const int nchunk = (kend - kbeg) / BKD;
     unsigned gA, gB;
     long sA, sB;
     vb::dma_offsets(p.lda, tid, gA, sA);
     vb::dma_offsets(p.ldb, tid, gB, sB);
     const char* Ag = reinterpret_cast<const char*>(A + (long)i0 * p.lda + kbeg);
     const char* Bg = reinterpret_cast<const char*>(B + (long)j0 * p.ldb + kbeg);
-    // k-segmented operands: the step INTO chunk n is a jump to the next segment's base when n is a multiple of kseg / BKD
-    const int segmask = p.kseg > 0 ? p.kseg / BKD - 1 : 0x7fffffff;
-    const long segjump = (p.kseg_stride - (long)(p.kseg - BKD)) * 8;
+    const int segmask = kseg_mask<BKD>(p);
+    const long segjump = kseg_jump<BKD>(p);
     auto advance = [&](int next_chunk) {
       const long d = (next_chunk & segmask) == 0 ? segjump : (long)BKD * 8;
       Ag += d;
@@ -345,26 +414,17 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
         if (kk == 0 && mode <= 1) {
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            sched_groups<SG_MFMA, 1,  SG_VMEM_READ, 1,  SG_MFMA, 1,  SG_DS_READ, 2,  SG_MFMA, 2>();
           }
         } else if (mode == 1 || (kk == 0 && mode == 3)) {
 #pragma unroll
           for (int g = 0; g < 8; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            sched_groups<SG_MFMA, 1,  SG_VMEM_READ, 2,  SG_MFMA, 1,  SG_DS_READ, 1>();
           }
         } else {
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            sched_groups<SG_MFMA, 2,  SG_DS_READ, 2,  SG_MFMA, 2>();
           }
         }
       }
@@ -389,35 +449,35 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
     chunk_body(c + 2, std::integral_constant<int, 2>(), std::integral_constant<int, 3>());
     chunk_body(c + 3, std::integral_constant<int, 3>(), std::integral_constant<int, 4>());
   } else {
+    // Even and >= 2: k and the triangular k ranges are multiples of 32 (gemm_args_error in api_blocks.hip refuses other k; the
+    // library's own launches pass multiples of 128), which the prologue and the two peeled last chunks below rely on.  No
+    // k-segments here: launch_gemm_f64 refuses kseg with a k-major operand.
     const int nchunk = (kend - kbeg) / BKB;
     unsigned gA, lA, gB, lB;
     long sA, sB;
-    vb::chunk_offsets<A_KMAJOR>(p.lda, tid, gA, lA, sA);
-    vb::chunk_offsets<B_KMAJOR>(p.ldb, tid, gB, lB, sB);
+    chunk_offsets<StageB, A_KMAJOR>(p.lda, tid, gA, lA, sA);
+    chunk_offsets<StageB, B_KMAJOR>(p.ldb, tid, gB, lB, sB);
     const char* Ag = reinterpret_cast<const char*>(A_KMAJOR ? A + (long)kbeg * p.lda + i0 : A + (long)i0 * p.lda + kbeg);
     const char* Bg = reinterpret_cast<const char*>(B_KMAJOR ? B + (long)kbeg * p.ldb + j0 : B + (long)j0 * p.ldb + kbeg);
     const long stepA = (A_KMAJOR ? (long)BKB * p.lda : (long)BKB) * 8;
     const long stepB = (B_KMAJOR ? (long)BKB * p.ldb : (long)BKB) * 8;
-    // k-segmented operands: the step INTO chunk n is a jump to the next segment's base when n is a multiple of kseg / BKB
-    const int segmask = p.kseg > 0 ? p.kseg / BKB - 1 : 0x7fffffff;
-    const long segjump = (p.kseg_stride - (long)(p.kseg - BKB)) * 8;
     char* Asb = reinterpret_cast<char*>(As);
     char* Bsb = reinterpret_cast<char*>(Bs);
     // Global -> register prefetch runs TWO chunks ahead (register set c & 1 holds chunk c until it is written to
     // LDS buffer c & 1 during chunk c - 1): ~7k cycles of latency tolerance instead of ~3k, enough for an
     // HBM / MALL miss under load while two workgroups share the CU.
     double2_t ra[2][NQB], rb[2][NQB];
-    if (nchunk > 0) {
-      vb::chunk_load(Ag, gA, sA, ra[0]);
-      vb::chunk_load(Bg, gB, sB, rb[0]);
+    if (nchunk > 0) {  // (always: see nchunk.  This guard and the two below stay because the k loop's registers move without them.)
+      chunk_load(Ag, gA, sA, ra[0]);
+      chunk_load(Bg, gB, sB, rb[0]);
       if (nchunk > 1) {
         Ag += stepA;
         Bg += stepB;
-        vb::chunk_load(Ag, gA, sA, ra[1]);
-        vb::chunk_load(Bg, gB, sB, rb[1]);
+        chunk_load(Ag, gA, sA, ra[1]);
+        chunk_load(Bg, gB, sB, rb[1]);
       }
-      vb::chunk_store<A_KMAJOR>(Asb, lA, ra[0]);
-      vb::chunk_store<B_KMAJOR>(Bsb, lB, rb[0]);
+      chunk_store<StageB, A_KMAJOR>(Asb, lA, ra[0]);
+      chunk_store<StageB, B_KMAJOR>(Bsb, lB, rb[0]);
     }
     __syncthreads();
 
@@ -447,17 +507,16 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
       constexpr int lastc = decltype(LASTC)::value;  // 0: inside the loop; 1 / 2: second-to-last / last chunk
       constexpr int boff = s * OPER_B;
       const bool adv = (c + 2 < nchunk);
-      const bool seg = ((c + 2) & segmask) == 0;
-      Ag += adv ? (seg ? segjump : stepA) : 0;
-      Bg += adv ? (seg ? segjump : stepB) : 0;
+      Ag += adv ? stepA : 0;
+      Bg += adv ? stepB : 0;
   #pragma unroll
       for (int kk = 0; kk < BKB / 4; ++kk) {
         const int cur = kk & 1;
         __builtin_amdgcn_sched_barrier(0);
         if (kk == 0) {
           if (lastc == 0) {
-            vb::chunk_load(Ag, gA, sA, ra[s]);
-            vb::chunk_load(Bg, gB, sB, rb[s]);
+            chunk_load(Ag, gA, sA, ra[s]);
+            chunk_load(Bg, gB, sB, rb[s]);
           } else {
             load_group(lastc - 1, lastc - 1);
           }
@@ -470,33 +529,25 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
             acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[cur][a], bf[cur][b], acc[a][b], 0, 0, 0);
         if (kk == BKB / 4 - 1) {
           constexpr int noff = (boff ^ OPER_B) * 8;
-          vb::chunk_store<A_KMAJOR>(Asb + noff, lA, ra[s ^ 1]);
-          vb::chunk_store<B_KMAJOR>(Bsb + noff, lB, rb[s ^ 1]);
+          chunk_store<StageB, A_KMAJOR>(Asb + noff, lA, ra[s ^ 1]);
+          chunk_store<StageB, B_KMAJOR>(Bsb + noff, lB, rb[s ^ 1]);
         }
         if (kk == 0) {
   #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            sched_groups<SG_MFMA, 1,  SG_VMEM_READ, 1,  SG_MFMA, 1,  SG_VMEM_READ, 1,  SG_MFMA, 1,  SG_DS_READ, 1,  SG_MFMA, 1>();
           }
         } else if (kk + 1 < BKB / 4) {
   #pragma unroll
           for (int g = 0; g < 4; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            sched_groups<SG_MFMA, 3,  SG_DS_READ, 1,  SG_MFMA, 1>();
           }
         } else {
           constexpr int nw = (A_KMAJOR ? NQB : 2 * NQB) + (B_KMAJOR ? NQB : 2 * NQB);  // ds_write instructions
   #pragma unroll
           for (int g = 0; g < 16; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if (g < nw) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+            sched_groups<SG_MFMA, 1>();
+            if (g < nw) sched_groups<SG_DS_WRITE, 1>();
           }
         }
       }
@@ -505,7 +556,7 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
       load_frags(0, boff ^ OPER_B, 0);
     };
     int c = 0;
-    for (; c + 2 < nchunk; c += 2) {  // k is a multiple of 128, so nchunk is even and >= 8
+    for (; c + 2 < nchunk; c += 2) {
       chunk_body(c, std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
       chunk_body(c + 1, std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
     }
@@ -540,61 +591,13 @@ __global__ __launch_bounds__(vb::NT_B, 2) void gemm_f64_kernel_b(GemmParams p) {
 // few hundred tiles, which sit on the factorisation's critical path): 4x the workgroups, 1/4 of the
 // per-workgroup latency.  GemmParams.mt / nt are reinterpreted in 64-row tiles by the launcher.
 namespace vs {
-constexpr int TS = 64;
+constexpr int TS = StageS::T;
 constexpr int BKS = 16;
-constexpr int LDS_S = 80;  // 64 + 16: odd k rows land 16 bank-pairs away from even ones
+constexpr int LDS_S = StageS::LD;
 constexpr int OPER_S = BKS * LDS_S;
 constexpr int NQS = TS * BKS / 2 / 256;  // 2
 constexpr int NBUF = 3;                  // LDS buffers per operand (see the pipeline note in the kernel)
-#ifndef MIGP_SWZ_S
-#define MIGP_SWZ_S 1
-#endif
-constexpr bool SWZ = MIGP_SWZ_S != 0;    // coalesced row-major operand loads + XOR-swizzled LDS image (chunk_offsets)
-#ifndef MIGP_XCD_MAP_S
-#define MIGP_XCD_MAP_S 1
-#endif
 
-template <bool KMAJOR>
-__device__ __forceinline__ void chunk_offsets(long ld, int tid, unsigned& goff, unsigned& loff, long& gstride) {
-  if (KMAJOR) {
-    const int k = tid >> 5, xc = tid & 31;  // k = 8q + (t>>5)
-    goff = (unsigned)((k * ld + 2 * xc) * 8);
-    loff = (unsigned)((k * LDS_S + 2 * xc) * 8);
-    gstride = 8 * ld * 8;
-  } else if (SWZ) {
-    // Eight consecutive lanes fetch ONE row's 128-byte chunk segment (a whole cache line per row, 8 rows per wave
-    // instruction) instead of sixteen lanes fetching 16 bytes of sixteen different rows.  The k-major LDS image is then
-    // written with the column XOR-swizzled by the k pair, col = x ^ (k & 14): a wave's 16-lane write groups (8 k pairs x 2
-    // rows) hit 16 distinct bank pairs, and a fragment read (16 consecutive x at one k, XORed with a constant below 16)
-    // stays a permutation of its aligned 16-column block, so the read side keeps its conflict-free pattern.
-    const int kc = tid & 7, row = tid >> 3;  // x = 32q + (t>>3), k = 2 (t&7)
-    goff = (unsigned)((row * ld + 2 * kc) * 8);
-    loff = (unsigned)(((2 * kc) * LDS_S + (row ^ (2 * kc))) * 8);
-    gstride = 32 * ld * 8;
-  } else {
-    const int xl = tid & 15, kc = (tid >> 4) & 7, xh = tid >> 7;  // x = 32q + 16*(t>>7) + (t&15)
-    goff = (unsigned)(((xh * 16 + xl) * ld + 2 * kc) * 8);
-    loff = (unsigned)(((2 * kc) * LDS_S + xh * 16 + xl) * 8);
-    gstride = 32 * ld * 8;
-  }
-}
-__device__ __forceinline__ void chunk_load(const char* __restrict__ base, unsigned goff, long gstride,
-                                           double2_t (&r)[NQS]) {
-#pragma unroll
-  for (int q = 0; q < NQS; ++q) r[q] = *reinterpret_cast<const double2_t*>(base + q * gstride + goff);
-}
-template <bool KMAJOR>
-__device__ __forceinline__ void chunk_store(char* __restrict__ lds, unsigned loff, const double2_t (&r)[NQS]) {
-#pragma unroll
-  for (int q = 0; q < NQS; ++q) {
-    if (KMAJOR) {
-      *reinterpret_cast<double2_t*>(lds + loff + q * (8 * LDS_S * 8)) = r[q];
-    } else {
-      *reinterpret_cast<double*>(lds + loff + q * (32 * 8)) = r[q].x;
-      *reinterpret_cast<double*>(lds + loff + q * (32 * 8) + LDS_S * 8) = r[q].y;
-    }
-  }
-}
 }  // namespace vs
 
 // FLUSH: the k-segmented update (GemmParams::kflush) -- an instantiation of its own, so that the plain kernel keeps the code
@@ -613,11 +616,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
 
   int ti, tj;
   int rc, cc;  // C tile row / column in 64-row units (differ from the operand rows ti / tj only in panel-list mode)
-  // XCD-aware block -> tile map for uniform-k launches, as in the 128x128-tile kernel: workgroup b runs on XCD b % 8, and
-  // each XCD takes a CONTIGUOUS range of the enumeration, so the tiles of one tile row (consecutive indices: they share
-  // their A rows) meet in one L2 instead of eight.
+  // XCD-aware block -> tile map for uniform-k launches: the map of gemm_f64_kernel_b, which explains it (keep the two in
+  // step); no tile0 here, small launches are never split
   int bid = (int)blockIdx.x;
-  if (MIGP_XCD_MAP_S && p.kmode == 0) {
+  if (p.kmode == 0) {
     const int nblk = (int)gridDim.x, x = bid & 7, q = nblk >> 3, r = nblk & 7;
     bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
   }
@@ -637,6 +639,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
       // tail of a 128x128-tile launch: this workgroup is one quadrant of parent tile sub_base + blockIdx.x / 4
       int pti, ptj;
       const int pidx = p.sub_base + (bid >> 2), quad = bid & 3;
+      // the parent launch's order, as gemm_f64_kernel_b chooses it (keep the two in step; tails are uniform-k, kmode is 0 here)
       if (p.fc > 0) tile_from_index_fc(p.sub_mt, p.sub_nt, p.fc, p.band, pidx, pti, ptj);
       else if (p.band > 0 && p.tri) tile_from_index_banded(p.tri, p.sub_mt, p.sub_nt, pidx, p.band, pti, ptj);
       else tile_from_index(p.tri, p.sub_nt, pidx, pti, ptj);
@@ -645,27 +648,23 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
       if (p.tri && tj > ti) return;  // the quadrant above the diagonal of a diagonal parent tile
       if (p.dead_last_half && ti == 2 * p.sub_mt - 1) return;  // the all-zero half of the y^T tile row
     } else {
-      tile_from_index(p, bid, ti, tj);
+      tile_from_index(p, bid, ti, tj);  // a whole launch on 64x64 tiles: row by row only, never fc or banded
       if (p.dead_last_half && ti == p.mt - 1) return;
     }
-    if (p.kmode == 2 && !p.tri) ti = p.mt - 1 - ti;  // as in the 128x128-tile kernel
-    if (p.kmode == 4 && !p.tri) { tj = p.nt - 1 - (int)blockIdx.x / p.mt; ti = (int)blockIdx.x % p.mt; }  // longest-k columns first (LPT order)
+    // longest-k tiles first, as in gemm_f64_kernel_b (keep the two in step; kmode is not 0 here, so bid is blockIdx.x)
+    if (p.kmode == 2 && !p.tri) ti = p.mt - 1 - ti;
+    if (p.kmode == 4 && !p.tri) { tj = p.nt - 1 - (int)blockIdx.x / p.mt; ti = (int)blockIdx.x % p.mt; }
     rc = ti;
     cc = tj;
   }
   const int i0 = ti * TS, j0 = tj * TS;
-  int kbeg = 0, kend = p.k;
-  if (p.kmode == 1) kbeg = j0;
-  else if (p.kmode == 2) kend = i0 + TS;
-  else if (p.kmode == 3) kbeg = i0;
-  else if (p.kmode == 4) kend = j0 + TS;
-  kbeg &= ~(BKS - 1);
+  const KRange kr = k_range<TS>(p, i0, j0);
+  const int kbeg = kr.beg & ~(BKS - 1), kend = kr.end;  // this kernel rounds the start down to a whole chunk
 
-  // blockIdx.z = z1 + batch1 * z2 (two-level batch: nodes of a triangular-inverse level x problems of a batched evaluation)
-  const long z1 = p.batch1 > 0 ? (long)(blockIdx.z % p.batch1) : (long)blockIdx.z, z2 = p.batch1 > 0 ? (long)(blockIdx.z / p.batch1) : 0;
-  const double* A = p.A + z1 * p.strideA + z2 * p.strideA2;
-  const double* B = p.B + z1 * p.strideB + z2 * p.strideB2;
-  double* C = p.C + z1 * p.strideC + z2 * p.strideC2;
+  const BatchPtrs bp = batch_ptrs(p);
+  const double* A = bp.A;
+  const double* B = bp.B;
+  double* C = bp.C;
 
   double4_t acc[2][2];
 #pragma unroll
@@ -676,14 +675,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
   const int nchunk = (kend - kbeg) / BKS;
   unsigned gA, lA, gB, lB;
   long sA, sB;
-  vs::chunk_offsets<A_KMAJOR>(p.lda, tid, gA, lA, sA);
-  vs::chunk_offsets<B_KMAJOR>(p.ldb, tid, gB, lB, sB);
+  chunk_offsets<StageS, A_KMAJOR>(p.lda, tid, gA, lA, sA);
+  chunk_offsets<StageS, B_KMAJOR>(p.ldb, tid, gB, lB, sB);
   const char* Ag = reinterpret_cast<const char*>(A_KMAJOR ? A + (long)kbeg * p.lda + i0 : A + (long)i0 * p.lda + kbeg);
   const char* Bg = reinterpret_cast<const char*>(B_KMAJOR ? B + (long)kbeg * p.ldb + j0 : B + (long)j0 * p.ldb + kbeg);
   const long stepA = (A_KMAJOR ? (long)BKS * p.lda : (long)BKS) * 8;
   const long stepB = (B_KMAJOR ? (long)BKS * p.ldb : (long)BKS) * 8;
-  const int segmask = p.kseg > 0 ? p.kseg / BKS - 1 : 0x7fffffff;  // k-segmented operands, as in the 128x128-tile kernel
-  const long segjump = (p.kseg_stride - (long)(p.kseg - BKS)) * 8;
+  const int segmask = kseg_mask<BKS>(p);
+  const long segjump = kseg_jump<BKS>(p);
   char* Asb = reinterpret_cast<char*>(As);
   char* Bsb = reinterpret_cast<char*>(Bs);
   // Pipeline (chunk = 16 k = 16 MFMAs per wave, 0.43 us): chunk c is requested from global memory during chunk c - 4
@@ -703,16 +702,16 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
   if (nchunk > 0) {
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
-      vs::chunk_load(Ag, gA, sA, ra[u]);
-      vs::chunk_load(Bg, gB, sB, rb[u]);
+      chunk_load(Ag, gA, sA, ra[u]);
+      chunk_load(Bg, gB, sB, rb[u]);
       advance(u + 1);
     }
-    vs::chunk_store<A_KMAJOR>(Asb, lA, ra[0]);
-    vs::chunk_store<B_KMAJOR>(Bsb, lB, rb[0]);
-    vs::chunk_store<A_KMAJOR>(Asb + OPER_S * 8, lA, ra[1]);
-    vs::chunk_store<B_KMAJOR>(Bsb + OPER_S * 8, lB, rb[1]);
-    vs::chunk_load(Ag, gA, sA, ra[0]);  // chunk 3
-    vs::chunk_load(Bg, gB, sB, rb[0]);
+    chunk_store<StageS, A_KMAJOR>(Asb, lA, ra[0]);
+    chunk_store<StageS, B_KMAJOR>(Bsb, lB, rb[0]);
+    chunk_store<StageS, A_KMAJOR>(Asb + OPER_S * 8, lA, ra[1]);
+    chunk_store<StageS, B_KMAJOR>(Bsb + OPER_S * 8, lB, rb[1]);
+    chunk_load(Ag, gA, sA, ra[0]);  // chunk 3
+    chunk_load(Bg, gB, sB, rb[0]);
     advance(4);
   }
   // C tile early: these launches are latency-bound, the read hides under the whole k loop
@@ -730,13 +729,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
   }
   __syncthreads();
 
-  // fragment bases per k4-step: the row-major operands' images are swizzled by the k pair (vs::chunk_offsets), k & 14 =
+  // fragment bases per k4-step: the row-major operands' images are swizzled by the k pair (chunk_offsets, StageS), k & 14 =
   // 4 kk + (kq & 2) for k = 4 kk + kq
   const double* a_ptr[4];
   const double* b_ptr[4];
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) {
-    const int sa = (vs::SWZ && !A_KMAJOR) ? (4 * kk + (kq & 2)) : 0, sb = (vs::SWZ && !B_KMAJOR) ? (4 * kk + (kq & 2)) : 0;
+    const int sa = !A_KMAJOR ? (4 * kk + (kq & 2)) : 0, sb = !B_KMAJOR ? (4 * kk + (kq & 2)) : 0;
     a_ptr[kk] = As + kq * LDS_S + wr * 32 + (l15 ^ sa);
     b_ptr[kk] = Bs + kq * LDS_S + wc * 32 + (l15 ^ sb);
   }
@@ -761,8 +760,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
       const int cur = kk & 1;
       __builtin_amdgcn_sched_barrier(0);
       if (kk == 0) {
-        vs::chunk_load(Ag, gA, sA, ra[s1]);
-        vs::chunk_load(Bg, gB, sB, rb[s1]);
+        chunk_load(Ag, gA, sA, ra[s1]);
+        chunk_load(Bg, gB, sB, rb[s1]);
       }
       if (kk + 1 < BKS / 4) load_frags(cur ^ 1, boff, kk + 1);
       else load_frags(cur ^ 1, s1 * OPER_S, 0);  // first fragments of the next chunk, ahead of the barrier
@@ -771,31 +770,23 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
       acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cur][1], fb[cur][0], acc[1][0], 0, 0, 0);
       acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cur][1], fb[cur][1], acc[1][1], 0, 0, 0);
       if (kk == BKS / 4 - 1) {
-        vs::chunk_store<A_KMAJOR>(Asb + s2 * OPER_S * 8, lA, ra[s2]);
-        vs::chunk_store<B_KMAJOR>(Bsb + s2 * OPER_S * 8, lB, rb[s2]);
+        chunk_store<StageS, A_KMAJOR>(Asb + s2 * OPER_S * 8, lA, ra[s2]);
+        chunk_store<StageS, B_KMAJOR>(Bsb + s2 * OPER_S * 8, lB, rb[s2]);
       }
       if (kk == 0) {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+          sched_groups<SG_MFMA, 1,  SG_VMEM_READ, 1,  SG_DS_READ, 1,  SG_MFMA, 1,  SG_VMEM_READ, 1>();
         }
       } else if (kk + 1 < BKS / 4) {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          sched_groups<SG_MFMA, 1,  SG_DS_READ, 1,  SG_MFMA, 1>();
         }
       } else {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
+          sched_groups<SG_MFMA, 1,  SG_DS_READ, 1,  SG_DS_WRITE, 2>();
         }
       }
     }
@@ -839,6 +830,22 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel_s(GemmParams p) {
       }
 }
 
+
+// Every instantiation, once: the launcher looks its kernel up here and gemm_f64_enable_lds walks the whole table.
+typedef void (*gemm_kernel_t)(GemmParams);
+struct GemmKernel { gemm_kernel_t fn; bool small, flush; int a_kmajor, b_kmajor; };  // small: 64x64 tiles; flush: GemmParams::kflush
+static const GemmKernel GEMM_KERNELS[] = {
+    {gemm_f64_kernel_b<false, false>, false, false, 0, 0}, {gemm_f64_kernel_b<false, true>, false, false, 0, 1},
+    {gemm_f64_kernel_b<true, false>, false, false, 1, 0},  {gemm_f64_kernel_b<true, true>, false, false, 1, 1},
+    {gemm_f64_kernel_s<false, false>, true, false, 0, 0},  {gemm_f64_kernel_s<false, true>, true, false, 0, 1},
+    {gemm_f64_kernel_s<true, false>, true, false, 1, 0},   {gemm_f64_kernel_s<true, true>, true, false, 1, 1},
+    {gemm_f64_kernel_s<false, false, true>, true, true, 0, 0},
+};
+static gemm_kernel_t gemm_kernel(bool small, bool flush, int a_kmajor, int b_kmajor) {
+  for (const GemmKernel& k : GEMM_KERNELS)
+    if (k.small == small && k.flush == flush && k.a_kmajor == !!a_kmajor && k.b_kmajor == !!b_kmajor) return k.fn;
+  return nullptr;  // (only the NT form has a flush instantiation; launch_gemm_f64 refuses the others before it asks)
+}
 
 constexpr size_t LDS_ONE_PER_CU = 82432;  // > half a CU (one workgroup per CU) and <= 160 KB - the 79 KB leaf image
 
@@ -901,13 +908,8 @@ hipError_t launch_gemm_f64(const GemmParams& p_in, int opA_kmajor, int opB_kmajo
     dim3 grid(nwg, 1, batch), block(256);
     // one_per_cu: unused dynamic LDS on top of the 60 KB static image pushes the request over half a CU
     const size_t pad = p.one_per_cu ? LDS_ONE_PER_CU - sizeof(double) * 2 * vs::NBUF * vs::OPER_S : 0;
-    if (q.kflush > 0) {
-      if (opA_kmajor || opB_kmajor || q.kmode != 0 || q.beta == 0.0 || q.kflush % vs::BKS) return hipErrorInvalidValue;
-      gemm_f64_kernel_s<false, false, true><<<grid, block, pad, stream>>>(q);
-    } else if (!opA_kmajor && !opB_kmajor) gemm_f64_kernel_s<false, false><<<grid, block, pad, stream>>>(q);
-    else if (!opA_kmajor && opB_kmajor) gemm_f64_kernel_s<false, true><<<grid, block, pad, stream>>>(q);
-    else if (opA_kmajor && opB_kmajor) gemm_f64_kernel_s<true, true><<<grid, block, pad, stream>>>(q);
-    else gemm_f64_kernel_s<true, false><<<grid, block, pad, stream>>>(q);
+    if (q.kflush > 0 && (opA_kmajor || opB_kmajor || q.kmode != 0 || q.beta == 0.0 || q.kflush % vs::BKS)) return hipErrorInvalidValue;
+    gemm_kernel(true, q.kflush > 0, opA_kmajor, opB_kmajor)<<<grid, block, pad, stream>>>(q);
     return hipGetLastError();
   };
   if (small) return (part == 2 || p.tile0 > 0) ? hipSuccess : launch_small(0);  // small launches are never split
@@ -919,10 +921,7 @@ hipError_t launch_gemm_f64(const GemmParams& p_in, int opA_kmajor, int opB_kmajo
     dim3 grid(big_end - t0, 1, batch), block(vb::NT_B);
     const bool dma = !opA_kmajor && !opB_kmajor;  // the NT form stages its operands by LDS-DMA (64 KiB), the others by registers
     const size_t lds = p.one_per_cu ? LDS_ONE_PER_CU : dma ? vb::LDS_DMA : sizeof(double) * 4 * vb::OPER_B;
-    if (!opA_kmajor && !opB_kmajor) gemm_f64_kernel_b<false, false><<<grid, block, lds, stream>>>(p);
-    else if (!opA_kmajor && opB_kmajor) gemm_f64_kernel_b<false, true><<<grid, block, lds, stream>>>(p);
-    else if (opA_kmajor && opB_kmajor) gemm_f64_kernel_b<true, true><<<grid, block, lds, stream>>>(p);
-    else gemm_f64_kernel_b<true, false><<<grid, block, lds, stream>>>(p);
+    gemm_kernel(false, false, opA_kmajor, opB_kmajor)<<<grid, block, lds, stream>>>(p);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -930,24 +929,11 @@ hipError_t launch_gemm_f64(const GemmParams& p_in, int opA_kmajor, int opB_kmajo
 }
 
 hipError_t gemm_f64_enable_lds() {
-  const int ldsb = (int)LDS_ONE_PER_CU;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_s<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_s<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_s<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_s<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_s<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_b<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_b<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_b<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_b<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
+  for (const GemmKernel& k : GEMM_KERNELS) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_ONE_PER_CU);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace migp

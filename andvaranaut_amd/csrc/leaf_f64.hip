@@ -1051,9 +1051,6 @@ __device__ __forceinline__ void trsm_strip128_body(const double* __restrict__ mi
   }
 }
 
-#ifndef MIGP_XCD_MAP_STRIP
-#define MIGP_XCD_MAP_STRIP 1
-#endif
 // one launch serves `gridDim.y` independent (M, B) pairs: M at minv + y * 16384, B at B + y * strideB
 template <int RG>
 __global__ __launch_bounds__(256) void trsm_strip128_kernel(const double* __restrict__ minv, double* __restrict__ B, long ldb,
@@ -1064,7 +1061,7 @@ __global__ __launch_bounds__(256) void trsm_strip128_kernel(const double* __rest
   // rows: the update that follows reads this strip's rows, and the next strip reads what that update wrote, out of the L2
   // that already holds them.
   int blk = (int)blockIdx.x;
-  if (MIGP_XCD_MAP_STRIP) {
+  {
     const int nblk = (int)gridDim.x, x = blk & 7, q = nblk >> 3, r = nblk & 7;
     blk = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (blk >> 3);
   }
