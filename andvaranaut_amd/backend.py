@@ -160,7 +160,7 @@ class MiGP:
 
     def lml_parts(self):
         a, b = ctypes.c_double(), ctypes.c_double()
-        self.lib.mi_gp_lml_parts(self.h, ctypes.byref(a), ctypes.byref(b))
+        self._check(self.lib.mi_gp_lml_parts(self.h, ctypes.byref(a), ctypes.byref(b)), "mi_gp_lml_parts")
         return a.value, b.value
 
     def lml_grad(self, theta):

@@ -363,6 +363,7 @@ static int factor_internal(mi_gp_handle* h, const double* theta, int what) {
   h->factored = false;
   h->have_kinv = false;
   h->have_u = false;
+  h->have_parts = false;
   if (!h->have_data) { snprintf(h->err, sizeof(h->err), "mi_gp_set_data has not been called"); return -1; }
   if (h->b_cond_k > 0) {  // (a caller may let the single K_dev alias one of the batch's: this evaluation then overwrites that factor)
     const char *s0 = (const char*)h->buf.K_dev, *s1 = s0 + sizeof(double) * (size_t)(h->np + 128) * h->buf.lda;
@@ -409,6 +410,7 @@ static int factor_internal(mi_gp_handle* h, const double* theta, int what) {
   }
   const int info = (int)h->one.out_host[3];  // forwarded by lml_reduce_kernel (reset by set_yrows_kernel)
   if (info != 0x7f7f7f7f) return info;  // 1-based index of the first bad pivot
+  h->have_parts = true;
   return 0;
 }
 
@@ -423,6 +425,8 @@ extern "C" int mi_gp_lml(mi_gp_handle* h, const double* theta, double* lml_out) 
 
 extern "C" int mi_gp_lml_parts(mi_gp_handle* h, double* logdet, double* quad) {
   if (!h) return -1;
+  // (out_host keeps the numbers of a failed evaluation -- NaN behind the bad pivot -- and of none at all)
+  if (!h->have_parts) { snprintf(h->err, sizeof(h->err), "mi_gp_lml_parts: the last single evaluation did not succeed"); return -1; }
   if (logdet) *logdet = h->one.out_host[1];
   if (quad) *quad = h->one.out_host[2];
   return 0;
@@ -493,8 +497,7 @@ extern "C" int mi_gp_grad_x(mi_gp_handle* h, double* gx_dev) {
 extern "C" int mi_gp_set_diag(mi_gp_handle* h, const double* diag_dev) {
   if (!h) return -1;
   h->diag_dev = diag_dev;
-  h->factored = false;
-  h->have_kinv = false;
+  h->factored = h->have_kinv = h->have_u = false;  // (as mi_gp_set_data: K, U and K^-1 belong to the diagonal they were built with)
   h->b_cond_k = 0;
   return 0;
 }

@@ -109,6 +109,8 @@ struct mi_gp_handle {
   bool factored;
   bool have_u;             // Z_dev holds U = L^-T and alpha_dev = K^-1 y of the last mi_gp_factor (mi_gp_predict_grad)
   bool have_kinv;          // W_dev holds K^-1 (lower) and alpha_dev = K^-1 y of the last mi_gp_lml_grad
+  bool have_parts;         // one.out_host[1..2] hold logdet / quad of a single evaluation that succeeded (mi_gp_lml_parts; grown by
+                           // mi_gp_append): cleared by every single evaluation that fails or is refused
   const double* diag_dev;  // optional per-point diagonal added at assembly (mi_gp_set_diag)
   int cap;                 // points the n-dependent scratch above is sized for (mi_gp_reserve; n until it is called)
   size_t gxs_elems;        // doubles gxs_dev holds

@@ -71,8 +71,13 @@ MI_GP_API int mi_gp_set_data(mi_gp_handle* h, const mi_gp_buffers* buffers);
 
 /* LML(theta) = -1/2 |L^-1 y|^2 - sum log L_ii - n/2 log 2pi with L = chol(K(theta) + gv I + jitter I).
  * Replaces the logp evaluation of gp.marginal_likelihood (gpmcmc.py:321-323; explicit form :311-318). */
+/* mi_gp_lml, mi_gp_lml_grad and mi_gp_factor (the single evaluations) all factorise in K_dev: each of them, whether it succeeds,
+ * returns info > 0 or is refused for its theta, ends what an earlier one left resident -- the factor of mi_gp_factor, U and K^-1.
+ * Before the first mi_gp_set_data they return -1. */
 MI_GP_API int mi_gp_lml(mi_gp_handle* h, const double* theta_host, double* lml_out);
-/* sum log L_ii and |L^-1 y|^2 of the last factorisation */
+/* sum log L_ii and |L^-1 y|^2 of the last single evaluation (mi_gp_lml / mi_gp_lml_grad: marginal form, mi_gp_factor: conditional
+ * form), grown by every accepted mi_gp_append.  Host-side numbers: mi_gp_set_data, mi_gp_set_diag and the batch calls leave them.
+ * Returns -1, and writes neither output, before the first single evaluation and while the last one returned info > 0 or -1. */
 MI_GP_API int mi_gp_lml_parts(mi_gp_handle* h, double* logdet_out, double* quad_out);
 
 /* LML and its gradient w.r.t. the natural parameters, grad_out[mi_gp_num_theta()] in theta order
@@ -97,6 +102,12 @@ typedef struct mi_gp_batch_buffers {
   long stride_zw;
   int count;
 } mi_gp_batch_buffers;
+/* mi_gp_set_batch (after mi_gp_set_data: -1 before) binds the buffers and ends the batch's conditional factors; the single-evaluation
+ * state stays.  A batch call that is refused (-1: no buffers bound, k > count, no Z_dev / W_dev for the gradient) changes nothing.
+ * The single K_dev of mi_gp_set_data MAY overlap the batch's K_dev range (member 0 on the single buffer saves one matrix): a batch
+ * call then overwrites the single factor -- which it ends anyway -- and every single evaluation (mi_gp_lml, mi_gp_lml_grad,
+ * mi_gp_factor) overwrites a member's factor, so with overlapping buffers it also ends the batch's conditional factors
+ * (mi_gp_predict_batch returns -1 until the next mi_gp_factor_batch).  Without overlap single evaluations leave them. */
 MI_GP_API int mi_gp_set_batch(mi_gp_handle* h, const mi_gp_batch_buffers* buffers);
 MI_GP_API int mi_gp_lml_batch(mi_gp_handle* h, int k, const double* thetas_host, double* lml_out, int* info_out);
 MI_GP_API int mi_gp_lml_grad_batch(mi_gp_handle* h, int k, const double* thetas_host, double* lml_out, double* grads_out, int* info_out);
@@ -111,7 +122,9 @@ MI_GP_API int mi_gp_lml_grad_batch(mi_gp_handle* h, int k, const double* thetas_
 MI_GP_API int mi_gp_alpha(mi_gp_handle* h, double* alpha_host);
 MI_GP_API int mi_gp_grad_x(mi_gp_handle* h, double* gx_dev);
 /* Optional per-point diagonal (n doubles, device, borrowed; NULL removes it) added to K on top of theta's
- * (gv, jitter): the noise vector `ynoise` of inverse_opt (gpmcmc.py:1134-1158, K += diag(ynoise)). */
+ * (gv, jitter): the noise vector `ynoise` of inverse_opt (gpmcmc.py:1134-1158, K += diag(ynoise)).  Every call, a repeated pointer
+ * included, ends the resident state like mi_gp_set_data: the factor, U, K^-1 and the batch's conditional factors were built with the
+ * diagonal before it.  May be called before mi_gp_set_data. */
 MI_GP_API int mi_gp_set_diag(mi_gp_handle* h, const double* diag_dev);
 
 /* Factorise K(theta) + jitter I + gv I (the conditional's form, [3P] Marginal._build_conditional) and
@@ -124,7 +137,9 @@ MI_GP_API int mi_gp_factor(mi_gp_handle* h, const double* theta_host);
  * ceil(m/128)*128 rows x ldw (ldw even, >= mi_gp_padded_n()); mean_dev / var_dev receive m doubles.
  * Xnew_dev, mean_dev and var_dev (and dmean_dev / dvar_dev below) may be any DEVICE-VISIBLE address: device memory, or pinned
  * host memory (hipHostMalloc) -- for a few points the Python host passes the latter and skips every copy around the call
- * (up to 256 points: 110 -> 48 us per call at N = 512); the call returns with the stream synchronised either way. */
+ * (up to 256 points: 110 -> 48 us per call at N = 512); the call returns with the stream synchronised either way.
+ * mi_gp_predict changes no handle state; mi_gp_predict_u and mi_gp_predict_grad leave U = L^-T (and alpha) resident beside the
+ * factor and change nothing else.  The same query in the same resident state returns the same bits every time. */
 MI_GP_API int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw, double* mean_dev,
                   double* var_dev, int pred_noise);
 /* The same conditional through U = L^-T (formed once per mi_gp_factor, N^3/3 flops): A = K(X*, X) U is one GEMM with
