@@ -852,8 +852,9 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_grad needs Z_dev and W_dev in mi_gp_set_data");
     return -1;
   }
-  if ((size_t)(h->cfg.nkern + 1) * h->cfg.d * sizeof(double) > 61440) {
-    snprintf(h->err, sizeof(h->err), "mi_gp_predict_grad: (nkern + 1) * d must fit 61440 bytes of LDS (d <= %d here)", 7680 / (h->cfg.nkern + 1));
+  if ((size_t)(h->cfg.nkern + 1) * h->cfg.d * sizeof(double) > PREDICT_GRAD_MAX_LDS) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_predict_grad: (nkern + 1) * d must fit %d bytes of LDS (d <= %d here)", (int)PREDICT_GRAD_MAX_LDS,
+             (int)(PREDICT_GRAD_MAX_LDS / sizeof(double)) / (h->cfg.nkern + 1));
     return -1;
   }
   if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_predict_grad: call mi_gp_factor first"); return -1; }

@@ -109,6 +109,37 @@ __device__ __forceinline__ void base_kernel_val_der(int kid, double r2, double a
   }
 }
 
+// What the three kernels that differentiate through the composite covariance (grad_contract, grad_x, predict_grad) share.
+// They hold further copies of one another's code -- the fold's derivative, the micro-tile reads, grad_contract's staging --
+// because this toolchain compiles those to other instructions once they are functions (profiles/NOTES_grad_refactor.md);
+// each such copy names its twins.
+
+// NK = 8 is the one instantiation for 5..8 components: it reads the count at run time, `RUNTIME_NK<NK> ? spec.nkern : NK`
+template <int NK>
+constexpr bool RUNTIME_NK = NK > 4;
+
+// Component c at scaled squared distance r2: kval = kv_c k, dkv = kv_c dk/dr2 and, only under RQ (some component is a
+// rational quadratic), dal = kv_c dk/dalpha -- identically zero otherwise, and then not carried.  kvc is a reference so
+// that a caller's kv[c] is read where it is used.
+template <bool RQ>
+__device__ __forceinline__ void comp_val_der(int kid, double r2, double alpha, const double& kvc, double& kval, double& dkv,
+                                             double& dal) {
+  double k, dk, da;
+  base_kernel_val_der(kid, r2, alpha, k, dk, da);
+  kval = kvc * k;
+  dkv = kvc * dk;
+  if constexpr (RQ) dal = kvc * da;
+}
+
+// Tile e of the lower triangle counted row by row: e = ti (ti + 1) / 2 + tj with tj <= ti (sqrt, then corrected to be exact)
+struct TriTile { int ti, tj; };
+__device__ __forceinline__ TriTile tri_tile(int e) {
+  int t = (int)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
+  while ((t + 1) * (t + 2) / 2 <= e) ++t;
+  while (t * (t + 1) / 2 > e) --t;
+  return {t, e - t * (t + 1) / 2};
+}
+
 // One 64x64 tile of the lower triangle per workgroup; thread (ty, tx) owns the 4x4 strided
 // micro-tile rows ty+16a, cols tx+16b.  part[blockIdx.x][p] receives the block's partial sums.
 // Parameter order p: ls(nk*d), kv(nk), alpha(nk), gv, jitter.
@@ -134,7 +165,7 @@ __global__ __launch_bounds__(256, NK == 1 ? 3 : (NK == 2 && !RQ) ? 2 : 1) void g
   __shared__ double red[256];
   const int tid = threadIdx.x;
   const int d = spec.d;
-  const int nk = NK > 4 ? spec.nkern : NK;  // NK = 8: one instantiation for 5..8 components, run-time count
+  const int nk = RUNTIME_NK<NK> ? spec.nkern : NK;
   const int P = nk * d + 2 * nk + 2;
   double* out = part + (long)blockIdx.x * P;
   int ti, tj;
@@ -149,12 +180,9 @@ __global__ __launch_bounds__(256, NK == 1 ? 3 : (NK == 2 && !RQ) ? 2 : 1) void g
     }
     W -= wrow0 * ldw + wcol0;
   } else {
-    const int e = blockIdx.x;
-    int t = (int)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
-    while ((t + 1) * (t + 2) / 2 <= e) ++t;
-    while (t * (t + 1) / 2 > e) --t;
-    ti = t;
-    tj = e - t * (t + 1) / 2;
+    const TriTile t = tri_tile(blockIdx.x);
+    ti = t.ti;
+    tj = t.tj;
   }
   const int i0 = ti * GT, j0 = tj * GT;
   const int tx = tid & 15, ty = tid >> 4;
@@ -189,7 +217,7 @@ __global__ __launch_bounds__(256, NK == 1 ? 3 : (NK == 2 && !RQ) ? 2 : 1) void g
     for (int m0 = 0; m0 < d; m0 += GDCH) {
       const int dc = min(GDCH, d - m0);
       __syncthreads();
-      {  // 256 % GDCH == 0: a thread always stages the same input dimension, one division per chunk
+      {  // 256 % GDCH == 0: a thread always stages the same input dimension, one division per chunk (again in the length-scale pass)
         const int m = tid % GDCH;
         const double il = (m < dc) ? 1.0 / ls[c * d + m0 + m] : 0.0;
         for (int r = tid / GDCH; r < GT; r += 256 / GDCH) {
@@ -204,7 +232,7 @@ __global__ __launch_bounds__(256, NK == 1 ? 3 : (NK == 2 && !RQ) ? 2 : 1) void g
       }
       __syncthreads();
       for (int m = 0; m < dc; ++m) {
-        double xi[4], xj[4];
+        double xi[4], xj[4];  // the micro-tile's coordinates (same reads: both passes here, grad_x_kernel's pass 1)
 #pragma unroll
         for (int a = 0; a < 4; ++a) xi[a] = Xi[(ty + 16 * a) * GDLD + m];
 #pragma unroll
@@ -220,6 +248,8 @@ __global__ __launch_bounds__(256, NK == 1 ? 3 : (NK == 2 && !RQ) ? 2 : 1) void g
     }
     const int kid = spec.kid[c];
     const double kvc = kv[c], alc = al[c];
+    // (comp_val_der<RQ>, written out: through the function the NK = 4 and NK = 8 instantiations without a rational quadratic
+    // come out with other vector registers)
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -231,7 +261,8 @@ __global__ __launch_bounds__(256, NK == 1 ? 3 : (NK == 2 && !RQ) ? 2 : 1) void g
         if constexpr (RQ) dal[c][a][b] = kvc * da;
       }
   }
-  // coefficient dK/dK_c of the left-to-right fold, times the weight
+  // coefficient dK/dK_c of the left-to-right fold, times the weight (the same recurrence is in grad_x_kernel's coef_elem and
+  // in predict_grad_kernel: a change to the fold goes into all three, and into assemble.hip's forward fold)
   double wc[NK][4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -309,7 +340,7 @@ __global__ __launch_bounds__(256, NK == 1 ? 3 : (NK == 2 && !RQ) ? 2 : 1) void g
     for (int m0 = 0; m0 < d; m0 += GDCH) {
       const int dc = min(GDCH, d - m0);
       __syncthreads();
-      if (!staged) {  // 256 % GDCH == 0: a thread always stages the same input dimension, one division per chunk
+      if (!staged) {  // (pass 1's staging block, word for word)
         const int m = tid % GDCH;
         const double il = (m < dc) ? 1.0 / ls[c * d + m0 + m] : 0.0;
         for (int r = tid / GDCH; r < GT; r += 256 / GDCH) {
@@ -326,7 +357,7 @@ __global__ __launch_bounds__(256, NK == 1 ? 3 : (NK == 2 && !RQ) ? 2 : 1) void g
       // per-dimension sums: wave partials of all dimensions of the chunk go to LDS, ONE barrier, then thread m adds
       // its four (same order as a per-dimension block sum, two barriers per dimension less)
       for (int m = 0; m < dc; ++m) {
-        double xi[4], xj[4];
+        double xi[4], xj[4];  // the micro-tile's coordinates (same reads: both passes here, grad_x_kernel's pass 1)
 #pragma unroll
         for (int a = 0; a < 4; ++a) xi[a] = Xi[(ty + 16 * a) * GDLD + m];
 #pragma unroll
@@ -362,7 +393,6 @@ __global__ __launch_bounds__(256, NK == 1 ? 3 : (NK == 2 && !RQ) ? 2 : 1) void g
 constexpr int GXCH = 16;  // input dimensions per LDS chunk
 constexpr int GXLD = GXCH + 1;
 constexpr int GX_MAXD = 128;  // output dimensions per grad_x pass (window)
-constexpr size_t PREDICT_GRAD_MAX_LDS = 61440;  // dynamic LDS of predict_grad_kernel: (nkern + 1) * d doubles
 
 // Input dimensions beyond GX_MAXD: the host launches one pass per WINDOW of up to 128 output dimensions [w0, w0 + dw); every
 // pass recomputes the coefficient tiles from all d dimensions (pass 1) and contracts them with its window (pass 2).
@@ -380,7 +410,7 @@ __global__ __launch_bounds__(256) void grad_x_kernel(KernSpec spec, const double
   __shared__ double ilc[NK * GXCH];     // 1 / l_cm of the pass-1 chunk being staged
   const int tid = threadIdx.x;
   const int d = spec.d;
-  const int nk = NK > 4 ? spec.nkern : NK;  // NK = 8: one instantiation for 5..8 components, run-time count
+  const int nk = RUNTIME_NK<NK> ? spec.nkern : NK;
   const int dw = min(GX_MAXD, d - w0);  // this pass's output dimensions
   const int nt = (n + GT - 1) / GT;
   const int ib = blockIdx.x, i0 = ib * GT;
@@ -438,7 +468,7 @@ __global__ __launch_bounds__(256) void grad_x_kernel(KernSpec spec, const double
       }
       __syncthreads();
       for (int m = 0; m < dc; ++m) {
-        double xi[4], xj[4];
+        double xi[4], xj[4];  // the micro-tile's coordinates (grad_contract_kernel's reads, leading dimension GXLD)
 #pragma unroll
         for (int a = 0; a < 4; ++a) xi[a] = Xi[(ty + 16 * a) * GXLD + m];
 #pragma unroll
@@ -459,15 +489,10 @@ __global__ __launch_bounds__(256) void grad_x_kernel(KernSpec spec, const double
     // coefficient tiles cf[c] = Wsym * (dK/dK_c of the fold) * kv_c dk_c/dr2
     double cf[NK][4][4];
     auto coef_elem = [&](int a, int b) {
-      double kval[NK], dkv[NK];
+      double kval[NK], dkv[NK], da;
 #pragma unroll
-      for (int c = 0; c < nk; ++c) {
-        double k, dk, da;
-        base_kernel_val_der(spec.kid[c], r2[c][a][b], al[c], k, dk, da);
-        kval[c] = kv[c] * k;
-        dkv[c] = kv[c] * dk;
-      }
-      double pref[NK];
+      for (int c = 0; c < nk; ++c) comp_val_der<false>(spec.kid[c], r2[c][a][b], al[c], kv[c], kval[c], dkv[c], da);
+      double pref[NK];  // dK/dK_c of the fold: grad_contract_kernel's recurrence, per element
       double T = kval[0];
       pref[0] = 1.0;
 #pragma unroll
@@ -729,86 +754,62 @@ static bool has_ratquad(const KernSpec& spec) {
   return false;
 }
 
+// Every instantiation of the three gradient kernels stands in one table per kernel (GRAD_CONTRACT_KERNELS here,
+// GRAD_X_KERNELS and PREDICT_GRAD_KERNELS ahead of their launchers).  One to four components have an instantiation of their
+// own, five to eight share <8>: slot nk_slot(nkern) of each table.
+static int nk_slot(int nkern) { return nkern >= 1 && nkern <= 4 ? nkern - 1 : 4; }
+
+static const decltype(&grad_contract_kernel<1, false>) GRAD_CONTRACT_KERNELS[5][2] = {  // [slot][a component is a rational quadratic]
+    {grad_contract_kernel<1, false>, grad_contract_kernel<1, true>}, {grad_contract_kernel<2, false>, grad_contract_kernel<2, true>},
+    {grad_contract_kernel<3, false>, grad_contract_kernel<3, true>}, {grad_contract_kernel<4, false>, grad_contract_kernel<4, true>},
+    {grad_contract_kernel<8, false>, grad_contract_kernel<8, true>}};
+
+// The contraction over grid.x tiles (grid.z problems) with the kernel's eight trailing arguments, then the fixed-order sum
+// of the tiles' partials
+static hipError_t launch_contract(const KernSpec& spec, const double* theta, const double* X, int n, const double* W, long ldw,
+                                  const double* alpha, double* part, double* grad, hipStream_t stream, dim3 grid,
+                                  int rect_tw, int tj0, long wrow0, long wcol0, int stheta, long sW, long salpha, long spart,
+                                  unsigned* done, double* flag, int sflag, double seq) {
+  const int P = spec.nkern * spec.d + 2 * spec.nkern + 2;
+  GRAD_CONTRACT_KERNELS[nk_slot(spec.nkern)][has_ratquad(spec)]<<<grid, 256, 0, stream>>>(
+      spec, theta, X, n, W, ldw, alpha, part, rect_tw, tj0, wrow0, wcol0, stheta, sW, salpha, spart);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  grad_final_kernel<<<dim3(P, 1, grid.z), 256, 0, stream>>>(part, (int)grid.x, P, grad, spart, stheta, done, flag, sflag, seq);
+  return hipGetLastError();
+}
+
 hipError_t launch_grad_contract(const KernSpec& spec, const double* theta, const double* X, int n, const double* W,
                                 long ldw, const double* alpha, double* part, double* grad, hipStream_t stream, const Batch* bt,
                                 unsigned* done, double* flag, double seq) {
   const int nblk = grad_contract_blocks(n);
-  const int P = spec.nkern * spec.d + 2 * spec.nkern + 2;
-  const dim3 grid(nblk, 1, bt ? bt->nb : 1);
-  const int sth = bt ? bt->stheta : 0;
-  const long sW = bt ? bt->sW : 0, sal = bt ? bt->salpha : 0, sp = bt ? bt->spart : 0;
-  const bool rq = has_ratquad(spec);
-  switch (spec.nkern) {
-    case 1:
-      if (rq) grad_contract_kernel<1, true><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      else grad_contract_kernel<1, false><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      break;
-    case 2:
-      if (rq) grad_contract_kernel<2, true><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      else grad_contract_kernel<2, false><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      break;
-    case 3:
-      if (rq) grad_contract_kernel<3, true><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      else grad_contract_kernel<3, false><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      break;
-    case 4:
-      if (rq) grad_contract_kernel<4, true><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      else grad_contract_kernel<4, false><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      break;
-    default:
-      if (rq) grad_contract_kernel<8, true><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      else grad_contract_kernel<8, false><<<grid, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, 0, 0, 0, 0, sth, sW, sal, sp);
-      break;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  grad_final_kernel<<<dim3(P, 1, bt ? bt->nb : 1), 256, 0, stream>>>(part, nblk, P, grad, sp, sth, done, flag, bt ? bt->sout : 0, seq);
-  return hipGetLastError();
+  return launch_contract(spec, theta, X, n, W, ldw, alpha, part, grad, stream, dim3(nblk, 1, bt ? bt->nb : 1), 0, 0, 0, 0,
+                         bt ? bt->stheta : 0, bt ? bt->sW : 0, bt ? bt->salpha : 0, bt ? bt->spart : 0, done, flag,
+                         bt ? bt->sout : 0, seq);
 }
 
 // Column slab [col0, col0 + cols) of the lower triangle (rows >= col0): W points at element (row0, col0) of K^-1,
-// row0 <= col0, both multiples of 64.  part: grad_contract_slab_blocks() x ntheta doubles.
-int grad_contract_slab_blocks(int n, int col0, int cols) {
-  const int nt = (n + GT - 1) / GT;
-  const int tj0 = col0 / GT, tw = min((cols + GT - 1) / GT, nt - tj0);
-  return tw <= 0 ? 0 : (nt - tj0) * tw;
-}
+// row0 <= col0, both multiples of 64.  Its tiles: columns [tj0, tj0 + tw), rows from tj0 down; tw <= 0: beyond the last column.
+struct SlabTiles {
+  int tj0, tw, nblk;
+  SlabTiles(int n, int col0, int cols) {
+    const int nt = (n + GT - 1) / GT;
+    tj0 = col0 / GT;
+    tw = min((cols + GT - 1) / GT, nt - tj0);
+    nblk = tw <= 0 ? 0 : (nt - tj0) * tw;
+  }
+};
+
+// part: grad_contract_slab_blocks() x ntheta doubles
+int grad_contract_slab_blocks(int n, int col0, int cols) { return SlabTiles(n, col0, cols).nblk; }
 
 hipError_t launch_grad_contract_slab(const KernSpec& spec, const double* theta, const double* X, int n, const double* W,
                                      long ldw, int row0, int col0, int cols, const double* alpha, double* part,
                                      double* grad, hipStream_t stream) {
-  const int nt = (n + GT - 1) / GT;
-  const int tj0 = col0 / GT, tw = min((cols + GT - 1) / GT, nt - tj0);
-  const int P = spec.nkern * spec.d + 2 * spec.nkern + 2;
-  if (tw <= 0) return hipMemsetAsync(grad, 0, sizeof(double) * P, stream);
-  const int nblk = (nt - tj0) * tw;
-  const bool rq = has_ratquad(spec);
-  switch (spec.nkern) {
-    case 1:
-      if (rq) grad_contract_kernel<1, true><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      else grad_contract_kernel<1, false><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      break;
-    case 2:
-      if (rq) grad_contract_kernel<2, true><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      else grad_contract_kernel<2, false><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      break;
-    case 3:
-      if (rq) grad_contract_kernel<3, true><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      else grad_contract_kernel<3, false><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      break;
-    case 4:
-      if (rq) grad_contract_kernel<4, true><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      else grad_contract_kernel<4, false><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      break;
-    default:
-      if (rq) grad_contract_kernel<8, true><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      else grad_contract_kernel<8, false><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, part, tw, tj0, row0, col0, 0, 0, 0, 0);
-      break;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  grad_final_kernel<<<P, 256, 0, stream>>>(part, nblk, P, grad, 0, 0, nullptr, nullptr, 0, 0.0);
-  return hipGetLastError();
+  const SlabTiles sl(n, col0, cols);
+  if (sl.tw <= 0) return hipMemsetAsync(grad, 0, sizeof(double) * (spec.nkern * spec.d + 2 * spec.nkern + 2), stream);
+  return launch_contract(spec, theta, X, n, W, ldw, alpha, part, grad, stream, dim3(sl.nblk), sl.tw, sl.tj0, row0, col0,
+                         0, 0, 0, 0, nullptr, nullptr, 0, 0.0);
 }
 
 // Gradient of the posterior conditional w.r.t. ONE prediction point x* (converted inputs):
@@ -828,7 +829,7 @@ __global__ __launch_bounds__(256) void predict_grad_kernel(KernSpec spec, const 
   __shared__ double red[2][GXCH][4];
   const int tid = threadIdx.x;
   const int d = spec.d;
-  const int nk = NK > 4 ? spec.nkern : NK;  // NK = 8: one instantiation for 5..8 components, run-time count
+  const int nk = RUNTIME_NK<NK> ? spec.nkern : NK;
   double* xs = pg_dyn;
   double* ils = pg_dyn + d;
   const int p = blockIdx.x;
@@ -853,12 +854,10 @@ __global__ __launch_bounds__(256) void predict_grad_kernel(KernSpec spec, const 
           const double df = (xs[m] - xi[m]) * ils[c * d + m];
           r2 += df * df;
         }
-        double k, dk, da;
-        base_kernel_val_der(spec.kid[c], r2, al[c], k, dk, da);
-        kval[c] = kv[c] * k;
-        dkv[c] = kv[c] * dk;
+        double da;
+        comp_val_der<false>(spec.kid[c], r2, al[c], kv[c], kval[c], dkv[c], da);
       }
-      double pref[NK];
+      double pref[NK];  // dK/dK_c of the fold: grad_contract_kernel's recurrence, per training point
       double T = kval[0];
       pref[0] = 1.0;
 #pragma unroll
@@ -904,18 +903,15 @@ __global__ __launch_bounds__(256) void predict_grad_kernel(KernSpec spec, const 
   }
 }
 
+static const decltype(&predict_grad_kernel<1>) PREDICT_GRAD_KERNELS[5] = {  // [slot]
+    predict_grad_kernel<1>, predict_grad_kernel<2>, predict_grad_kernel<3>, predict_grad_kernel<4>, predict_grad_kernel<8>};
+
 hipError_t launch_predict_grad(const KernSpec& spec, const double* theta, const double* X, int n, const double* xstar,
                                int m, const double* alpha, const double* w, long ldw, double* dmean, double* dvar,
                                hipStream_t stream) {
   const size_t lds = sizeof(double) * (size_t)(spec.nkern + 1) * spec.d;
-  if (lds > PREDICT_GRAD_MAX_LDS) return hipErrorInvalidValue;  // d <= 1536 with four components
-  switch (spec.nkern) {
-    case 1: predict_grad_kernel<1><<<m, 256, lds, stream>>>(spec, theta, X, n, xstar, alpha, w, ldw, dmean, dvar); break;
-    case 2: predict_grad_kernel<2><<<m, 256, lds, stream>>>(spec, theta, X, n, xstar, alpha, w, ldw, dmean, dvar); break;
-    case 3: predict_grad_kernel<3><<<m, 256, lds, stream>>>(spec, theta, X, n, xstar, alpha, w, ldw, dmean, dvar); break;
-    case 4: predict_grad_kernel<4><<<m, 256, lds, stream>>>(spec, theta, X, n, xstar, alpha, w, ldw, dmean, dvar); break;
-    default: predict_grad_kernel<8><<<m, 256, lds, stream>>>(spec, theta, X, n, xstar, alpha, w, ldw, dmean, dvar); break;
-  }
+  if (lds > PREDICT_GRAD_MAX_LDS) return hipErrorInvalidValue;  // (mi_gp_predict_grad says which d fit)
+  PREDICT_GRAD_KERNELS[nk_slot(spec.nkern)]<<<m, 256, lds, stream>>>(spec, theta, X, n, xstar, alpha, w, ldw, dmean, dvar);
   return hipGetLastError();
 }
 
@@ -941,6 +937,12 @@ int grad_x_splits(int n, int d) {
   return s < 1 ? 1 : s;
 }
 
+static const decltype(&grad_x_kernel<1, 1>) GRAD_X_KERNELS[5][3] = {  // [slot][window of 1, 2, GX_MAXD / GXCH = 8 chunks]
+    {grad_x_kernel<1, 1>, grad_x_kernel<1, 2>, grad_x_kernel<1, 8>}, {grad_x_kernel<2, 1>, grad_x_kernel<2, 2>, grad_x_kernel<2, 8>},
+    {grad_x_kernel<3, 1>, grad_x_kernel<3, 2>, grad_x_kernel<3, 8>}, {grad_x_kernel<4, 1>, grad_x_kernel<4, 2>, grad_x_kernel<4, 8>},
+    {grad_x_kernel<8, 1>, grad_x_kernel<8, 2>, grad_x_kernel<8, 8>}};
+static_assert(GX_MAXD / GXCH == 8, "GRAD_X_KERNELS' last column is the full window");
+
 // scratch: [grad_x_splits(n, d)][n][d] doubles when more than one split is used (may be null otherwise)
 hipError_t launch_grad_x(const KernSpec& spec, const double* theta, const double* X, int n, const double* W, long ldw,
                          const double* alpha, double* gx_out, double* scratch, hipStream_t stream) {
@@ -948,22 +950,8 @@ hipError_t launch_grad_x(const KernSpec& spec, const double* theta, const double
   double* gx = nsplit > 1 ? scratch : gx_out;
   const dim3 nblk((n + GT - 1) / GT, nsplit);
   // one pass per window of GX_MAXD output dimensions (a single pass up to d = 128)
-#define GX_LAUNCH(NK_)                                                                                                     \
-  do {                                                                                                                    \
-    if (spec.d <= GXCH) grad_x_kernel<NK_, 1><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, gx, 0);          \
-    else if (spec.d <= 2 * GXCH) grad_x_kernel<NK_, 2><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, gx, 0); \
-    else                                                                                                                  \
-      for (int w0 = 0; w0 < spec.d; w0 += GX_MAXD)                                                                        \
-        grad_x_kernel<NK_, GX_MAXD / GXCH><<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, gx, w0);            \
-  } while (0)
-  switch (spec.nkern) {
-    case 1: GX_LAUNCH(1); break;
-    case 2: GX_LAUNCH(2); break;
-    case 3: GX_LAUNCH(3); break;
-    case 4: GX_LAUNCH(4); break;
-    default: GX_LAUNCH(8); break;
-  }
-#undef GX_LAUNCH
+  const auto kern = GRAD_X_KERNELS[nk_slot(spec.nkern)][spec.d <= GXCH ? 0 : spec.d <= 2 * GXCH ? 1 : 2];
+  for (int w0 = 0; w0 < spec.d; w0 += GX_MAXD) kern<<<nblk, 256, 0, stream>>>(spec, theta, X, n, W, ldw, alpha, gx, w0);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || nsplit == 1) return e;
   const long len = (long)n * spec.d;

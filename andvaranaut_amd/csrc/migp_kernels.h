@@ -208,6 +208,8 @@ int grad_x_splits(int n, int d);  // column splits; scratch of [splits][n][d] do
 hipError_t launch_grad_x(const KernSpec& spec, const double* theta, const double* X, int n, const double* W, long ldw,
                          const double* alpha, double* gx, double* scratch, hipStream_t stream);
 // dmean/dvar: [m][d] gradients of the conditional at m points; w: row p = K^-1 k(X, x*_p) (leading dimension ldw)
+// the kernel keeps x* and every component's 1 / l in dynamic LDS: (nkern + 1) * d doubles, at most PREDICT_GRAD_MAX_LDS bytes
+constexpr size_t PREDICT_GRAD_MAX_LDS = 61440;
 hipError_t launch_predict_grad(const KernSpec& spec, const double* theta, const double* X, int n, const double* xstar,
                                int m, const double* alpha, const double* w, long ldw, double* dmean, double* dvar,
                                hipStream_t stream);
