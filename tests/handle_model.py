@@ -63,8 +63,8 @@ def padded(n):
 class Problem:
     """Everything a walk over one size reads: data versions, thetas, diagonals, query points -- all pure functions of the size."""
 
-    def __init__(self, size):
-        c = SIZES[size]
+    def __init__(self, size, cfg=None):
+        c = cfg or SIZES[size]  # (cfg: a size outside the walks' table, tests/test_gpu_handle_layouts.py)
         self.size, self.n0, self.cap, self.kapp, self.d = size, size, c["cap"], c["kapp"], c["d"]
         self.kernel = c["kernel"]
         self.kerns, self.ops = split_kernel(self.kernel)
@@ -883,11 +883,11 @@ class WalkFailure(AssertionError):
 
 class Stats:
     def __init__(self):
-        self.steps = self.refusals = self.infos = self.bit_compares = self.value_compares = 0
+        self.steps = self.refusals = self.infos = self.bit_compares = self.value_compares = self.padding_checks = 0
         self.ops, self.pairs, self.refusal_kinds = {}, set(), {}
 
     def add(self, other):
-        for k in ("steps", "refusals", "infos", "bit_compares", "value_compares"):
+        for k in ("steps", "refusals", "infos", "bit_compares", "value_compares", "padding_checks"):
             setattr(self, k, getattr(self, k) + getattr(other, k))
         for k, v in other.ops.items():
             self.ops[k] = self.ops.get(k, 0) + v
@@ -987,6 +987,13 @@ def run_walk(handle, problem, oracle, ops, seed=None, registry=None):
         res = getattr(handle, name)(*args)
         if res.rc == -2 and exp.rc != -2:
             raise WalkFailure(f"{where}: returned -2 (a HIP / RCCL failure, {res.err!r}): the walk ends here")
+        book = getattr(handle, "bk", None)  # (tests/handle_layouts.py: a handle on poisoned buffers says what the call wrote outside)
+        if book is not None:
+            before = book.checked
+            v = book.violation()
+            st.padding_checks += book.checked - before
+            if v:
+                raise WalkFailure(f"{where}: {v[2]}")
         want = exp.rc
         if want == "info":
             if exp.extra.get("dup"):

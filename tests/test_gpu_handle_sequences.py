@@ -26,6 +26,7 @@ import time
 import numpy as np
 import pytest
 
+import handle_layouts as HL
 import handle_model as H
 
 pytestmark = pytest.mark.gpu
@@ -60,10 +61,40 @@ def _guard():
         pytest.fail(f"not started: an earlier walk ended in a HIP failure ({_STATE['stop']})")
 
 
-class RawHandle:
-    """handle_model's call surface over the C-ABI: the test's own torch buffers, allocated once for the capacity."""
+class TorchBackend:
+    """handle_layouts.Book on the device: flat float64 tensors, strided views, the comparison of the int64 view on the GPU."""
 
-    def __init__(self, problem):
+    def __init__(self, torch, dev):
+        self.torch, self.dev = torch, dev
+
+    def alloc(self, total, bits):
+        t = self.torch.zeros(total, dtype=self.torch.float64, device=self.dev)
+        if bits is not None:
+            t.view(self.torch.int64).fill_(int(bits))
+        return t
+
+    def bits(self, flat):
+        return flat.view(self.torch.int64)
+
+    def index(self, idx):
+        return self.torch.from_numpy(idx).to(self.dev)
+
+    def strided(self, flat, shape, strides, off):
+        return flat.as_strided(shape, strides, off)
+
+    def any_changed(self, pairs, want):
+        return self.torch.stack([(b[i] != want).any() for b, i in pairs]).cpu().tolist()
+
+    def first_changed(self, b, i, want):
+        return int(i[self.torch.nonzero(b[i] != want)[0, 0]])
+
+
+class RawHandle:
+    """handle_model's call surface over the C-ABI: the test's own torch buffers, allocated once for the capacity, under one
+    layout of tests/handle_layouts.py (every allocation, pointer, lda, ldw and stride comes from it; `bk` is its bookkeeping,
+    which run_walk asks after every call what was written outside the writable regions)."""
+
+    def __init__(self, problem, layout=HL.DEFAULT):
         import torch
 
         from andvaranaut_amd import _lib
@@ -84,32 +115,36 @@ class RawHandle:
         self.h, self._lib_mod = h, _lib
         self.n, self.ver, self.next_ver, self.diag_id, self.next_diag, self.f_ti = p.n0, 0, 1, None, 0, None
         capp = H.padded(p.cap)
-        self.capp, self.lda = capp, capp + 16
-        f8 = dict(dtype=torch.float64, device=self.dev)
+        self.capp, self.layout = capp, layout
         with torch.cuda.device(self.dev):
-            self.X = torch.zeros((p.rows, p.d), **f8)
-            self.y = torch.zeros(p.rows, **f8)
-            self.dg = torch.zeros(p.rows, **f8)
-            self.Xpool, self.ypool, self.dpool = torch.zeros_like(self.X), torch.zeros_like(self.y), torch.zeros_like(self.dg)
-            self.Kall = torch.zeros((H.BATCH_COUNT, capp + 128, self.lda), **f8)  # [0] is the single K_dev (the aliased batch's member 0)
-            self.Z = torch.zeros((capp, self.lda), **f8)
-            self.W = torch.zeros((capp, self.lda), **f8)
-            self.bK = torch.zeros((H.BATCH_COUNT, capp + 128, self.lda), **f8)
-            self.bZ = torch.zeros((H.BATCH_COUNT, capp, self.lda), **f8)
-            self.bW = torch.zeros((H.BATCH_COUNT, capp, self.lda), **f8)
-            self.work = torch.zeros((2 * 128, self.lda), **f8)
-            self.bwork = torch.zeros((H.BATCH_COUNT + 1, 128, self.lda), **f8)
-            self.awork = torch.zeros(4 * 128 * self.lda + 65600, **f8)
-            self.xn = torch.from_numpy(p.xnew).to(self.dev)
-            self.out = torch.zeros(8 * H.M_NEW * (p.d + 2), **f8)
-            self.cov = torch.zeros((128, 128), **f8)
-            self.gx = torch.zeros((p.rows, p.d), **f8)
-            self.scov = torch.zeros((128, 128), **f8)
-            self.smean = torch.from_numpy(p.sample_mean).to(self.dev)
-            self.draws = torch.zeros((H.S_SAMPLE, H.M_SAMPLE), **f8)
+            bk = self.bk = HL.Book(layout, capp, TorchBackend(torch, self.dev))
+            self.lda, self.ldw = bk.lda, bk.ldw
+            self.X = bk.vector("X", p.rows * p.d).view(p.rows, p.d)
+            self.y = bk.vector("y", p.rows)
+            self.dg = bk.vector("diag", p.rows)
+            self.Xpool, self.ypool, self.dpool = bk.vector("Xpool", p.rows * p.d).view(p.rows, p.d), bk.vector("ypool", p.rows), bk.vector("dpool", p.rows)
+            self.Kall = bk.matrix("K", capp + 128, "K", H.BATCH_COUNT)  # [0] is the single K_dev (the aliased batch's member 0)
+            self.Z = bk.matrix("Z", capp, "ZW")
+            self.W = bk.matrix("W", capp, "ZW")
+            self.bK = bk.matrix("batch K", capp + 128, "K", H.BATCH_COUNT)
+            self.bZ = bk.matrix("batch Z", capp, "ZW", H.BATCH_COUNT)
+            self.bW = bk.matrix("batch W", capp, "ZW", H.BATCH_COUNT)
+            self.work = bk.matrix("work", 2 * 128, "work")
+            self.bwork = bk.matrix("batch work", 128, "work", H.BATCH_COUNT + 1)
+            self.awork = bk.vector("append work", 4 * 128 * self.ldw + 65600, big=True)
+            self.xn = bk.vector("Xnew", H.M_NEW * p.d).view(H.M_NEW, p.d)
+            self.xn.copy_(torch.from_numpy(p.xnew))
+            self.out = bk.vector("out", 8 * H.M_NEW * (p.d + 2))
+            self.mix = bk.vector("mix", 2 * H.M_NEW)
+            self.cov = bk.vector("cov", 128 * 128, big=True).view(128, 128)
+            self.gx = bk.vector("gx", p.rows * p.d).view(p.rows, p.d)
+            self.scov = bk.vector("sample cov", 128 * 128, big=True).view(128, 128)
+            self.smean = bk.vector("sample mean", H.M_SAMPLE)
+            self.smean.copy_(torch.from_numpy(p.sample_mean))
+            self.draws = bk.vector("draws", H.S_SAMPLE * H.M_SAMPLE).view(H.S_SAMPLE, H.M_SAMPLE)
             self.swork_len = int(self.lib.mi_gp_sample_cov_work(H.M_SAMPLE, H.S_SAMPLE))
-            self.swork = torch.zeros(self.swork_len, **f8)
-            self.dnew = torch.zeros(1, **f8)
+            self.swork = bk.vector("sample work", self.swork_len, big=True)
+            self.dnew = bk.vector("diag new", 1)
             self._pool()
             self.X[: self.n].copy_(self.Xpool[: self.n])
             self.y[: self.n].copy_(self.ypool[: self.n])
@@ -209,7 +244,7 @@ class RawHandle:
         m, d = H.M_NEW, self.p.d
         self._fill(self.out)
         o = self.out.data_ptr()
-        args = [self.h, self.xn.data_ptr(), m, self.work.data_ptr(), self.lda, o, o + 8 * m, 1]
+        args = [self.h, self.xn.data_ptr(), m, self.work.data_ptr(), self.ldw, o, o + 8 * m, 1]
         if grad:
             args += [o + 16 * m, o + 16 * m + 8 * m * d]
         rc = fn(*args)
@@ -233,7 +268,7 @@ class RawHandle:
     def predict_cov(self):
         m = H.M_NEW
         self._fill(self.out, self.cov)
-        rc = self.lib.mi_gp_predict_cov(self.h, self.xn.data_ptr(), m, self.work.data_ptr(), self.lda, self.out.data_ptr(),
+        rc = self.lib.mi_gp_predict_cov(self.h, self.xn.data_ptr(), m, self.work.data_ptr(), self.ldw, self.out.data_ptr(),
                                         self.cov.data_ptr(), 128, 1)
         if rc != 0:
             return self._res(rc, None, [self.out, self.cov])
@@ -263,7 +298,7 @@ class RawHandle:
         head = self.torch.tril(self.Kall[0, :n, :n]).view(self.torch.int64).clone()
         self._sync()
         rc = self.lib.mi_gp_append(self.h, x.data_ptr(), y.data_ptr(), dn.data_ptr() if dn is not None else None, k,
-                                   self.awork.data_ptr(), self.lda)
+                                   self.awork.data_ptr(), self.ldw)
         same = bool(self.torch.equal(head, self.torch.tril(self.Kall[0, :n, :n]).view(self.torch.int64)))
         if rc == 0:
             self.n += k
@@ -274,7 +309,7 @@ class RawHandle:
         b.K_dev = (self.Kall if how == "alias" else self.bK).data_ptr()
         b.Z_dev = self.bZ.data_ptr() if how != "plain" else None
         b.W_dev = self.bW.data_ptr() if how != "plain" else None
-        b.stride_k, b.stride_zw, b.count = (self.capp + 128) * self.lda, self.capp * self.lda, H.BATCH_COUNT
+        b.stride_k, b.stride_zw, b.count = self.bk.stride("K"), self.bk.stride("batch Z"), H.BATCH_COUNT
         return H.Res(self.lib.mi_gp_set_batch(self.h, ctypes.byref(b)), None, self._err())
 
     def _batch_eval(self, which, k, shift):
@@ -301,16 +336,20 @@ class RawHandle:
     def factor_batch(self, k, shift):
         return self._batch_eval("factor", k, shift)
 
-    def predict_batch(self, k):
+    def predict_batch(self, k, mix=False):
         m = H.M_NEW
-        self._fill(self.out)
-        o = self.out.data_ptr()
-        rc = self.lib.mi_gp_predict_batch(self.h, k, self.xn.data_ptr(), m, self.bwork.data_ptr(), self.lda, 128 * self.lda, o,
-                                          o + 8 * k * m, 1, None, None)
+        self._fill(self.out, self.mix)
+        o, x = self.out.data_ptr(), self.mix.data_ptr()
+        rc = self.lib.mi_gp_predict_batch(self.h, k, self.xn.data_ptr(), m, self.bwork.data_ptr(), self.ldw, self.bk.stride("batch work"), o,
+                                          o + 8 * k * m, 1, x if mix else None, x + 8 * m if mix else None)
         if rc != 0:
-            return self._res(rc, None, [self.out])
+            return self._res(rc, None, [self.out, self.mix])
         v = self.out.cpu().numpy()
-        return H.Res(0, {"mean": v[: k * m].reshape(k, m).copy(), "var": v[k * m: 2 * k * m].reshape(k, m).copy()}, self._err())
+        out = {"mean": v[: k * m].reshape(k, m).copy(), "var": v[k * m: 2 * k * m].reshape(k, m).copy()}
+        if mix:
+            w = self.mix.cpu().numpy()
+            out["mix_mean"], out["mix_var"] = w[:m].copy(), w[m:].copy()
+        return H.Res(0, out, self._err())
 
     def set_option(self, what, value):
         return H.Res(self.lib.mi_gp_set_option(self.h, what, value), None, self._err())
