@@ -52,8 +52,11 @@ typedef struct mi_gp_buffers {
   double* K_dev;       /* (np+128) x lda, np = mi_gp_padded_n(): covariance, overwritten by its
                           lower Cholesky factor; the extra 128 rows carry y^T -> beta^T = (L^-1 y)^T */
   long lda;            /* leading dimension of K/Z/W in elements: even, >= np */
-  double* Z_dev;       /* np x lda  U = L^-T, upper triangular (mi_gp_lml_grad / mi_gp_predict_grad only; else may be NULL) */
-  double* W_dev;       /* np x lda  K^-1 (lower triangle) and GEMM scratch (same entry points; else may be NULL) */
+  double* Z_dev;       /* np x lda  U = L^-T, upper triangular (mi_gp_lml_grad / mi_gp_predict_grad only; else may be NULL).
+                          Rows and columns >= n hold the identity, and U is zero below its diagonal inside the diagonal 128 x 128
+                          tiles too (nothing but zeros is ever written to the tiles below them). */
+  double* W_dev;       /* np x lda  K^-1 (lower triangle) and GEMM scratch (same entry points; else may be NULL).  Rows and
+                          columns >= n of the lower triangle hold the identity; the strict upper triangle is scratch. */
 } mi_gp_buffers;
 
 MI_GP_API const char* mi_gp_last_global_error(void);
