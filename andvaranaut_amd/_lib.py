@@ -112,6 +112,9 @@ def load():
     lib.mi_gp_factor_batch.argtypes = [vp, ci, dp, ip]
     lib.mi_gp_reserve.argtypes = [vp, ci]
     lib.mi_gp_append.argtypes = [vp, vp, vp, vp, ci, vp, cl]
+    lib.mi_gp_logpdf_work.argtypes = [cl]
+    lib.mi_gp_logpdf_work.restype = cl
+    lib.mi_gp_logpdf.argtypes = [vp, vp, vp, vp, ci, vp, cl, dp, vp, vp]
     lib.mi_gp_predict_batch.argtypes = [vp, ci, vp, ci, vp, cl, cl, vp, vp, ci, vp, vp]
     lib.mi_gp_predict_cov.argtypes = [vp, vp, ci, vp, cl, vp, vp, cl, ci]
     lib.mi_gp_sample_cov_work.argtypes = [ci, ci]
@@ -155,6 +158,8 @@ def load():
 EXPORTS = [
     "mi_gp_reserve",
     "mi_gp_append",
+    "mi_gp_logpdf_work",
+    "mi_gp_logpdf",
     "mi_gp_last_global_error",
     "mi_gp_last_error",
     "mi_gp_create",

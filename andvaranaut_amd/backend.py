@@ -474,6 +474,61 @@ class MiGP:
             self._drop_batch()
         return 0
 
+    def logpdf(self, theta, Xnew, ynew, diag=None, grad=True):
+        """Joint log predictive density of up to 128 trial points given the training data at theta (mi_gp_logpdf):
+        log p(ynew | y, X, Xnew, theta) = LML(n + k) - LML(n), with its gradients w.r.t. the trial inputs and outputs --
+        (logp, dX [k, d], dy [k]); dX and dy are None with ``grad=False``.  Nothing is committed: the resident factor serves any
+        number of trial sets.  ``diag``: the trial points' entries of the per-point diagonal, required exactly when one is
+        set.  A trial block that is not positive definite gives (-inf, zeros, zeros), ``self.info`` its pivot."""
+        Xnew = np.ascontiguousarray(np.atleast_2d(np.asarray(Xnew, dtype=np.float64)))
+        ynew = np.ascontiguousarray(np.asarray(ynew, dtype=np.float64).reshape(-1))
+        if Xnew.ndim != 2 or Xnew.shape[1] != self.d or Xnew.shape[0] != ynew.shape[0]:
+            raise ValueError("Xnew must be (k, d) and ynew (k,)")
+        k = ynew.shape[0]
+        if not 1 <= k <= 128:
+            raise ValueError("logpdf takes 1 to 128 trial points")
+        if not (np.isfinite(Xnew).all() and np.isfinite(ynew).all()):
+            raise ValueError("Xnew and ynew must be finite")
+        has_diag = getattr(self, "_diag_t", None) is not None
+        if (diag is not None) != has_diag:
+            raise ValueError("diag must be given exactly when a per-point diagonal is set (set_diag)")
+        if diag is not None:
+            diag = np.ascontiguousarray(np.asarray(diag, dtype=np.float64).reshape(-1))
+            if diag.shape != ynew.shape or not np.isfinite(diag).all():
+                raise ValueError("diag must hold one finite entry per trial point")
+        if grad and self.Z_t is None:
+            raise RuntimeError("this MiGP was created with need_grad=False")
+        self._ensure_factored(theta)
+        nin = k * self.d + k + (k if diag is not None else 0)
+        with torch.cuda.device(self.dev):
+            need = int(self.lib.mi_gp_logpdf_work(self.lda))
+            if getattr(self, "_lwork", None) is None or self._lwork.numel() < need:
+                self._lwork = None
+                self._lwork = torch.empty(need, dtype=torch.float64, device=self.dev)
+                torch.cuda.synchronize(self.dev)
+            # (pinned I/O as in predict(): this is the call inverse_opt's optimiser makes once per step)
+            io = self._pinned_io(nin + k * self.d + k)
+            io_np = io.numpy()
+            io_np[: k * self.d] = Xnew.ravel()
+            io_np[k * self.d : k * self.d + k] = ynew
+            if diag is not None:
+                io_np[k * self.d + k : nin] = diag
+            base = io.data_ptr()
+            out = ctypes.c_double()
+            dx_p, dy_p = (base + 8 * nin, base + 8 * (nin + k * self.d)) if grad else (None, None)
+            self.info = self._check(self.lib.mi_gp_logpdf(self.h, base, base + 8 * k * self.d,
+                                                          base + 8 * (k * self.d + k) if diag is not None else None, k,
+                                                          self._lwork.data_ptr(), self.lda, ctypes.byref(out), dx_p, dy_p),
+                                    "mi_gp_logpdf")
+            if grad:
+                self._u_theta_ok = True
+            if self.info != 0:
+                return (-np.inf, np.zeros((k, self.d)), np.zeros(k)) if grad else (-np.inf, None, None)
+            if not grad:
+                return out.value, None, None
+            o = io_np[nin : nin + k * self.d + k].copy()
+        return out.value, o[: k * self.d].reshape(k, self.d), o[k * self.d :]
+
     def _drop_batch(self):
         """The batch buffers were sized for the old n: the next batch call re-creates them (mi_gp_append ended the batch state)."""
         self._bK = self._bZ = self._bW = self._bwork = None
@@ -734,10 +789,11 @@ class MiGP:
         self.lib.mi_gp_set_profiling(self.h, int(level))
 
     def timers(self):
-        out = (ctypes.c_double * 14)()
-        self.lib.mi_gp_timers(self.h, out, 14)
+        out = (ctypes.c_double * 17)()
+        self.lib.mi_gp_timers(self.h, out, 17)
         keys = ["assemble_ms", "cholesky_ms", "reduce_ms", "total_ms", "gemm_ms", "gemm_flops", "gemm_launches",
-                "trtri_ms", "lauum_ms", "contract_ms", "gemm_b_ms", "gemm_b_flops", "gemm_b_launches", "enqueue_ms"]
+                "trtri_ms", "lauum_ms", "contract_ms", "gemm_b_ms", "gemm_b_flops", "gemm_b_launches", "enqueue_ms",
+                "logpdf_block_ms", "logpdf_weights_ms", "logpdf_grad_ms"]
         return dict(zip(keys, list(out)))
 
     def close(self):
@@ -745,7 +801,7 @@ class MiGP:
             self.lib.mi_gp_destroy(self.h)  # synchronises the handle's streams first
             self.h = None
         # the device buffers the handle borrowed (a batch holds K-fold copies of K, U, K^-1)
-        for name in ("_bK", "_bZ", "_bW", "_bwork", "K_t", "Z_t", "W_t", "_work", "_work2", "_gx_t", "_pin_io", "_awork", "_X_store",
+        for name in ("_bK", "_bZ", "_bW", "_bwork", "K_t", "Z_t", "W_t", "_work", "_work2", "_gx_t", "_pin_io", "_awork", "_lwork", "_X_store",
                      "_y_store", "_diag_store"):
             if hasattr(self, name):
                 setattr(self, name, None)

@@ -387,10 +387,13 @@ class ConsumersMixin:
             yvcon = np.sum(wi * yir ** 2) / np.sqrt(np.pi) - ym ** 2
         return yvcon
 
-    def inverse_opt(self, yobs, yvarobs=None, method="map", evaluate_opt=False, jitter=1e-6, **kwargs):
+    def inverse_opt(self, yobs, yvarobs=None, method="map", evaluate_opt=False, jitter=1e-6, resident=False, **kwargs):
         """Bayesian inverse solve of gpmcmc.py:1040-1217: posterior over the input x that produced the
         observation(s) ``yobs`` -- the GP likelihood of the training set extended by ``nobs`` rows that all sit
-        at the unknown x, times the input priors.  The (N + nobs) Cholesky, its LML and dLML/dX run on the device."""
+        at the unknown x, times the input priors.  The (N + nobs) Cholesky, its LML and dLML/dX run on the device.
+        ``resident=True``: the N training rows are factorised ONCE and every potential evaluation is LML(N) + the joint log
+        predictive density of the nobs observation rows (MiGP.logpdf): O(N^2) per step instead of O(N^3), the same
+        potential to rounding."""
         if self.m is None:
             raise Exception("Model must be fitted before running Bayesian optimisation")
         if self.verbose:
@@ -415,18 +418,36 @@ class ConsumersMixin:
         theta[nk * self.nx + 2 * nk] = 0.0  # the noise enters through ynoise only
         xaug = np.zeros((n + nobs, self.nx))
         xaug[:-nobs] = self.xc
-        gpi = MiGP(xaug, yin, self.kernel, device=self.device)
+        if resident and nobs > 128:
+            raise ValueError("inverse_opt(resident=True) takes at most 128 observations (one trial block)")
+        gpi = MiGP(xaug[:n], yin[:n], self.kernel, device=self.device) if resident else MiGP(xaug, yin, self.kernel, device=self.device)
         try:
-            gpi.set_diag(ynoise)
+            if resident:
+                # the training block, its factor and alpha do not move with x: factorise once, LML(N) is a constant
+                gpi.set_diag(ynoise[:n])
+                if gpi.factor(theta) != 0:
+                    raise FloatingPointError(f"covariance not positive definite at pivot {gpi.info}")
+                logdet, quad = gpi.lml_parts()
+                lml_n = -0.5 * n * np.log(2.0 * np.pi) - 0.5 * quad - logdet
 
-            def potential(x):
-                cd = [_con_and_der(self.xconrevs[j], float(x[j])) for j in range(self.nx)]
-                xaug[-nobs:, :] = np.array([c for c, _ in cd])
-                gpi.update_data(X=xaug)
-                val, _, _, gx = gpi.lml_grad_data(theta, want_x=True)
-                if not np.isfinite(val):
-                    return -np.inf, np.zeros(self.nx)
-                return val + logjac, gx[-nobs:].sum(axis=0) * np.array([dv for _, dv in cd])
+                def potential(x):
+                    cd = [_con_and_der(self.xconrevs[j], float(x[j])) for j in range(self.nx)]
+                    xrep = np.tile(np.array([c for c, _ in cd]), (nobs, 1))
+                    val, gx, _ = gpi.logpdf(theta, xrep, yin[-nobs:], diag=ynoise[-nobs:])
+                    if not np.isfinite(val):
+                        return -np.inf, np.zeros(self.nx)
+                    return lml_n + val + logjac, gx.sum(axis=0) * np.array([dv for _, dv in cd])
+            else:
+                gpi.set_diag(ynoise)
+
+                def potential(x):
+                    cd = [_con_and_der(self.xconrevs[j], float(x[j])) for j in range(self.nx)]
+                    xaug[-nobs:, :] = np.array([c for c, _ in cd])
+                    gpi.update_data(X=xaug)
+                    val, _, _, gx = gpi.lml_grad_data(theta, want_x=True)
+                    if not np.isfinite(val):
+                        return -np.inf, np.zeros(self.nx)
+                    return val + logjac, gx[-nobs:].sum(axis=0) * np.array([dv for _, dv in cd])
 
             mp, data = self._drive_input_model(imodel, potential, method, random_start=True, **kwargs)
         finally:

@@ -45,7 +45,7 @@ static hipError_t alloc_scratch(const mi_gp_handle* h, Scratch& s, int k, int ca
   return e;
 }
 
-static Eval one_eval(const mi_gp_handle* h) {
+Eval one_eval(const mi_gp_handle* h) {
   return {h->buf.K_dev, h->buf.Z_dev, h->buf.W_dev, h->one, Batch(), false, h->prof_level};
 }
 
@@ -433,13 +433,14 @@ extern "C" int mi_gp_lml_parts(mi_gp_handle* h, double* logdet, double* quad) {
 }
 
 // out: [assemble_ms, chol_ms, reduce_ms, total_ms, gemm_ms, gemm_flops, n_gemm_launches,
-//       trtri_ms, lauum_ms, contract_ms, gemm_b_ms, gemm_b_flops, n_gemm_b_launches, enqueue_ms (host, any profiling level)]
+//       trtri_ms, lauum_ms, contract_ms, gemm_b_ms, gemm_b_flops, n_gemm_b_launches, enqueue_ms (host, any profiling level),
+//       the last mi_gp_logpdf's conditional-block, weights and gradient-kernel ms]
 extern "C" int mi_gp_timers(mi_gp_handle* h, double* out, int n) {
   if (!h || !out) return -1;
-  const double v[14] = {h->t_assemble_ms, h->t_chol_ms, h->t_reduce_ms, h->t_total_ms, h->t_gemm_ms, h->gemm_flops,
+  const double v[17] = {h->t_assemble_ms, h->t_chol_ms, h->t_reduce_ms, h->t_total_ms, h->t_gemm_ms, h->gemm_flops,
                         h->n_gemm, h->t_trtri_ms, h->t_lauum_ms, h->t_contract_ms, h->t_gemm_big_ms,
-                        h->gemm_big_flops, h->n_gemm_big, h->t_enqueue_ms};
-  for (int i = 0; i < n && i < 14; ++i) out[i] = v[i];
+                        h->gemm_big_flops, h->n_gemm_big, h->t_enqueue_ms, h->t_logpdf_ms[0], h->t_logpdf_ms[1], h->t_logpdf_ms[2]};
+  for (int i = 0; i < n && i < 17; ++i) out[i] = v[i];
   return 0;
 }
 extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_out, double* grad_out) {
@@ -792,7 +793,7 @@ extern "C" int mi_gp_predict_batch(mi_gp_handle* h, int k, const double* Xnew_de
 }
 
 // U = L^-T in Z_dev and alpha = U beta, formed once per mi_gp_factor (mi_gp_predict_u / mi_gp_predict_grad)
-static int make_u_resident(mi_gp_handle* h) {
+int make_u_resident(mi_gp_handle* h) {
   if (h->have_u) return 0;
   HCK(inverse_transpose(h, one_eval(h)), "inverse_transpose");
   HCK(launch_trmv_upper(h->buf.Z_dev, h->buf.lda, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, h->one.alpha_dev, h->stream), "trmv");
@@ -910,40 +911,24 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   return 0;
 }
 
-// Conditional-form factor of n points -> n + k points at the same theta (Schur complement of the appended block):
-//   L21 = K21 L11^-T, S = K22 + noise - L21 L21^T = L22 L22^T, beta2 = L22^-1 (y2 - L21 beta1),
-//   logdet += sum log diag L22, quad += |beta2|^2; with U resident U12 = -U11 L21^T U22, U22 = L22^-T, alpha = U beta.
-// Everything up to the factor of S runs in the caller's work block: a non-positive-definite S leaves the handle untouched.
-// work_dev layout (R = 128 * ldw doubles): [0, R) L21 (then -L22^-1 L21 U11^T), [R, 2R) K21 (then L21 U11^T), [2R, 4R) the
-// k-segmented partial products of L21 L21^T, then the S block (2 * 16384), S's leaf inverse (16384) and L22^-1 row-major (16384).
-extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
-                            double* work_dev, long ldw) {
-  if (!h) { set_global_error("mi_gp_append: null handle"); return -1; }
-  if (!Xnew_dev || !ynew_dev || !work_dev) { snprintf(h->err, sizeof(h->err), "mi_gp_append: null point, value or work buffer"); return -1; }
-  if (k < 1 || k > 128) { snprintf(h->err, sizeof(h->err), "mi_gp_append: 1 <= k <= 128 (got %d)", k); return -1; }
-  if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_append: call mi_gp_factor first"); return -1; }
-  if (h->n + k > h->cap) {
-    snprintf(h->err, sizeof(h->err), "mi_gp_append: n + k = %d exceeds the capacity %d (mi_gp_reserve)", h->n + k, h->cap);
-    return -1;
-  }
-  if (!diag_new_dev != !h->diag_dev) {
-    snprintf(h->err, sizeof(h->err), "mi_gp_append: diag_new_dev must be given exactly when a diagonal is set (mi_gp_set_diag)");
-    return -1;
-  }
-  const int n = h->n, n2 = n + k;
-  const int np = h->np, ntc = h->ntc, np2 = (n2 + 127) / 128 * 128;
+// Phase 1 of mi_gp_append, shared with mi_gp_logpdf (api_logpdf.hip): the conditional of k new points given the resident
+// factor, in the caller's work block alone -- L21 = K21 L11^-T (one GEMM against U when it is resident, else the blocked
+// solve), S = K22 + noise - L21 L21^T and its factor L22 in the S block, beta2 = L22^-1 (y2 - L21 beta1) in row 128 of that
+// block -- then stats = {sum log diag L22, |beta2|^2, the bad-pivot word} on the host.  Of the handle it uses info_dev and the
+// stats scratch; the stream is idle when it returns.
+// work_dev layout (R = 128 * ldw doubles): [0, R) L21, [R, 2R) K21 (U route), [2R, 4R) the k-segmented partial products of
+// L21 L21^T, then the S block (2 * 16384), S's leaf inverse (16384) and room for L22^-1 row-major (16384).
+int conditional_block(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
+                      double* work_dev, long ldw, double stats[3]) {
+  const int n = h->n, np = h->np, ntc = h->ntc;
   const long ld = h->buf.lda;
-  if (ldw < np2 || (ldw & 1)) { snprintf(h->err, sizeof(h->err), "mi_gp_append: ldw must be even and >= padded(n + k) = %d", np2); return -1; }
-  if (ld < np2) { snprintf(h->err, sizeof(h->err), "mi_gp_append: lda of mi_gp_set_data < padded(n + k) = %d", np2); return -1; }
-  HCK(hipSetDevice(h->device), "hipSetDevice");
   if (!h->app_stats_dev) HCK(hipMalloc(&h->app_stats_dev, sizeof(double) * 4), "append scratch");
   const long R = 128L * ldw;
   double *L21 = work_dev, *W1 = work_dev + R, *parts = work_dev + 2 * R, *S = work_dev + 4 * R;
-  double *Sinv = S + 2 * MINV_ELEMS, *Linv22 = Sinv + MINV_ELEMS;
+  double* Sinv = S + 2 * MINV_ELEMS;
   const hipStream_t st = h->stream;
   const double* beta1 = h->buf.K_dev + (long)np * ld;
   const Eval E = one_eval(h);
-  // ---- phase 1: scratch only
   if (h->have_u) {  // L21 = K21 U11: one GEMM against the resident inverse (mi_gp_predict_u's route)
     HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, k, h->buf.X_dev, n, W1, ldw, 128, np, 0, 0, st), "assemble K21");
     HCK(gemm_call(h, E, 0, 1, {W1, ldw}, {h->buf.Z_dev, ld}, {L21, ldw}, 1, ntc, np, 0, 4, 1.0, 0.0, 1), "K21 U11");
@@ -967,9 +952,44 @@ extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const doubl
   HCK(hipMemsetAsync(h->one.info_dev, 0x7f, sizeof(int), st), "info reset");
   HCK(launch_potrf_leaf128(S, 128, Sinv, n, h->one.info_dev, st, S + MINV_ELEMS), "leaf S");
   HCK(launch_append_stats(S, k, h->one.info_dev, h->app_stats_dev, st), "append stats");
-  double stats[3];
-  HCK(hipMemcpyAsync(stats, h->app_stats_dev, sizeof(stats), hipMemcpyDeviceToHost, st), "stats download");
+  HCK(hipMemcpyAsync(stats, h->app_stats_dev, sizeof(double) * 3, hipMemcpyDeviceToHost, st), "stats download");
   HCK(hipStreamSynchronize(st), "stream sync");
+  return 0;
+}
+
+// Conditional-form factor of n points -> n + k points at the same theta (Schur complement of the appended block):
+//   L21 = K21 L11^-T, S = K22 + noise - L21 L21^T = L22 L22^T, beta2 = L22^-1 (y2 - L21 beta1),
+//   logdet += sum log diag L22, quad += |beta2|^2; with U resident U12 = -U11 L21^T U22, U22 = L22^-T, alpha = U beta.
+// Everything up to the factor of S runs in the caller's work block (conditional_block()): a non-positive-definite S leaves the
+// handle untouched.  The commit reuses that block: [0, R) L21 becomes -L22^-1 L21 U11^T, [R, 2R) becomes L21 U11^T.
+extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
+                            double* work_dev, long ldw) {
+  if (!h) { set_global_error("mi_gp_append: null handle"); return -1; }
+  if (!Xnew_dev || !ynew_dev || !work_dev) { snprintf(h->err, sizeof(h->err), "mi_gp_append: null point, value or work buffer"); return -1; }
+  if (k < 1 || k > 128) { snprintf(h->err, sizeof(h->err), "mi_gp_append: 1 <= k <= 128 (got %d)", k); return -1; }
+  if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_append: call mi_gp_factor first"); return -1; }
+  if (h->n + k > h->cap) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_append: n + k = %d exceeds the capacity %d (mi_gp_reserve)", h->n + k, h->cap);
+    return -1;
+  }
+  if (!diag_new_dev != !h->diag_dev) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_append: diag_new_dev must be given exactly when a diagonal is set (mi_gp_set_diag)");
+    return -1;
+  }
+  const int n = h->n, n2 = n + k;
+  const int np = h->np, ntc = h->ntc, np2 = (n2 + 127) / 128 * 128;
+  const long ld = h->buf.lda;
+  if (ldw < np2 || (ldw & 1)) { snprintf(h->err, sizeof(h->err), "mi_gp_append: ldw must be even and >= padded(n + k) = %d", np2); return -1; }
+  if (ld < np2) { snprintf(h->err, sizeof(h->err), "mi_gp_append: lda of mi_gp_set_data < padded(n + k) = %d", np2); return -1; }
+  HCK(hipSetDevice(h->device), "hipSetDevice");
+  const long R = 128L * ldw;
+  double *L21 = work_dev, *W1 = work_dev + R, *S = work_dev + 4 * R;
+  double* Linv22 = S + 3 * MINV_ELEMS;
+  const hipStream_t st = h->stream;
+  const Eval E = one_eval(h);
+  // ---- phase 1: scratch only
+  double stats[3];
+  if (int r = conditional_block(h, Xnew_dev, ynew_dev, diag_new_dev, k, work_dev, ldw, stats)) return r;
   const int info = (int)stats[2];
   if (info != INFO_OK) {
     snprintf(h->err, sizeof(h->err), "mi_gp_append: the appended block is not positive definite (pivot %d); the handle is unchanged", info);

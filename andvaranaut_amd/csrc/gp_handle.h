@@ -99,6 +99,7 @@ struct mi_gp_handle {
   double t_trtri_ms, t_lauum_ms, t_contract_ms;
   double t_enqueue_ms;  // host time of enqueueing the last single evaluation (always measured: two clock reads)
   double t_gemm_big_ms, gemm_big_flops, n_gemm_big;  // the 128x128-tile kernel only
+  double t_logpdf_ms[3];  // the last mi_gp_logpdf: conditional block, weights (L22^-1, S^-1, P, Q, C), gradient kernel
   // batched evaluation (mi_gp_set_batch / mi_gp_lml_batch / mi_gp_lml_grad_batch): the caller's K / Z / W and the batch's
   // scratch (k = bbuf.count or more, sized for n points); batch_eval() hands both to the enqueue code
   mi_gp_batch_buffers bbuf;
@@ -188,3 +189,11 @@ int run_evaluation(mi_gp_handle* h, const Eval& E, int what);
 hipError_t inverse_transpose(mi_gp_handle* h, const Eval& E);  // all of U = L^-T behind a factorisation that started none of it
 hipError_t gemm_call(mi_gp_handle* h, const Eval& E, int ak, int bk, In A, In B, Out C, int mt, int nt, int k, int tri, int kmode,
                      double alpha, double beta, int batch, bool single_form = false);
+
+// api_gp.hip
+Eval one_eval(const mi_gp_handle* h);  // the single problem
+int make_u_resident(mi_gp_handle* h);  // U = L^-T in Z_dev and alpha = U beta, once per mi_gp_factor; 0 or a C-ABI error code
+// mi_gp_append's phase 1 (also mi_gp_logpdf's value): L21, the factor of the Schur complement and beta2 in the caller's work block,
+// stats = {sum log diag L22, |beta2|^2, bad-pivot word}; 0 or a C-ABI error code
+int conditional_block(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
+                      double* work_dev, long ldw, double stats[3]);

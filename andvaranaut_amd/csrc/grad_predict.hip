@@ -915,6 +915,147 @@ hipError_t launch_predict_grad(const KernSpec& spec, const double* theta, const 
   return hipGetLastError();
 }
 
+// ---- mi_gp_logpdf's gradient: dx_im = sum_j C_ij dk(x*_i, x_j)/dx*_im + sum_j D_ij dk(x*_i, x*_j)/dx*_im (api_gp.hip)
+
+// Row i of S^-1 = L22^-T L22^-1 per workgroup (thread j: sum over l >= max(i, j) in index order), and gamma_i = (L22^-T beta2)_i
+// by its thread 0.  Linv is lower triangular with the identity in the padding, beta2 zero there: so are Sinv and gamma.
+__global__ __launch_bounds__(128) void logpdf_sinv_kernel(const double* __restrict__ Linv, const double* __restrict__ beta2,
+                                                          double* __restrict__ Sinv, double* __restrict__ gamma) {
+  const int i = blockIdx.x, j = threadIdx.x;
+  double s = 0.0;
+  for (int l = max(i, j); l < 128; ++l) s = __builtin_fma(Linv[l * 128 + i], Linv[l * 128 + j], s);
+  Sinv[i * 128 + j] = s;
+  if (j == 0) {
+    double g = 0.0;
+    for (int l = i; l < 128; ++l) g = __builtin_fma(Linv[l * 128 + i], beta2[l], g);
+    gamma[i] = g;
+  }
+}
+
+// One thread per training point j: C[i][j] = gamma_i (alpha_j - sum_l gamma_l P[l][j]) + Q[i][j] over Q, in place
+__global__ __launch_bounds__(256) void logpdf_weights_kernel(double* __restrict__ Cw, const double* __restrict__ P, long ldw,
+                                                             const double* __restrict__ alpha_v, const double* __restrict__ gamma,
+                                                             int n, int k, double* __restrict__ dy) {
+  __shared__ double g[128];
+  const int tid = threadIdx.x;
+  if (tid < 128) g[tid] = tid < k ? gamma[tid] : 0.0;
+  __syncthreads();
+  if (dy && blockIdx.x == 0 && tid < k) dy[tid] = -g[tid];
+  const int j = blockIdx.x * 256 + tid;
+  if (j >= n) return;
+  double t = 0.0;
+  for (int l = 0; l < k; ++l) t = __builtin_fma(g[l], P[(long)l * ldw + j], t);
+  const double a = alpha_v[j] - t;
+  for (int i = 0; i < k; ++i) Cw[(long)i * ldw + j] = __builtin_fma(g[i], a, Cw[(long)i * ldw + j]);
+}
+
+// Twin of predict_grad_kernel (its dimension chunks, fold derivative and fixed-order block reduction, word for word where the
+// two agree): one workgroup per trial point p, ONE accumulator set over two point segments -- the n training points with the
+// weights of row p of C, then the kk trial points with D_pj = gamma_p gamma_j - Sinv[p][j].  A coincident point (the trial
+// point itself, duplicates, a training point) contributes 0 through its zero coordinate difference.
+template <int NK>
+__global__ __launch_bounds__(256) void logpdf_grad_kernel(KernSpec spec, const double* __restrict__ theta,
+                                                          const double* __restrict__ X, int n,
+                                                          const double* __restrict__ xstar, int kk,
+                                                          const double* __restrict__ Cw, long ldw,
+                                                          const double* __restrict__ gamma, const double* __restrict__ Sinv,
+                                                          double* __restrict__ dx) {
+  extern __shared__ double pg_dyn[];  // xs[d], then ils[NK][d]: sized by the launcher (any d that fits 64 KB of LDS)
+  __shared__ double red[GXCH][4];
+  const int tid = threadIdx.x;
+  const int d = spec.d;
+  const int nk = RUNTIME_NK<NK> ? spec.nkern : NK;
+  double* xs = pg_dyn;
+  double* ils = pg_dyn + d;
+  const int p = blockIdx.x;
+  const double* kv = theta + nk * d;
+  const double* al = kv + nk;
+  const double* crow = Cw + (long)p * ldw;
+  const double* srow = Sinv + p * 128;
+  const double gp = gamma[p];
+  for (int e = tid; e < d; e += 256) xs[e] = xstar[(long)p * d + e];
+  for (int e = tid; e < nk * d; e += 256) ils[e] = 1.0 / theta[e];
+  __syncthreads();
+  for (int m0 = 0; m0 < d; m0 += GXCH) {
+    const int dc = min(GXCH, d - m0);
+    double am[GXCH];
+#pragma unroll
+    for (int u = 0; u < GXCH; ++u) am[u] = 0.0;
+    for (int i = tid; i < n + kk; i += 256) {
+      const bool trial = i >= n;
+      const double* xi = trial ? xstar + (long)(i - n) * d : X + (long)i * d;
+      const double wi = trial ? gp * gamma[i - n] - srow[i - n] : crow[i];
+      double kval[NK], dkv[NK];
+#pragma unroll
+      for (int c = 0; c < nk; ++c) {
+        double r2 = 0.0;
+        for (int m = 0; m < d; ++m) {
+          const double df = (xs[m] - xi[m]) * ils[c * d + m];
+          r2 += df * df;
+        }
+        double da;
+        comp_val_der<false>(spec.kid[c], r2, al[c], kv[c], kval[c], dkv[c], da);
+      }
+      double pref[NK];  // dK/dK_c of the fold: grad_contract_kernel's recurrence, per point
+      double T = kval[0];
+      pref[0] = 1.0;
+#pragma unroll
+      for (int c = 1; c < nk; ++c) {
+        pref[c] = (spec.op[c - 1] == 0) ? 1.0 : T;
+        T = (spec.op[c - 1] == 0) ? T + kval[c] : T * kval[c];
+      }
+#pragma unroll
+      for (int c = 0; c < nk; ++c) {
+        double coef = pref[c];
+#pragma unroll
+        for (int c2 = c + 1; c2 < nk; ++c2)
+          if (spec.op[c2 - 1] == 1) coef *= kval[c2];
+        const double g = coef * dkv[c];
+#pragma unroll
+        for (int u = 0; u < GXCH; ++u) {
+          if (u < dc) {
+            const double il = ils[c * d + m0 + u];
+            const double dkx = g * 2.0 * (xs[m0 + u] - xi[m0 + u]) * il * il;
+            am[u] += wi * dkx;
+          }
+        }
+      }
+    }
+    // fixed-order block reduction: wave shuffle, then the four wave sums
+#pragma unroll
+    for (int u = 0; u < GXCH; ++u) {
+      double a = am[u];
+      for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+      if ((tid & 63) == 0) red[u][tid >> 6] = a;
+    }
+    __syncthreads();
+    if (tid < dc) dx[(long)p * d + m0 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+    __syncthreads();
+  }
+}
+
+static const decltype(&logpdf_grad_kernel<1>) LOGPDF_GRAD_KERNELS[5] = {  // [slot]
+    logpdf_grad_kernel<1>, logpdf_grad_kernel<2>, logpdf_grad_kernel<3>, logpdf_grad_kernel<4>, logpdf_grad_kernel<8>};
+
+hipError_t launch_logpdf_sinv(const double* Linv, const double* beta2, double* Sinv, double* gamma, hipStream_t stream) {
+  logpdf_sinv_kernel<<<128, 128, 0, stream>>>(Linv, beta2, Sinv, gamma);
+  return hipGetLastError();
+}
+
+hipError_t launch_logpdf_weights(double* Cw, const double* P, long ldw, const double* alpha, const double* gamma, int n, int k,
+                                 double* dy, hipStream_t stream) {
+  logpdf_weights_kernel<<<(n + 255) / 256, 256, 0, stream>>>(Cw, P, ldw, alpha, gamma, n, k, dy);
+  return hipGetLastError();
+}
+
+hipError_t launch_logpdf_grad(const KernSpec& spec, const double* theta, const double* X, int n, const double* xstar, int k,
+                              const double* Cw, long ldw, const double* gamma, const double* Sinv, double* dx, hipStream_t stream) {
+  const size_t lds = sizeof(double) * (size_t)(spec.nkern + 1) * spec.d;
+  if (lds > PREDICT_GRAD_MAX_LDS) return hipErrorInvalidValue;  // (mi_gp_logpdf says which d fit)
+  LOGPDF_GRAD_KERNELS[nk_slot(spec.nkern)]<<<k, 256, lds, stream>>>(spec, theta, X, n, xstar, k, Cw, ldw, gamma, Sinv, dx);
+  return hipGetLastError();
+}
+
 hipError_t launch_trmv_upper_t(const double* U, long ld, const double* x, int n, double* out, hipStream_t stream) {
   trmv_upper_t_kernel<<<(n + 63) / 64, 256, 0, stream>>>(U, ld, x, n, out);
   return hipGetLastError();

@@ -213,6 +213,17 @@ constexpr size_t PREDICT_GRAD_MAX_LDS = 61440;
 hipError_t launch_predict_grad(const KernSpec& spec, const double* theta, const double* X, int n, const double* xstar,
                                int m, const double* alpha, const double* w, long ldw, double* dmean, double* dvar,
                                hipStream_t stream);
+// mi_gp_logpdf's gradient (api_gp.hip has the algebra).  Linv: L22^-1 row-major 128 x 128 (identity in the padding), beta2: 128.
+// Sinv = Linv^T Linv, gamma = Linv^T beta2
+hipError_t launch_logpdf_sinv(const double* Linv, const double* beta2, double* Sinv, double* gamma, hipStream_t stream);
+// Cw (k rows, ldw apart, Q = S^-1 P on entry) becomes C[i][j] = gamma_i (alpha[j] - sum_l gamma_l P[l][j]) + Q[i][j], j < n;
+// dy (optional, k) = -gamma
+hipError_t launch_logpdf_weights(double* Cw, const double* P, long ldw, const double* alpha, const double* gamma, int n, int k,
+                                 double* dy, hipStream_t stream);
+// dx[i][m] (k x d) over the training points (weights: row i of Cw) and the trial points (weights gamma_i gamma_j - Sinv[i][j]);
+// the LDS rule of launch_predict_grad
+hipError_t launch_logpdf_grad(const KernSpec& spec, const double* theta, const double* X, int n, const double* xstar, int k,
+                              const double* Cw, long ldw, const double* gamma, const double* Sinv, double* dx, hipStream_t stream);
 hipError_t launch_predict_reduce(const double* A, long lda, const double* beta, int n, int m, double kdiag,
                                  double noise, double* mean, double* var, hipStream_t stream);
 // batched form (mi_gp_predict_batch, blockIdx.z = problem z): A + z * bt->swork, beta + z * bt->sK, theta + z * bt->stheta; kdiag

@@ -763,6 +763,25 @@ class GPMCMC(ConsumersMixin):
         mu, cov = self.gp.predict_cov(self._theta_from_hypers(self.hypers, jitter), xarg, pred_noise=pred_noise)
         return mu.reshape((-1, 1)), cov
 
+    def log_predictive(self, x, y, jitter=1e-6):
+        """Held-out JOINT log predictive density of up to 128 points (x [M, nx], y [M] or [M, 1]) in the original output
+        units, at ``self.hypers``: log N(y_con | conditional of the fitted GP at x_con, with observation noise) plus the
+        Jacobian sum log|d y_con / d y| when the output conversion has ``der`` (MiGP.logpdf; nothing is appended)."""
+        if self._ensure_gp() is None or self.hypers is None:
+            raise Exception("Error: fit the GP before predicting")
+        x = np.asarray(x, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        if x.ndim != 2 or x.shape[1] != self.nx or x.shape[0] != y.shape[0]:
+            raise ValueError("x must be (M, nx) and y hold M values")
+        if not 1 <= len(y) <= 128:
+            raise ValueError("log_predictive takes 1 to 128 points (the joint density of one trial block)")
+        xarg, xorig = self._converted_x(x, True)
+        yres = y - self._mean_at(xorig)
+        logp, _, _ = self.gp.logpdf(self._theta_from_hypers(self.hypers, jitter), xarg, self.yconrevs[0].con(yres), grad=False)
+        if hasattr(self.yconrevs[0], "der"):
+            logp += float(np.sum(np.log(np.abs(self.yconrevs[0].der(yres)))))
+        return logp
+
     def sample_posterior(self, x, nsamples=1, seed=None, convert=True, revert=True, pred_noise=False, jitter=1e-6):
         """``nsamples`` joint posterior draws at the M points x, an (nsamples, M) array: sample paths of the latent function
         by default (pred_noise=False), of noisy observations with pred_noise=True.  revert=True maps each draw through the

@@ -240,6 +240,40 @@ MI_GP_API int mi_gp_reserve(mi_gp_handle* h, int capacity);
 MI_GP_API int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
                            double* work_dev, long ldw);
 
+/* Joint log predictive density of k trial points given the resident factorisation, and its gradients w.r.t. the trial inputs
+ * and outputs: the differentiable companion of mi_gp_predict_cov, and mi_gp_append's conditional without the commit.  It is the
+ * held-out log predictive density of a fit, and the one term of inverse_opt's potential (gpmcmc.py:1156-1165: the LML of the
+ * training set extended by the observation rows) that moves with the trial x:
+ *     log p(y2 | y1, X1, X2, theta) = LML(n + k) - LML(n).
+ *   mi_gp_logpdf  after a successful mi_gp_factor (or mi_gp_append), 1 <= k <= 128, Xnew_dev k x d, ynew_dev k, diag_new_dev the
+ *                 k entries of the per-point diagonal -- required exactly when one is set, as for mi_gp_append; K22 gets
+ *                 jitter + gv + diag_new.  L21 = K21 L11^-T, S = K22 - L21 L21^T = L22 L22^T, beta2 = L22^-1 (y2 - L21 beta1),
+ *                     *logp_out (host) = -1/2 |beta2|^2 - sum log L22_ii - k/2 log 2 pi.
+ *                 Gradients are computed when dx_dev (k x d) or dy_dev (k) is given (device-visible, either may be NULL); they
+ *                 need Z_dev / W_dev and make U = L^-T resident exactly as mi_gp_predict_grad does, and (nkern + 1) * d doubles
+ *                 must fit 60 KB of LDS as there.  With gamma = L22^-T beta2, P = L21 U11^T, Q = S^-1 P:
+ *                     dy = -gamma,
+ *                     dx[i][m] = sum_{j<n} C[i][j] dk(x*_i, x_j)/dx*_im + sum_{j<k} D[i][j] dk(x*_i, x*_j)/dx*_im,
+ *                     C[i][j] = gamma_i (alpha1[j] - sum_l gamma_l P[l][j]) + Q[i][j],   D[i][j] = gamma_i gamma_j - S^-1[i][j]
+ *                 (the trial rows of alpha_J alpha_J^T - K_J^-1 of the joint system); coincident points (r2 = 0) contribute 0.
+ *                 NO handle state changes, apart from U / alpha becoming resident on a gradient call: the factor, the beta
+ *                 row, the leaf inverses, mi_gp_lml_parts, K^-1's validity, the batch state, n and the capacity all stay (the
+ *                 handle's bad-pivot word and mi_gp_append's scalar scratch are used as scratch).  If S is not positive
+ *                 definite the call returns info > 0 (1-based global index n + pivot), *logp_out = -inf, and dx_dev / dy_dev
+ *                 are not written.  Bad arguments (no factorisation, k out of range, a diagonal mismatch, ldw odd or
+ *                 < mi_gp_padded_n(), gradients without Z_dev / W_dev or beyond the LDS rule, a null buffer) return -1 before
+ *                 any HIP call, with text in mi_gp_last_error(h) (mi_gp_last_global_error() for a null handle); -2 on a HIP
+ *                 failure.  work_dev holds mi_gp_logpdf_work(ldw) doubles; every element a launch reads is written earlier in
+ *                 the same call (a work block full of NaN gives the bits of a zeroed one).  The same query in the same resident
+ *                 state returns the same bits; with and without U resident the value agrees to rounding (the blocked solve
+ *                 against one GEMM with U, as for mi_gp_append).  With profiling level >= 1, mi_gp_timers' out[14..16] receive
+ *                 the call's conditional-block, weights (L22^-1, S^-1, P, Q, C) and gradient-kernel times.
+ *   mi_gp_logpdf_work  doubles of work_dev for a leading dimension ldw: mi_gp_append's 4 * 128 * ldw + 65600, plus S^-1 (16384)
+ *                 and gamma (128); -1 for ldw odd or < 128.  No capacity is needed: nothing grows. */
+MI_GP_API long mi_gp_logpdf_work(long ldw);
+MI_GP_API int mi_gp_logpdf(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
+                           double* work_dev, long ldw, double* logp_out, double* dx_dev, double* dy_dev);
+
 /* tuning knobs (benchmarks / A-B tests), ALL per handle -- nothing here is process-wide:
  *   0  look-ahead: factor the next super-panel on a second stream while the trailing update runs; 0 never, 1 by size
  *      (default: from 20 tile columns = N > 2432 on, where the overlap beats the cross-stream hand-offs -- and from 4 tile
@@ -330,7 +364,8 @@ MI_GP_API int mi_gp_set_profiling(mi_gp_handle* h, int level);
  *             gemm_flops (algorithmic), number of gemm launches, trtri_ms, lauum_ms, contract_ms,
  *             then the same three GEMM figures for the 128x128-tile kernel (gemm_f64_kernel_b) alone
  *             -- of the last evaluation (profiling level >= 1);
- *   out[13] = host time spent enqueueing the last single evaluation's launches, ms (measured at every profiling level) */
+ *   out[13] = host time spent enqueueing the last single evaluation's launches, ms (measured at every profiling level)
+ *   out[14..16] = conditional-block, weights and gradient-kernel ms of the last mi_gp_logpdf (profiling level >= 1) */
 MI_GP_API int mi_gp_timers(mi_gp_handle* h, double* out, int n);
 
 /* ---- block-level operations (also used by the multi-GPU driver and the parity tests) ---- */
