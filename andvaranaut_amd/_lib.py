@@ -115,6 +115,9 @@ def load():
     lib.mi_gp_logpdf_work.argtypes = [cl]
     lib.mi_gp_logpdf_work.restype = cl
     lib.mi_gp_logpdf.argtypes = [vp, vp, vp, vp, ci, vp, cl, dp, vp, vp]
+    lib.mi_gp_kfold_work.argtypes = [ci, cl]
+    lib.mi_gp_kfold_work.restype = cl
+    lib.mi_gp_kfold.argtypes = [vp, ci, ip, ip, vp, cl, vp, vp, vp, ip]
     lib.mi_gp_predict_batch.argtypes = [vp, ci, vp, ci, vp, cl, cl, vp, vp, ci, vp, vp]
     lib.mi_gp_predict_cov.argtypes = [vp, vp, ci, vp, cl, vp, vp, cl, ci]
     lib.mi_gp_sample_cov_work.argtypes = [ci, ci]
@@ -160,6 +163,8 @@ EXPORTS = [
     "mi_gp_append",
     "mi_gp_logpdf_work",
     "mi_gp_logpdf",
+    "mi_gp_kfold_work",
+    "mi_gp_kfold",
     "mi_gp_last_global_error",
     "mi_gp_last_error",
     "mi_gp_create",

@@ -529,6 +529,61 @@ class MiGP:
             o = io_np[nin : nin + k * self.d + k].copy()
         return out.value, o[: k * self.d].reshape(k, self.d), o[k * self.d :]
 
+    KFOLD_MAX_PASS = 256  # folds per pass of mi_gp_kfold (one leaf workgroup per fold: one round on the chip's 256 CUs)
+
+    def kfold(self, theta, folds, moments=True, resident=False):
+        """Exact k-fold cross-validation at theta (mi_gp_kfold): for every fold -- a sequence of 1 to 128 distinct point indices;
+        folds may overlap and need not cover the data; equal folds may be the rows of one 2-D array -- the hold-out predictive of its noisy observations given all other
+        points, out of ONE gradient evaluation: (logp [nfolds], mean, var, info [nfolds]) with ``mean`` / ``var`` lists of
+        one array per fold (its points in the fold's order; None with ``moments=False``), ``logp`` the joint log density of
+        the fold's observations and ``info`` 0 or the 1-based position of the fold's first non-positive pivot (logp = -inf and
+        NaN moments for that fold alone).  ``resident=True`` skips ``lml_grad(theta)``: K^-1 of the last ``lml_grad`` is used
+        as it is (theta is ignored).  The hyper-parameters are the same for every fold: nothing is refitted."""
+        if self.Z_t is None:
+            raise RuntimeError("this MiGP was created with need_grad=False")
+        if isinstance(folds, np.ndarray) and folds.ndim == 2 and folds.shape[0] > 0:
+            # equal folds as the rows of one array (leave-one-out of 16384 points: no Python loop over the folds)
+            sizes = np.full(folds.shape[0], folds.shape[1])
+            idx = np.ascontiguousarray(folds, dtype=np.int32).reshape(-1)
+        else:
+            folds = [np.asarray(f).reshape(-1) for f in folds]
+            if not folds:
+                raise ValueError("kfold needs at least one fold")
+            sizes = np.array([len(f) for f in folds])
+            idx = np.ascontiguousarray(np.concatenate(folds), dtype=np.int32)
+        if sizes.min() < 1 or sizes.max() > 128:
+            raise ValueError(f"every fold holds 1 to 128 points (got sizes {sizes.min()} to {sizes.max()})")
+        if not resident:
+            val, _ = self.lml_grad(theta)
+            if not np.isfinite(val):
+                raise FloatingPointError(f"covariance not positive definite at pivot {self.info}")
+        nf, total = len(sizes), int(sizes.sum())
+        ptr = np.zeros(nf + 1, dtype=np.int32)
+        ptr[1:] = np.cumsum(sizes)
+        info = np.zeros(nf, dtype=np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        with torch.cuda.device(self.dev):
+            work_p, need = None, 0
+            if sizes.max() > 1:  # (leave-one-out runs the closed form: no work block)
+                need = int(self.lib.mi_gp_kfold_work(min(self.KFOLD_MAX_PASS, nf), total))
+                if getattr(self, "_kwork", None) is None or self._kwork.numel() < need:
+                    self._kwork = None
+                    self._kwork = torch.empty(need, dtype=torch.float64, device=self.dev)
+                work_p = self._kwork.data_ptr()
+            out = torch.empty(nf + (2 * total if moments else 0), dtype=torch.float64, device=self.dev)
+            torch.cuda.synchronize(self.dev)
+            base = out.data_ptr()
+            self._check(self.lib.mi_gp_kfold(self.h, nf, ptr.ctypes.data_as(ip), idx.ctypes.data_as(ip), work_p, need, base,
+                                             base + 8 * nf if moments else None, base + 8 * (nf + total) if moments else None,
+                                             info.ctypes.data_as(ip)), "mi_gp_kfold")
+            o = out.cpu().numpy()
+        if not moments:
+            return o[:nf], None, None, info
+        if sizes.min() == sizes.max():
+            return o[:nf], list(o[nf : nf + total].reshape(nf, -1)), list(o[nf + total :].reshape(nf, -1)), info
+        cuts = ptr[1:-1]
+        return o[:nf], np.split(o[nf : nf + total], cuts), np.split(o[nf + total :], cuts), info
+
     def _drop_batch(self):
         """The batch buffers were sized for the old n: the next batch call re-creates them (mi_gp_append ended the batch state)."""
         self._bK = self._bZ = self._bW = self._bwork = None

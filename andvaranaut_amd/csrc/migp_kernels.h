@@ -270,6 +270,20 @@ hipError_t launch_zero_diag_upper(double* L, long ld, int ntiles, hipStream_t st
 hipError_t launch_draw_epilogue(const double* D, long ldp, const double* mean, int m, int s, double* draws, long ldd,
                                 hipStream_t stream);
 
+// ---------------------------------------------------------------- kfold_f64.hip (mi_gp_kfold)
+// idx / ptr: the folds in CSR form on the device; a pass handles the folds f0 .. f0 + nf - 1.  blocks / minv: nf blocks of
+// MINV_ELEMS doubles, vecs: nf x 256 (alpha_I, then y_I), info: one bad-pivot word per fold of the CALL (indexed f0 + f).
+// blocks[f] = K^-1_II from the LOWER triangle of W (identity in the padding), vecs and the INFO_OK reset of the words
+hipError_t launch_kfold_gather(const double* W, long ld, const double* alpha, const double* y, const int* idx, const int* ptr, int f0,
+                               int nf, double* blocks, double* vecs, int* info, hipStream_t stream);
+// behind the leaf (blocks = chol(K^-1_II), minv its inverse): logp[f0 + f], mean / var (optional, both or neither) at the fold's
+// positions of idx; -inf and NaN for a fold whose word is not INFO_OK
+hipError_t launch_kfold_moments(const double* blocks, const double* minv, const double* vecs, const int* ptr, const int* info, int f0,
+                                int nf, double* logp, double* mean, double* var, hipStream_t stream);
+// every fold one point: the closed form, info[f] = 0 or 1
+hipError_t launch_kfold_loo(const double* W, long ld, const double* alpha, const double* y, const int* idx, int nfolds, double* logp,
+                            double* mean, double* var, int* info, hipStream_t stream);
+
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)
 void set_global_error(const char* text);

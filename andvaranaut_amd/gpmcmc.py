@@ -283,6 +283,66 @@ class GPMCMC(ConsumersMixin):
             print(f"R^2 for y is: {out['r2']:0.5f}")
         return out
 
+    def cv_stats(self, nfolds=10, seed=None, folds=None, revert=True, jitter=1e-6):
+        """Exact k-fold cross-validation of the fitted model on its own data: every point is predicted from all points outside
+        its fold, and the figures of ``test_stats`` are formed over all held-out points (``rmse``, ``mea``, ``mpe``, ``r2``,
+        ``ytest``, ``ypred``, ``yvars``, ``xtest``; Gauss-Hermite reversion with ``revert``).  All folds come out of ONE gradient
+        evaluation on the full data (MiGP.kfold) instead of a factorisation per fold.  It works at the stored ``self.hypers``:
+        NO hyper-parameter is refitted per fold, so the figures measure the model at these hyper-parameters (what
+        ``test_stats(method='none')`` measures on one split) and are optimistic where the hyper-parameters were fitted to the
+        same data.  ``nfolds``: an integer >= 2 or 'loo' (leave-one-out); the folds are a random partition --
+        ``np.random.default_rng(seed).permutation`` cut by ``np.array_split`` -- unless ``folds``, a list of index arrays, is
+        given.  A fold holds at most 128 points.  Also returned: ``lpd``, the sum of the folds' joint log predictive densities
+        in the original output units (with the Jacobian sum log|d y_con / d y| when the output conversion has ``der``, as in
+        ``log_predictive``), ``lpd_folds`` (per fold, its Jacobian included), ``folds`` and ``info`` (0 per fold, or the
+        pivot at which the fold's block of K^-1 was not positive definite)."""
+        if self._ensure_gp() is None or self.hypers is None:
+            raise Exception("Error: fit the GP before cross-validating")
+        n = len(self.x)
+        if folds is None:
+            if isinstance(nfolds, str):
+                if nfolds != "loo":
+                    raise ValueError("nfolds must be an integer or 'loo'")
+                folds = [np.array([i]) for i in range(n)]
+            else:
+                k, kmin = int(nfolds), max(2, -(-n // 128))
+                if k < kmin:
+                    raise ValueError(f"{k} folds of {n} points: a fold holds at most 128 points and there are at least two "
+                                     f"folds, so the smallest admissible nfolds is {kmin}")
+                if k > n:
+                    raise ValueError(f"nfolds = {k} exceeds the {n} points")
+                folds = np.array_split(np.random.default_rng(seed).permutation(n), k)
+        folds = [np.asarray(f, dtype=np.int64).reshape(-1) for f in folds]
+        equal = len({len(f) for f in folds}) == 1
+        logp, mu, var, info = self.gp.kfold(self._theta_from_hypers(self.hypers, jitter), np.stack(folds) if equal else folds)
+        idx = np.concatenate(folds)
+        xtest, ytest, ymtest = self.x[idx, :], self.y[idx, :], self.ym[idx, :]
+        ypred, yvars = np.concatenate(mu).reshape((-1, 1)), np.concatenate(var).reshape((-1, 1))
+        if revert:
+            yt = ytest[:, 0]
+            ypred, yvars = self.__gh_stats(xtest, ypred, yvars, normvar=False)
+            meany = np.mean(self.y)
+        else:
+            yt = self.yconrevs[0].con(ytest[:, 0] - ymtest[:, 0])
+            meany = np.mean(self.yconrevs[0].con((self.y - self.ym)[:, 0]))
+        ypred, yvars = ypred[:, 0], yvars[:, 0]
+        lpd_folds = np.array(logp, dtype=np.float64)
+        if hasattr(self.yconrevs[0], "der"):
+            jac = np.log(np.abs(self.yconrevs[0].der(ytest[:, 0] - ymtest[:, 0])))
+            lpd_folds = lpd_folds + np.add.reduceat(jac, np.cumsum([0] + [len(f) for f in folds[:-1]]))
+        out = {"rmse": float(np.sqrt(np.mean((ypred - yt) ** 2))), "mea": float(np.mean(np.abs(ypred - yt))),
+               "mpe": float(np.mean(np.abs(ypred - yt) / np.abs(yt))),
+               "r2": float(1 - np.sum((ypred - yt) ** 2) / np.sum((yt - meany) ** 2)),
+               "xtest": xtest if revert else self._converted(xtest, ytest - ymtest)[0], "ytest": yt, "ypred": ypred,
+               "yvars": yvars, "lpd": float(np.sum(lpd_folds)), "lpd_folds": lpd_folds, "folds": folds, "info": info}
+        if self.verbose:
+            print(f"RMSE for y is: {out['rmse']:0.5e}")
+            print(f"Mean absoulte error for y is: {out['mea']:0.5e}")
+            print(f"Mean percentage error for y is: {out['mpe']:0.5%}")
+            print(f"R^2 for y is: {out['r2']:0.5f}")
+            print(f"Log predictive density is: {out['lpd']:0.5e}")
+        return out
+
     def y_dist(self, mode="hist_kde", nsamps=None, return_data=False, surrogate=True, seed=None):
         """Uncertainty propagation through the surrogate (gpmcmc.py:140-151; tutorial.ipynb cell 34): a Latin-hypercube sample of the
         input priors is pushed through ``predict`` (one device sweep via U = L^-T for large ``nsamps``).  The density plots of

@@ -274,6 +274,48 @@ MI_GP_API long mi_gp_logpdf_work(long ldw);
 MI_GP_API int mi_gp_logpdf(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
                            double* work_dev, long ldw, double* logp_out, double* dx_dev, double* dy_dev);
 
+/* Exact k-fold cross-validation at fixed hyper-parameters, from the K^-1 and alpha = K^-1 y that the last successful mi_gp_lml_grad
+ * left resident: "how well does the model predict points it has not seen", the question GPMCMC.test_stats answers with one random
+ * split and a refit (the numeric half of test_plots, gpmcmc.py:933-976), for every fold of a partition at the cost of one
+ * gradient evaluation plus one 128 x 128 factorisation per fold.  For an index set I the hold-out predictive of the noisy
+ * observations y_I given all other points is exact in the blocks of K^-1 (marginal form, a per-point diagonal of mi_gp_set_diag
+ * included -- the density mi_gp_logpdf defines for its trial block):
+ *     Sigma_I = (K^-1_II)^-1,   y_I - mu_I = Sigma_I alpha_I,
+ *     log p(y_I | y_-I) = -1/2 alpha_I^T Sigma_I alpha_I + 1/2 log det K^-1_II - |I|/2 log 2 pi.
+ *   mi_gp_kfold  nfolds >= 1 folds in CSR form on the HOST: fold f is the points fold_idx_host[fold_ptr_host[f] ..
+ *                fold_ptr_host[f + 1]), fold_ptr_host[0] = 0; 1 to 128 points per fold, indices in [0, n), distinct inside a
+ *                fold, in any order; folds may overlap one another and need not cover the data.  Outputs (device-visible
+ *                addresses as for mi_gp_predict): logp_dev[nfolds]; mean_dev[t] = mu and var_dev[t] = diag Sigma_I for position
+ *                t of fold_idx_host (both or neither).  info_out[nfolds] (host, optional): 0, or the 1-based position inside
+ *                the fold of the first non-positive pivot of K^-1_II -- that fold's logp is -inf and its moments NaN, the other
+ *                folds are not affected, and the call still returns 0.
+ *                Per pass of up to P folds: a gather of K^-1_II into a 128 x 128 block per fold (element (a, b) from
+ *                W[max(i_a, i_b)][min(i_a, i_b)]: the strict upper triangle of W_dev, scratch, is never read; identity in the
+ *                padding) with alpha_I and y_I; the factorisation's leaf kernel, one workgroup per fold, for C = chol(K^-1_II)
+ *                and M = C^-1; and one workgroup per fold for t = M alpha_I, mean = y_I - M^T t, var_j = sum_r M[r][j]^2,
+ *                logp = -1/2 |t|^2 + sum log C_ii - |I|/2 log 2 pi, every sum in a fixed order.  P = the folds work_dev holds
+ *                (work_len doubles, 16-byte aligned): a fold's result does not depend on P, the same query in the same state
+ *                returns the same bits, and every element a launch reads is written earlier in the same call (a work block
+ *                full of NaN changes nothing).  The library stages the index lists into the work block itself.
+ *                A call in which every fold has ONE point (leave-one-out) runs the closed form in one launch and needs no work
+ *                block (work_dev may be NULL): var = 1 / Kinv_ii, mean = y_i - alpha_i / Kinv_ii,
+ *                logp = 1/2 log Kinv_ii - 1/2 alpha_i^2 / Kinv_ii - 1/2 log 2 pi; Kinv_ii <= 0 gives info 1.
+ *                NO handle state changes: nothing is written to K_dev, Z_dev or W_dev, and the handle's bad-pivot word and
+ *                mi_gp_append's scalar scratch are not used.  Returns 0; -1 for bad arguments -- K^-1 not resident (before
+ *                mi_gp_lml_grad; after mi_gp_set_data, mi_gp_set_diag, mi_gp_lml, mi_gp_factor, mi_gp_append or a batch call),
+ *                nfolds < 1, a fold outside 1..128 points, an index outside [0, n) or repeated inside a fold, a null buffer,
+ *                one of mean_dev / var_dev alone, a work block too small for one fold -- checked on the host before any HIP
+ *                call, with text in mi_gp_last_error(h) (mi_gp_last_global_error() for a null handle); -2 on a HIP failure.
+ *                Returns with the stream synchronised.
+ *   mi_gp_kfold_work  doubles of work_dev for P = folds_per_pass and total_idx = fold_ptr_host[nfolds]: per fold two 128 x 128
+ *                blocks and the gathered alpha_I / y_I (2 * 16384 + 256), plus 2 * total_idx + 2 for the staged index lists
+ *                and the folds' bad-pivot words; -1 for folds_per_pass < 1 or total_idx < 1.
+ * Out of scope: gradients w.r.t. theta; folds of more than 128 points (they need a blocked factorisation of K^-1_II); the full
+ * Sigma_I; a batched (one theta per member) form; phase timers. */
+MI_GP_API long mi_gp_kfold_work(int folds_per_pass, long total_idx);
+MI_GP_API int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host, const int* fold_idx_host, double* work_dev,
+                          long work_len, double* logp_dev, double* mean_dev, double* var_dev, int* info_out);
+
 /* tuning knobs (benchmarks / A-B tests), ALL per handle -- nothing here is process-wide:
  *   0  look-ahead: factor the next super-panel on a second stream while the trailing update runs; 0 never, 1 by size
  *      (default: from 20 tile columns = N > 2432 on, where the overlap beats the cross-stream hand-offs -- and from 4 tile
