@@ -178,6 +178,26 @@ class MiGP:
         self.info = self._check(self.lib.mi_gp_lml_grad(self.h, tp, ctypes.byref(out), gp_), "mi_gp_lml_grad")
         return out.value, grad
 
+    OBJECTIVES = {"lml": 0, "loo": 1}
+
+    def set_objective(self, objective):
+        """What lml_grad returns (option 48 of mi_gp_set_option): "lml", the log marginal likelihood, or "loo", the leave-one-out
+        log predictive density sum_i log p(y_i | y_-i) with its exact theta gradient.  lml, the batched evaluations,
+        lml_grad_data's data-side gradients and kfold keep their meaning ("loo" has no batched form: lml_grad_batch raises)."""
+        if objective not in self.OBJECTIVES:
+            raise ValueError(f"objective must be one of {list(self.OBJECTIVES)}")
+        self.set_option(48, self.OBJECTIVES[objective])
+
+    def loo_grad(self, theta):
+        """(L_LOO, dL_LOO/dtheta) at natural-scale theta, whatever objective is set (it is the same afterwards); (-inf, zeros)
+        if K is not positive definite or a diagonal entry of K^-1 is not positive (``info``)."""
+        before = self.get_option(48)
+        self.set_option(48, 1)
+        try:
+            return self.lml_grad(theta)
+        finally:
+            self.set_option(48, before)
+
     # ------------------------------------------------------------------ batched evaluation
     def _ensure_batch(self, k, need_grad):
         """Device buffers for k problems in lockstep (mi_gp_set_batch): K (+ Z, W for the gradient) as ONE tensor each."""

@@ -64,7 +64,7 @@ static void release_handle(mi_gp_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   free_scratch(h->one);
   free_scratch(h->batch);
-  (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
+  (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev); (void)hipFree(h->loo_vec_dev);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -190,6 +190,21 @@ static int special_option(mi_gp_handle* h, int what, const int* set, int* get) {
     case 47:
       if (set) { h->spin_us = *set < 0 ? 0 : *set; h->spin_backoff = 0; }
       else *get = h->spin_us;
+      return 1;
+    case 48:  // what mi_gp_lml_grad returns (no resident state changes with it)
+      if (set) {
+        if (*set != 0 && *set != 1) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 48 is 0 (log marginal likelihood) or 1 (leave-one-out), got %d", *set);
+          return -1;
+        }
+        if (*set == 1 && !loo_objective) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the leave-one-out objective (option 48 = 1) is not part of this build");
+          return -1;
+        }
+        h->objective = *set;
+      } else {
+        *get = h->objective;
+      }
       return 1;
   }
   return 0;
@@ -458,6 +473,8 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
   *lml_out = h->one.out_host[0];
   for (int i = 0; i < h->ntheta; ++i) grad_out[i] = h->one.grad_host[i];
   h->have_kinv = true;
+  // option 48 = 1: the same evaluation, then the leave-one-out tail on the resident K^-1 and alpha (api_loo.hip)
+  if (h->objective == 1) return loo_objective(h, lml_out, grad_out);
   return 0;
 }
 
@@ -576,6 +593,10 @@ extern "C" int mi_gp_lml_batch(mi_gp_handle* h, int k, const double* thetas, dou
 
 extern "C" int mi_gp_lml_grad_batch(mi_gp_handle* h, int k, const double* thetas, double* lml_out, double* grad_out, int* info_out) {
   if (!h || !thetas || !lml_out || !grad_out) return -1;
+  if (h->objective == 1) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad_batch: the leave-one-out objective (option 48 = 1) has no batched form");
+    return -1;
+  }
   return batch_internal(h, k, thetas, 2, lml_out, grad_out, info_out);
 }
 
@@ -879,6 +900,18 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
   return 0;
 }
 
+// The vectors of the leave-one-out objective (api_loo.hip), all zero: the zero vector among them is never written again
+hipError_t size_loo_vectors(mi_gp_handle* h, int cap) {
+  const size_t len = (size_t)LOO_VECS * ((cap + 127) / 128 * 128) + 8;
+  (void)hipFree(h->loo_vec_dev);
+  h->loo_vec_dev = nullptr;
+  h->loo_cap = 0;
+  hipError_t e = hipMalloc(&h->loo_vec_dev, sizeof(double) * len);
+  if (e == hipSuccess) e = hipMemset(h->loo_vec_dev, 0, sizeof(double) * len);
+  if (e == hipSuccess) h->loo_cap = cap;
+  return e;
+}
+
 // ---------------------------------------------------------------- appending points at fixed theta
 // The handle's n-dependent scratch for up to `capacity` points; the resident contents (leaf inverses, alpha) are kept.
 extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
@@ -908,6 +941,7 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   (void)hipFree(s.dinv_dev); (void)hipFree(s.alpha_dev); (void)hipFree(s.part_dev);
   s.dinv_dev = dinv; s.alpha_dev = alpha; s.part_dev = part;
   h->cap = capacity;
+  if (h->loo_vec_dev) HCK(size_loo_vectors(h, capacity), "mi_gp_reserve");
   return 0;
 }
 

@@ -116,6 +116,11 @@ struct mi_gp_handle {
   int cap;                 // points the n-dependent scratch above is sized for (mi_gp_reserve; n until it is called)
   size_t gxs_elems;        // doubles gxs_dev holds
   double* app_stats_dev;   // [4] mi_gp_append's scalar increments and bad-pivot word
+  int objective;           // option 48: what mi_gp_lml_grad returns -- 0 the log marginal likelihood, 1 the leave-one-out log
+                           // predictive density (loo_objective() behind the ordinary evaluation)
+  double* loo_vec_dev;     // [LOO_VECS][padded loo_cap] e, s, q, w, the zero vector and the per-point logp, then [8] scalars
+                           // (allocated by the first evaluation under option 48 = 1; mi_gp_reserve drops it, the next one re-sizes it)
+  int loo_cap;             // points loo_vec_dev is sized for
   char err[256];
 };
 
@@ -197,3 +202,12 @@ int make_u_resident(mi_gp_handle* h);  // U = L^-T in Z_dev and alpha = U beta, 
 // stats = {sum log diag L22, |beta2|^2, bad-pivot word}; 0 or a C-ABI error code
 int conditional_block(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
                       double* work_dev, long ldw, double stats[3]);
+// the handle's vectors of the leave-one-out objective for up to cap points (zeroed; what they held is not kept)
+constexpr int LOO_VECS = 6;
+hipError_t size_loo_vectors(mi_gp_handle* h, int cap);
+
+// api_loo.hip: the tail of mi_gp_lml_grad under option 48 = 1, behind a successful ordinary evaluation (K^-1 in W_dev, alpha
+// resident).  *value = L_LOO and grad[ntheta] its gradient; 0, the 1-based index of the first bad K^-1_ii (-inf, zero gradient) or
+// a C-ABI error code.  Weak: api_gp.hip also links without it (the host-only schedule-trace program), and option 48 = 1 is
+// refused there.
+int loo_objective(mi_gp_handle* h, double* value, double* grad) __attribute__((weak));

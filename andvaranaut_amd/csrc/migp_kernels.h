@@ -284,6 +284,20 @@ hipError_t launch_kfold_moments(const double* blocks, const double* minv, const 
 hipError_t launch_kfold_loo(const double* W, long ld, const double* alpha, const double* y, const int* idx, int nfolds, double* logp,
                             double* mean, double* var, int* info, hipStream_t stream);
 
+// ---------------------------------------------------------------- loo_f64.hip (option 48: the leave-one-out objective, api_loo.hip)
+// From P = K^-1 (LOWER triangle of W) and alpha: logp[i] (mi_gp_kfold's singleton density), e[i] = alpha_i / p_i,
+// s[i] = sqrt((1 + alpha_i^2 / p_i) / p_i), q[i] = e[i] / s[i] for i < n; scal[0] = sum logp in a fixed order, scal[1] = 1-based index
+// of the first p_i that is not a positive finite number (0: none; that point gets logp = -inf and zero weights)
+hipError_t launch_loo_weights(const double* W, long ld, const double* alpha, int n, double* e, double* s, double* q, double* logp,
+                              double* scal, hipStream_t stream);
+// B[i][j] = P[max(i, j)][min(i, j)] * s[j] for i, j < n, zeros up to np: the full np x np matrix (np a multiple of 128)
+hipError_t launch_loo_scale_mirror(const double* W, long ldw, const double* s, int n, int np, double* B, long ldb,
+                                   hipStream_t stream);
+// w[i] = sum_{k < n} B[i][k] q[k], i < n
+hipError_t launch_loo_gemv(const double* B, long ld, const double* q, int n, double* w, hipStream_t stream);
+// G[i][j] = -(alpha_i w_j + w_i alpha_j) over the 128 x 128 tiles on and below the block diagonal (whole tiles), zeros up to np
+hipError_t launch_loo_rank2_init(const double* alpha, const double* w, int n, int np, double* G, long ld, hipStream_t stream);
+
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)
 void set_global_error(const char* text);

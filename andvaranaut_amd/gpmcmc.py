@@ -415,10 +415,17 @@ class GPMCMC(ConsumersMixin):
 
     # ------------------------------------------------------------------ fit
     def fit(self, method="map", return_data=False, iwgp=False, cwgp=False, jitter=1e-6, truncate=False,
-            restarts=1, **kwargs):
-        """gpmcmc.py:175-182."""
+            restarts=1, objective="lml", **kwargs):
+        """gpmcmc.py:175-182.  ``objective="loo"`` (with ``method="map"``) maximises the leave-one-out log predictive density
+        sum_i log p(y_i | y_-i) plus the priors instead of the log marginal likelihood (Rasmussen & Williams section 5.4.2: the
+        criterion for a misspecified kernel family); the hyper-parameters are stored as a MAP fit stores them.  It has no
+        sampler (a pseudo-likelihood) and no warps (their data-side gradients are the marginal likelihood's)."""
+        if objective not in MiGP.OBJECTIVES:
+            raise ValueError(f"objective must be one of {list(MiGP.OBJECTIVES)}")
+        if objective == "loo" and (method != "map" or iwgp or cwgp):
+            raise ValueError("objective='loo' needs method='map' and neither iwgp nor cwgp")
         self.m, self.gp, self.hypers, data = self.__fit(self.x, self.y - self.ym, method, iwgp, cwgp, jitter,
-                                                        truncate, restarts, **kwargs)
+                                                        truncate, restarts, objective=objective, **kwargs)
         if return_data:
             return data
 
@@ -529,7 +536,7 @@ class GPMCMC(ConsumersMixin):
 
         return likelihood
 
-    def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, **kwargs):
+    def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", **kwargs):
         n_i, n_pos, n_free = self._warp_sizes(iwgp, cwgp)
         model = HyperModel(self.nx, self.kerns, noise=self.noise, truncate=truncate, jitter=jitter, n_iwgp=n_i,
                            n_cwgp_pos=n_pos, n_cwgp=n_free)
@@ -541,6 +548,8 @@ class GPMCMC(ConsumersMixin):
         fun_map = lambda q: model.logp_dlogp(q, gp.lml_grad, jacobian=False, likelihood=lik)  # noqa: E731
         data = None
         if method == "map":
+            if objective != "lml":
+                gp.set_objective(objective)  # (gp.lml_grad is the same callable under either objective)
             best, mp = -np.inf, None
             nrest = max(int(restarts), 1)
             last_error = None
@@ -563,6 +572,8 @@ class GPMCMC(ConsumersMixin):
                     continue
                 if info["logp"] > best:
                     best, mp, data = info["logp"], model.point_dict(q), info
+            if objective != "lml":
+                gp.set_objective("lml")
             if mp is None:
                 raise RuntimeError("find_MAP failed in every restart") from last_error
             if self.verbose:

@@ -310,7 +310,7 @@ MI_GP_API int mi_gp_logpdf(mi_gp_handle* h, const double* Xnew_dev, const double
  *   mi_gp_kfold_work  doubles of work_dev for P = folds_per_pass and total_idx = fold_ptr_host[nfolds]: per fold two 128 x 128
  *                blocks and the gathered alpha_I / y_I (2 * 16384 + 256), plus 2 * total_idx + 2 for the staged index lists
  *                and the folds' bad-pivot words; -1 for folds_per_pass < 1 or total_idx < 1.
- * Out of scope: gradients w.r.t. theta; folds of more than 128 points (they need a blocked factorisation of K^-1_II); the full
+ * Out of scope: gradients w.r.t. theta (the leave-one-out sum has one: option 48 of mi_gp_set_option); folds of more than 128 points (they need a blocked factorisation of K^-1_II); the full
  * Sigma_I; a batched (one theta per member) form; phase timers. */
 MI_GP_API long mi_gp_kfold_work(int folds_per_pass, long total_idx);
 MI_GP_API int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host, const int* fold_idx_host, double* work_dev,
@@ -388,6 +388,29 @@ MI_GP_API int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host,
  *      through the spin every device-side read and write of the evaluation is complete (that kernel writes nothing but the
  *      pinned result buffer) and only its retirement may be outstanding -- the handle's buffers may be read or overwritten
  *      from any stream, as after a synchronisation.  Same bits.
+ *   48 (not a tuning knob) the OBJECTIVE of mi_gp_lml_grad: 0 (default) the log marginal likelihood, 1 the leave-one-out log
+ *      predictive density of Rasmussen & Williams section 5.4.2, the criterion to fit hyper-parameters to when the kernel family is
+ *      misspecified.  With P = K^-1, p_i = P_ii and alpha = P y (marginal form, a per-point diagonal of mi_gp_set_diag included)
+ *          L_LOO = sum_i [ 1/2 log p_i - 1/2 alpha_i^2 / p_i - 1/2 log 2 pi ]     (the sum of mi_gp_kfold's singleton logp)
+ *          e_i = alpha_i / p_i,  s_i = sqrt((1 + alpha_i^2 / p_i) / p_i),  w = P e,  M = (P diag s)(P diag s)^T
+ *          dL_LOO/dtheta_k = 1/2 sum_ij [ (alpha_i w_j + w_i alpha_j) - M_ij ] dK_ij/dtheta_k.
+ *      Under 1, mi_gp_lml_grad runs the ordinary evaluation first (same launches, same schedule: K^-1 and alpha become resident
+ *      as always) and then, on the handle's stream, a tail of one lower-trapezoid GEMM with k = padded n (M, about the flops of
+ *      the evaluation in front of it, whatever ntheta is -- the forward form, R & W eq. 5.13, costs one N^3 product per
+ *      hyper-parameter) between four memory-bound kernels and the LML gradient's contraction kernel, which takes
+ *      M - (alpha w^T + w alpha^T) in the place of K^-1 and a zero vector in the place of alpha.  *lml_out = L_LOO, grad_out its
+ *      gradient in theta order (d/d jitter = d/d gv); the call returns with the stream synchronised; the same call in the same
+ *      state returns the same bits, and every element a launch of the tail reads is written earlier in the same call.  A bad
+ *      pivot of the factorisation is reported as under 0 (info > 0, -inf, zero gradient; no tail); a K^-1_ii that is not a
+ *      positive finite number -- rounding alone can produce one behind a successful factorisation -- returns i + 1, -inf and
+ *      a zero gradient.  K^-1 and alpha stay resident with their meaning: mi_gp_alpha, mi_gp_grad_x (the LML's data-side
+ *      gradients) and mi_gp_kfold work behind the call, mi_gp_lml_parts keeps the factorisation's logdet and quad.  K_dev and
+ *      Z_dev are the tail's scratch: their contents are unspecified afterwards, except that Z_dev holds zeros wherever the next
+ *      evaluation expects them (all of it is cleared).  No buffer is asked of the caller; the handle owns six vectors of padded
+ *      capacity (allocated by the first such call, re-sized by mi_gp_reserve).  mi_gp_lml_grad_batch returns -1 under 1 (no
+ *      batched form); mi_gp_lml, mi_gp_lml_batch, mi_gp_factor* and every other entry are not affected.  Setting the option
+ *      changes no resident state; values other than 0 / 1 return -1, and so does 1 in a build without the tail (the host-only
+ *      schedule-trace program).  Out of scope: k-fold gradients, data-side gradients of L_LOO, a batched or sharded form.
  * 8, 14, 16, 18, 19, 21, 26, 27, 30, 31, 38, 45 and 47 only change scheduling (bit-identical results); 20 moves tiles between the
  * two GEMM kernels (same k order); 2, 4-7, 9, 32, 35, 37 and 46 regroup sums (agreement to rounding), and so does 0 where it changes
  * the super-panel width (20 to 60 tile columns).
