@@ -198,6 +198,25 @@ class MiGP:
         finally:
             self.set_option(48, before)
 
+    def set_cv_block(self, b):
+        """The fold size of the objective "loo" (option 49 of mi_gp_set_option): 1, leave-one-out, or 2..128, the leave-block-out
+        log predictive density sum_f log p(y_I_f | y_-I_f) over the contiguous folds I_f = [f b, min((f + 1) b, n)) -- the sum of
+        ``kfold``'s logp over these folds -- with its exact theta gradient.  No effect under the objective "lml"."""
+        self.set_option(49, int(b))
+
+    def cv_grad(self, theta, block):
+        """(L_CV, dL_CV/dtheta) at natural-scale theta over contiguous folds of ``block`` points, whatever objective and fold size
+        are set (they are the same afterwards); (-inf, zeros) if K or a fold's block of K^-1 is not positive definite (``info``:
+        the 1-based index of the point at the bad pivot)."""
+        before = self.get_option(48), self.get_option(49)
+        self.set_option(49, int(block))
+        try:
+            self.set_option(48, 1)
+            return self.lml_grad(theta)
+        finally:
+            self.set_option(48, before[0])
+            self.set_option(49, before[1])
+
     # ------------------------------------------------------------------ batched evaluation
     def _ensure_batch(self, k, need_grad):
         """Device buffers for k problems in lockstep (mi_gp_set_batch): K (+ Z, W for the gradient) as ONE tensor each."""

@@ -65,6 +65,7 @@ static void release_handle(mi_gp_handle* h) {
   free_scratch(h->one);
   free_scratch(h->batch);
   (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev); (void)hipFree(h->loo_vec_dev);
+  (void)hipFree(h->cv_dev);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -149,6 +150,7 @@ static void special_defaults(mi_gp_handle* h) {
   h->w_thr[0] = 1 << 20; h->w_thr[1] = 0; h->w_thr[2] = 0;
   h->use_smo = 2;  // (0 where the driver lacks stream memory operations: mi_gp_create)
   h->spin_us = 2000;
+  h->cv_block = 1;
 }
 
 // The options with behaviour beyond a clamp; `set` (or nullptr) is the new value, `get` (or nullptr) receives the current one.
@@ -204,6 +206,21 @@ static int special_option(mi_gp_handle* h, int what, const int* set, int* get) {
         h->objective = *set;
       } else {
         *get = h->objective;
+      }
+      return 1;
+    case 49:  // the fold size of the objective under option 48 = 1 (no resident state changes with it)
+      if (set) {
+        if (*set < 1 || *set > 128) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 49 is a fold size of 1 (leave-one-out) to 128 points, got %d", *set);
+          return -1;
+        }
+        if (*set != 1 && !loo_objective) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the k-fold objective (option 49 > 1) is not part of this build");
+          return -1;
+        }
+        h->cv_block = *set;
+      } else {
+        *get = h->cv_block;
       }
       return 1;
   }
@@ -912,6 +929,16 @@ hipError_t size_loo_vectors(mi_gp_handle* h, int cap) {
   return e;
 }
 
+// The scratch of the k-fold objective's fold pass (cv_scratch(), gp_handle.h): every element is written before it is read
+hipError_t size_cv_scratch(mi_gp_handle* h, int cap) {
+  (void)hipFree(h->cv_dev);
+  h->cv_dev = nullptr;
+  h->cv_cap = 0;
+  const hipError_t e = hipMalloc(&h->cv_dev, sizeof(double) * cv_scratch_len(cap));
+  if (e == hipSuccess) h->cv_cap = cap;
+  return e;
+}
+
 // ---------------------------------------------------------------- appending points at fixed theta
 // The handle's n-dependent scratch for up to `capacity` points; the resident contents (leaf inverses, alpha) are kept.
 extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
@@ -942,6 +969,7 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   s.dinv_dev = dinv; s.alpha_dev = alpha; s.part_dev = part;
   h->cap = capacity;
   if (h->loo_vec_dev) HCK(size_loo_vectors(h, capacity), "mi_gp_reserve");
+  if (h->cv_dev) HCK(size_cv_scratch(h, capacity), "mi_gp_reserve");
   return 0;
 }
 

@@ -10,7 +10,45 @@
 // with k = np (np^3 flops, about what the evaluation in front of it costs) whatever ntheta is, where the forward form (R & W
 // eq. 5.13) costs one N^3 product per hyper-parameter.  B = P diag(s) goes to Z_dev as a full matrix, G' to the lower triangle of
 // K_dev: both are scratch between evaluations (the factor and U = L^-T are not resident after mi_gp_lml_grad).
+//
+// Option 49 = b > 1: the k-fold objective over the contiguous folds I_f = [f b, min((f + 1) b, n)), the sum of mi_gp_kfold's
+// logp over them.  With C = chol(P_II), M = C^-1, t = M alpha_I, tau = |t|^2 (mi_gp_kfold's quantities) and Sigma_I = M^T M
+//   L_CV = sum_f [ -1/2 tau_f + sum_i log C_ii - |I_f|/2 log 2 pi ]
+//   dL_CV/dP_II = 1/2 (e e^T + Sigma_I) = 1/2 R R^T,   dL_CV/dalpha_I = -e_I,   e_I = M^T t,   R = M^T + e t^T / (1 + sqrt(1 + tau))
+// (R is M^T times the symmetric square root of I + t t^T: no second factorisation).  diag(s) becomes blockdiag(R_f),
+// B[:, I_f] = P[:, I_f] R_f, q_I = t / sqrt(1 + tau) so that R q = e and w = B q = P e -- and from B on the tail is the one above,
+// launch for launch.  b = 1 takes the leave-one-out path itself; b >= n is the log marginal likelihood by another route.
 #include "gp_handle.h"
+
+// The fold pass of option 49: mi_gp_kfold's gather and batched leaf over passes of the handle's scratch, then per fold t, e_I,
+// q_I, R_f and the logp (cv_fold_kernel); the folds' sum and the first bad index in one launch behind the last pass.  idx / ptr:
+// the caller's host lists, staged from here (they live until the caller synchronises the stream).
+static int cv_fold_pass(mi_gp_handle* h, int b, std::vector<int>& idx, std::vector<int>& ptr, double* e, double* q, double* scal) {
+  const int n = h->n;
+  const hipStream_t st = h->stream;
+  if (!h->cv_dev || h->cv_cap < h->cap) HCK(size_cv_scratch(h, h->cap), "k-fold scratch");
+  const CvScratch c = cv_scratch(h);
+  const int nfolds = (n + b - 1) / b;
+  idx.resize(n);
+  ptr.resize(nfolds + 1);
+  for (int i = 0; i < n; ++i) idx[i] = i;
+  for (int f = 0; f <= nfolds; ++f) ptr[f] = f * b < n ? f * b : n;
+  HCK(hipMemcpyAsync(c.idx, idx.data(), sizeof(int) * n, hipMemcpyHostToDevice, st), "index upload");
+  HCK(hipMemcpyAsync(c.ptr, ptr.data(), sizeof(int) * (nfolds + 1), hipMemcpyHostToDevice, st), "fold upload");
+  for (int f0 = 0; f0 < nfolds; f0 += c.pass) {
+    const int nf = nfolds - f0 < c.pass ? nfolds - f0 : c.pass;
+    Batch bt;
+    bt.nb = nf;
+    bt.sK = bt.sdinv = MINV_ELEMS;
+    bt.sinfo = 1;
+    HCK(launch_kfold_gather(h->buf.W_dev, h->buf.lda, h->one.alpha_dev, h->buf.y_dev, c.idx, c.ptr, f0, nf, c.blocks, c.vecs, c.info,
+                            st), "kfold_gather");
+    HCK(launch_potrf_leaf128(c.blocks, 128, c.minv, 0, c.info + f0, st, nullptr, &bt), "k-fold leaf");
+    HCK(launch_cv_fold(c.blocks, c.minv, c.vecs, c.ptr, c.info, f0, nf, c.flogp, e, q, c.R, st), "cv_fold");
+  }
+  HCK(launch_cv_reduce(c.flogp, c.ptr, c.info, nfolds, scal, st), "cv_reduce");
+  return 0;
+}
 
 int loo_objective(mi_gp_handle* h, double* value, double* grad) {
   const int n = h->n, np = h->np;
@@ -25,8 +63,15 @@ int loo_objective(mi_gp_handle* h, double* value, double* grad) {
   const double *P = h->buf.W_dev, *alpha = h->one.alpha_dev;
   double *B = h->buf.Z_dev, *G = h->buf.K_dev;
   h->have_u = false;  // (Z_dev is this call's scratch)
-  HCK(launch_loo_weights(P, ld, alpha, n, e, s, q, logp, scal, st), "loo_weights");
-  HCK(launch_loo_scale_mirror(P, ld, s, n, np, B, ld, st), "loo_scale_mirror");
+  std::vector<int> fold_idx, fold_ptr;  // (the staged lists of option 49: alive until the stream is synchronised)
+  if (h->cv_block > 1) {
+    const int r = cv_fold_pass(h, h->cv_block, fold_idx, fold_ptr, e, q, scal);
+    if (r != 0) return r;
+    HCK(launch_cv_mirror_multiply(P, ld, cv_scratch(h).R, h->cv_block, n, np, B, ld, st), "cv_mirror_multiply");
+  } else {
+    HCK(launch_loo_weights(P, ld, alpha, n, e, s, q, logp, scal, st), "loo_weights");
+    HCK(launch_loo_scale_mirror(P, ld, s, n, np, B, ld, st), "loo_scale_mirror");
+  }
   HCK(launch_loo_gemv(B, ld, q, n, w, st), "loo_gemv");
   HCK(launch_loo_rank2_init(alpha, w, n, np, G, ld, st), "loo_rank2_init");
   // G' += B B^T over the lower tiles (the padding rows and columns of B are zero: so is the padding of G')

@@ -121,6 +121,11 @@ struct mi_gp_handle {
   double* loo_vec_dev;     // [LOO_VECS][padded loo_cap] e, s, q, w, the zero vector and the per-point logp, then [8] scalars
                            // (allocated by the first evaluation under option 48 = 1; mi_gp_reserve drops it, the next one re-sizes it)
   int loo_cap;             // points loo_vec_dev is sized for
+  int cv_block;            // option 49: the fold size b of the objective under option 48 = 1 -- 1 (default) leave-one-out, 2..128 the
+                           // leave-block-out density over the contiguous folds [f b, min((f + 1) b, n))
+  double* cv_dev;          // the fold pass of that objective (CvScratch; allocated by the first evaluation with b > 1, re-sized like
+                           // loo_vec_dev)
+  int cv_cap;              // points cv_dev is sized for
   char err[256];
 };
 
@@ -205,9 +210,40 @@ int conditional_block(mi_gp_handle* h, const double* Xnew_dev, const double* yne
 // the handle's vectors of the leave-one-out objective for up to cap points (zeroed; what they held is not kept)
 constexpr int LOO_VECS = 6;
 hipError_t size_loo_vectors(mi_gp_handle* h, int cap);
+// The handle's scratch of the k-fold objective's fold pass for up to cap points, as mi_gp_kfold lays a work block out: `pass`
+// gathered blocks, `pass` leaf inverses and `pass` x 256 gathered vectors (pass = the folds of one pass: no result depends on it),
+// then R [padded cap][128], the per-fold logp [padded cap] and as ints the contiguous index list, the fold pointers and one
+// bad-pivot word per fold.  What it held is not kept.
+struct CvScratch {
+  int pass;
+  double *blocks, *minv, *vecs, *R, *flogp;
+  int *idx, *ptr, *info;
+};
+constexpr int CV_PASS_MAX = 128;
+inline int cv_pass(int cap) { return cap / 2 + 1 < CV_PASS_MAX ? cap / 2 + 1 : CV_PASS_MAX; }  // (folds of two points or more)
+inline size_t cv_scratch_len(int cap) {
+  const size_t vl = (size_t)(cap + 127) / 128 * 128;
+  return (size_t)cv_pass(cap) * (2 * MINV_ELEMS + 256) + vl * 128 + vl + 2 * vl + 2;
+}
+inline CvScratch cv_scratch(const mi_gp_handle* h) {
+  const long vl = (h->cv_cap + 127) / 128 * 128, P = cv_pass(h->cv_cap);
+  CvScratch c;
+  c.pass = (int)P;
+  c.blocks = h->cv_dev;
+  c.minv = c.blocks + P * MINV_ELEMS;
+  c.vecs = c.minv + P * MINV_ELEMS;
+  c.R = c.vecs + P * 256;
+  c.flogp = c.R + vl * 128;
+  c.idx = reinterpret_cast<int*>(c.flogp + vl);
+  c.ptr = c.idx + vl;
+  c.info = c.ptr + vl + 1;
+  return c;
+}
+hipError_t size_cv_scratch(mi_gp_handle* h, int cap);
 
 // api_loo.hip: the tail of mi_gp_lml_grad under option 48 = 1, behind a successful ordinary evaluation (K^-1 in W_dev, alpha
 // resident).  *value = L_LOO and grad[ntheta] its gradient; 0, the 1-based index of the first bad K^-1_ii (-inf, zero gradient) or
-// a C-ABI error code.  Weak: api_gp.hip also links without it (the host-only schedule-trace program), and option 48 = 1 is
-// refused there.
+// a C-ABI error code.  Under option 49 = b > 1 the k-fold objective over the contiguous folds of b points instead (the same tail
+// behind another B; the return value is then the index of the point at the bad pivot of a fold's block).  Weak: api_gp.hip also
+// links without it (the host-only schedule-trace program), and option 48 = 1 and option 49 > 1 are refused there.
 int loo_objective(mi_gp_handle* h, double* value, double* grad) __attribute__((weak));

@@ -8,8 +8,6 @@
 
 namespace migp {
 
-constexpr double KFOLD_LOG_2PI = 1.8378770664093453;
-
 // Workgroup (f, g): rows 16 g .. 16 g + 15 of fold f0 + f's block: element (a, b) = W[max(i_a, i_b)][min(i_a, i_b)] -- never the
 // strict upper triangle of W, which is scratch -- and the identity in the padding.  Group 0 also gathers alpha_I and y_I (zeros in
 // the padding) and resets the fold's bad-pivot word.
@@ -43,8 +41,9 @@ __global__ __launch_bounds__(256) void kfold_gather_kernel(const double* __restr
 
 // One workgroup per fold, thread j = position j of the fold.  With C = chol(K^-1_II) in the fold's block and M = C^-1 in minv
 // (minv_index order; only the lower triangle is read): t = M alpha_I, r = M^T t = Sigma_I alpha_I, mean = y_I - r,
-// var_j = sum_r M[r][j]^2, logp = -1/2 |t|^2 + sum log C_ii - |I|/2 log 2 pi.  Every sum runs in a fixed order.  A fold whose
-// block was not positive definite gets logp = -inf and NaN moments.
+// var_j = sum_r M[r][j]^2, logp = -1/2 |t|^2 + sum log C_ii - |I|/2 log 2 pi (kfold_fold_logp, migp_kernels.h: the k-fold
+// objective's fold kernel returns the same bits through it).  Every sum runs in a fixed order.  A fold whose block was not
+// positive definite gets logp = -inf and NaN moments.
 __global__ __launch_bounds__(128) void kfold_moments_kernel(const double* __restrict__ blocks, const double* __restrict__ minv,
                                                             const double* __restrict__ vecs, const int* __restrict__ ptr,
                                                             const int* __restrict__ info, int f0, double* __restrict__ logp,
@@ -60,13 +59,7 @@ __global__ __launch_bounds__(128) void kfold_moments_kernel(const double* __rest
   const double* M = minv + (long)f * MINV_ELEMS;
   const double* al = vecs + (long)f * 256;
   __shared__ double tv[128], s1[128], s2[128];
-  double t = 0.0;
-  if (j < s)
-    for (int c = 0; c <= j; ++c) t = __builtin_fma(M[minv_index(j, c)], al[c], t);
-  tv[j] = t;
-  s1[j] = j < s ? log(C[j * 129]) : 0.0;
-  s2[j] = t * t;
-  __syncthreads();
+  const double lp = kfold_fold_logp(C, M, al, j, s, tv, s1, s2);
   if (mean != nullptr && j < s) {
     double r = 0.0, v = 0.0;
     for (int i = j; i < s; ++i) {
@@ -77,11 +70,7 @@ __global__ __launch_bounds__(128) void kfold_moments_kernel(const double* __rest
     mean[p0 + j] = al[128 + j] - r;
     var[p0 + j] = v;
   }
-  for (int w = 64; w > 0; w >>= 1) {
-    if (j < w) { s1[j] += s1[j + w]; s2[j] += s2[j + w]; }
-    __syncthreads();
-  }
-  if (j == 0) logp[f0 + f] = -0.5 * s2[0] + s1[0] - 0.5 * (double)s * KFOLD_LOG_2PI;
+  if (j == 0) logp[f0 + f] = lp;
 }
 
 // Leave-one-out, fold f = the point i = idx[f]: with k = K^-1_ii, var = 1 / k, mean = y_i - alpha_i / k,

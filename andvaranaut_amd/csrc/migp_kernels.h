@@ -283,6 +283,41 @@ hipError_t launch_kfold_moments(const double* blocks, const double* minv, const 
 // every fold one point: the closed form, info[f] = 0 or 1
 hipError_t launch_kfold_loo(const double* W, long ld, const double* alpha, const double* y, const int* idx, int nfolds, double* logp,
                             double* mean, double* var, int* info, hipStream_t stream);
+// The density of one fold, shared by kfold_moments_kernel and cv_fold_kernel (cvobj_f64.hip) so that both return the same bits:
+// a workgroup of 128 threads, thread j = position j of a fold of s points, C = chol(K^-1_II) row-major, M = C^-1 in minv_index
+// order, al = alpha_I.  tv / s1 / s2: 128 doubles of LDS each.  Returns logp on every thread; afterwards tv holds t = M alpha_I
+// (zeros from s on) and s2[0] = |t|^2.  Every sum runs in a fixed order.
+constexpr double KFOLD_LOG_2PI = 1.8378770664093453;
+__device__ __forceinline__ double kfold_fold_logp(const double* __restrict__ C, const double* __restrict__ M,
+                                                  const double* __restrict__ al, int j, int s, double* tv, double* s1, double* s2) {
+  double t = 0.0;
+  if (j < s)
+    for (int c = 0; c <= j; ++c) t = __builtin_fma(M[minv_index(j, c)], al[c], t);
+  tv[j] = t;
+  s1[j] = j < s ? log(C[j * 129]) : 0.0;
+  s2[j] = t * t;
+  __syncthreads();
+  for (int w = 64; w > 0; w >>= 1) {
+    if (j < w) { s1[j] += s1[j + w]; s2[j] += s2[j + w]; }
+    __syncthreads();
+  }
+  return -0.5 * s2[0] + s1[0] - 0.5 * (double)s * KFOLD_LOG_2PI;
+}
+
+// ---------------------------------------------------------------- cvobj_f64.hip (option 49: the k-fold objective, api_loo.hip)
+// behind the leaf of a pass (launch_kfold_gather's layout; ptr = the contiguous folds): per fold t = M alpha_I, tau = |t|^2,
+// e_I = M^T t, q_I = t / sqrt(1 + tau) and the rows of R = M^T + e t^T / (1 + sqrt(1 + tau)) at the fold's points -- e[i], q[i],
+// R[i * 128 + 0 .. 127] (zeros from the fold's size on) -- and flogp[f0 + f], mi_gp_kfold's logp of the fold.  A fold whose word
+// is not INFO_OK: -inf and zeros
+hipError_t launch_cv_fold(const double* blocks, const double* minv, const double* vecs, const int* ptr, const int* info, int f0,
+                          int nf, double* flogp, double* e, double* q, double* R, hipStream_t stream);
+// scal[0] = sum_f flogp[f] in a fixed order, scal[1] = the smallest ptr[f] + info[f] over the folds whose word is not INFO_OK
+// (the 1-based index of the point at the bad pivot; 0: none)
+hipError_t launch_cv_reduce(const double* flogp, const int* ptr, const int* info, int nfolds, double* scal, hipStream_t stream);
+// B[:, I_f] = Pfull[:, I_f] R_f for the folds I_f = [f b, min((f + 1) b, n)): Pfull[i][j] = W[max(i, j)][min(i, j)] (the LOWER
+// triangle of W alone), R as launch_cv_fold left it; the full np x np matrix, zeros in the rows and columns from n on
+hipError_t launch_cv_mirror_multiply(const double* W, long ldw, const double* R, int b, int n, int np, double* B, long ldb,
+                                     hipStream_t stream);
 
 // ---------------------------------------------------------------- loo_f64.hip (option 48: the leave-one-out objective, api_loo.hip)
 // From P = K^-1 (LOWER triangle of W) and alpha: logp[i] (mi_gp_kfold's singleton density), e[i] = alpha_i / p_i,

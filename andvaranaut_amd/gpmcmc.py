@@ -415,19 +415,43 @@ class GPMCMC(ConsumersMixin):
 
     # ------------------------------------------------------------------ fit
     def fit(self, method="map", return_data=False, iwgp=False, cwgp=False, jitter=1e-6, truncate=False,
-            restarts=1, objective="lml", **kwargs):
+            restarts=1, objective="lml", nfolds=10, fold_seed=None, **kwargs):
         """gpmcmc.py:175-182.  ``objective="loo"`` (with ``method="map"``) maximises the leave-one-out log predictive density
         sum_i log p(y_i | y_-i) plus the priors instead of the log marginal likelihood (Rasmussen & Williams section 5.4.2: the
         criterion for a misspecified kernel family); the hyper-parameters are stored as a MAP fit stores them.  It has no
-        sampler (a pseudo-likelihood) and no warps (their data-side gradients are the marginal likelihood's)."""
-        if objective not in MiGP.OBJECTIVES:
-            raise ValueError(f"objective must be one of {list(MiGP.OBJECTIVES)}")
+        sampler (a pseudo-likelihood) and no warps (their data-side gradients are the marginal likelihood's).
+        ``objective="kfold"`` maximises the k-fold log predictive density sum_f log p(y_I_f | y_-I_f) plus the priors under the
+        same conditions: the remedy where points cluster and every left-out point is predicted by its twin.  The folds are a
+        random partition, ``np.random.default_rng(fold_seed).permutation`` cut into blocks of b = ceil(n / nfolds) points (the
+        last fold may be smaller; a fold holds at most 128 points); ``return_data`` carries them as ``data["folds"]``, index
+        arrays into the data as given, for ``cv_stats(folds=...)``."""
+        cv = None
+        if objective == "kfold":
+            cv = self._kfold_plan(method, iwgp, cwgp, nfolds, fold_seed)
+        elif objective not in MiGP.OBJECTIVES:
+            raise ValueError(f"objective must be one of {list(MiGP.OBJECTIVES) + ['kfold']}")
         if objective == "loo" and (method != "map" or iwgp or cwgp):
             raise ValueError("objective='loo' needs method='map' and neither iwgp nor cwgp")
         self.m, self.gp, self.hypers, data = self.__fit(self.x, self.y - self.ym, method, iwgp, cwgp, jitter,
-                                                        truncate, restarts, objective=objective, **kwargs)
+                                                        truncate, restarts, objective=objective, cv=cv, **kwargs)
         if return_data:
             return data
+
+    def _kfold_plan(self, method, iwgp, cwgp, nfolds, fold_seed):
+        """(b, permutation) of a fit on the k-fold objective: the fit's handle holds the data in the order of the permutation,
+        where the folds are the contiguous blocks of b points.  Every refusal is raised here, before any device call."""
+        if method != "map" or iwgp or cwgp:
+            raise ValueError("objective='kfold' needs method='map' and neither iwgp nor cwgp")
+        n = len(self.x)
+        if isinstance(nfolds, bool) or not isinstance(nfolds, (int, np.integer)) or nfolds < 2:
+            raise ValueError(f"objective='kfold' needs an integer nfolds >= 2 (got {nfolds!r})")
+        if nfolds > n:
+            raise ValueError(f"objective='kfold': nfolds = {nfolds} exceeds the {n} points")
+        b = -(-n // int(nfolds))
+        if b > 128:
+            raise ValueError(f"objective='kfold': {nfolds} folds of {n} points hold {b} points each and a fold holds at most 128, "
+                             f"so the smallest admissible nfolds is {-(-n // 128)}")
+        return b, np.random.default_rng(fold_seed).permutation(n)
 
     def _converted(self, x, y):
         xin = np.zeros_like(x)
@@ -536,7 +560,7 @@ class GPMCMC(ConsumersMixin):
 
         return likelihood
 
-    def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", **kwargs):
+    def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", cv=None, **kwargs):
         n_i, n_pos, n_free = self._warp_sizes(iwgp, cwgp)
         model = HyperModel(self.nx, self.kerns, noise=self.noise, truncate=truncate, jitter=jitter, n_iwgp=n_i,
                            n_cwgp_pos=n_pos, n_cwgp=n_free)
@@ -548,7 +572,16 @@ class GPMCMC(ConsumersMixin):
         fun_map = lambda q: model.logp_dlogp(q, gp.lml_grad, jacobian=False, likelihood=lik)  # noqa: E731
         data = None
         if method == "map":
-            if objective != "lml":
+            fit_gp = None
+            if cv is not None:
+                # the k-fold objective: a handle of its own for the fit, on the permuted data; `gp`, the handle that is stored,
+                # keeps the data's order and the ordinary objective
+                b, perm = cv
+                fit_gp = MiGP(np.ascontiguousarray(xin[perm]), np.ascontiguousarray(yin[perm]), self.kernel, device=self.device)
+                fit_gp.set_objective("loo")
+                fit_gp.set_cv_block(b)
+                fun_map = lambda q: model.logp_dlogp(q, fit_gp.lml_grad, jacobian=False)  # noqa: E731
+            elif objective != "lml":
                 gp.set_objective(objective)  # (gp.lml_grad is the same callable under either objective)
             best, mp = -np.inf, None
             nrest = max(int(restarts), 1)
@@ -572,7 +605,11 @@ class GPMCMC(ConsumersMixin):
                     continue
                 if info["logp"] > best:
                     best, mp, data = info["logp"], model.point_dict(q), info
-            if objective != "lml":
+            if fit_gp is not None:
+                fit_gp.close()
+                if data is not None:
+                    data["folds"] = [perm[a : a + b].copy() for a in range(0, len(perm), b)]
+            elif objective != "lml":
                 gp.set_objective("lml")
             if mp is None:
                 raise RuntimeError("find_MAP failed in every restart") from last_error

@@ -310,7 +310,7 @@ MI_GP_API int mi_gp_logpdf(mi_gp_handle* h, const double* Xnew_dev, const double
  *   mi_gp_kfold_work  doubles of work_dev for P = folds_per_pass and total_idx = fold_ptr_host[nfolds]: per fold two 128 x 128
  *                blocks and the gathered alpha_I / y_I (2 * 16384 + 256), plus 2 * total_idx + 2 for the staged index lists
  *                and the folds' bad-pivot words; -1 for folds_per_pass < 1 or total_idx < 1.
- * Out of scope: gradients w.r.t. theta (the leave-one-out sum has one: option 48 of mi_gp_set_option); folds of more than 128 points (they need a blocked factorisation of K^-1_II); the full
+ * Out of scope: gradients w.r.t. theta (the sum over leave-one-out or contiguous folds has one: options 48 and 49 of mi_gp_set_option); folds of more than 128 points (they need a blocked factorisation of K^-1_II); the full
  * Sigma_I; a batched (one theta per member) form; phase timers. */
 MI_GP_API long mi_gp_kfold_work(int folds_per_pass, long total_idx);
 MI_GP_API int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host, const int* fold_idx_host, double* work_dev,
@@ -410,7 +410,33 @@ MI_GP_API int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host,
  *      capacity (allocated by the first such call, re-sized by mi_gp_reserve).  mi_gp_lml_grad_batch returns -1 under 1 (no
  *      batched form); mi_gp_lml, mi_gp_lml_batch, mi_gp_factor* and every other entry are not affected.  Setting the option
  *      changes no resident state; values other than 0 / 1 return -1, and so does 1 in a build without the tail (the host-only
- *      schedule-trace program).  Out of scope: k-fold gradients, data-side gradients of L_LOO, a batched or sharded form.
+ *      schedule-trace program).  Out of scope: data-side gradients of L_LOO, a batched or sharded form (k-fold gradients: option 49).
+ *   49 (not a tuning knob) the FOLD SIZE b of the cross-validation objective that mi_gp_lml_grad returns under option 48 = 1:
+ *      1 (default) is leave-one-out as described there, with the bits it has without this option; 2..128 give the
+ *      leave-block-out log predictive density over the contiguous folds I_f = [f b, min((f + 1) b, n)) -- the last fold may be
+ *      smaller, down to one point; b >= n is one fold, and L_CV the log marginal likelihood.  With P = K^-1 and alpha = P y as
+ *      under option 48, and per fold C = chol(P_II), M = C^-1, t = M alpha_I, tau = |t|^2 (mi_gp_kfold's quantities)
+ *          L_CV = sum_f [ -1/2 tau_f + sum_i log C_ii - |I_f|/2 log 2 pi ]        (the sum of mi_gp_kfold's logp over these folds:
+ *                                                                                  a fold's logp has mi_gp_kfold's bits)
+ *          e_I = M^T t  (= Sigma_I alpha_I, Sigma_I = P_II^-1 = M^T M),   dL_CV/dP_II = 1/2 (e e^T + Sigma_I) = 1/2 R R^T,
+ *          R = M^T + c e t^T,  c = 1 / (1 + sqrt(1 + tau)),   q_I = t / sqrt(1 + tau)  (R q = e)
+ *          B[:, I_f] = P[:, I_f] R_f,  w = B q = P e,   dL_CV/dtheta_k = -1/2 sum_ij G'_ij dK_ij/dtheta_k,
+ *          G' = B B^T - (alpha w^T + w alpha^T):
+ *      option 48's tail with diag(s) replaced by the block-diagonal matrix of the folds' R_f.  In front of the tail's GEMM run,
+ *      per pass of up to 128 folds, mi_gp_kfold's gather and batched 128 x 128 leaf and one kernel that forms t, e, q, R and the
+ *      fold's logp, then a fixed-order reduction over the folds and one multiply B = P blockdiag(R_f) on the fp64 matrix cores
+ *      (2 * 128 * padded n * n flops, from the lower triangle of W_dev alone) in the place of the scaling by s; the number of
+ *      folds per pass changes no result.  *lml_out = L_CV, grad_out its gradient in theta order (d/d jitter = d/d gv).
+ *      Every contract of option 48 carries over: the ordinary evaluation runs first with the same launches; K^-1 and alpha stay
+ *      resident with their meaning (mi_gp_alpha, mi_gp_grad_x, mi_gp_kfold, mi_gp_lml_parts); K_dev and Z_dev are scratch and
+ *      Z_dev is all zeros afterwards; the call returns with the stream synchronised; the same call in the same state returns the
+ *      same bits; every element a launch reads is written earlier in the same call; mi_gp_lml_grad_batch stays refused under
+ *      48 = 1.  A bad pivot of the factorisation is reported as under 48 = 0; a fold whose P_II is not positive definite returns
+ *      -inf, a zero gradient and the 1-based index of the point at the bad pivot (the smallest over the folds).  The handle owns
+ *      the scratch of a pass (allocated by the first such call, re-sized by mi_gp_reserve, freed by mi_gp_destroy).  Setting the
+ *      option changes no resident state and has no effect at all under 48 = 0; values outside 1..128 return -1, and so does a
+ *      value other than 1 in a build without the tail.  Out of scope: arbitrary index sets (permute the data: the contiguous
+ *      folds of a random permutation are random folds), folds of more than 128 points, a batched or sharded form.
  * 8, 14, 16, 18, 19, 21, 26, 27, 30, 31, 38, 45 and 47 only change scheduling (bit-identical results); 20 moves tiles between the
  * two GEMM kernels (same k order); 2, 4-7, 9, 32, 35, 37 and 46 regroup sums (agreement to rounding), and so does 0 where it changes
  * the super-panel width (20 to 60 tile columns).
