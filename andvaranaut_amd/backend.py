@@ -149,6 +149,7 @@ class MiGP:
 
     def lml(self, theta):
         """LML at natural-scale theta; -inf if K is not positive definite (info > 0)."""
+        self._no_trend("lml")
         theta, tp = self._theta(theta)
         out = ctypes.c_double()
         self._factored_ok = False
@@ -167,6 +168,8 @@ class MiGP:
         """(LML, dLML/dtheta) at natural-scale theta; (-inf, zeros) if K is not positive definite."""
         if self.Z_t is None:
             raise RuntimeError("this MiGP was created with need_grad=False")
+        if self._trend != 0 and self.get_option(48) == 1:
+            self._no_trend("a cross-validation objective")
         theta, tp = self._theta(theta)
         out = ctypes.c_double()
         grad = np.zeros(self.ntheta)
@@ -187,6 +190,30 @@ class MiGP:
         if objective not in self.OBJECTIVES:
             raise ValueError(f"objective must be one of {list(self.OBJECTIVES)}")
         self.set_option(48, self.OBJECTIVES[objective])
+
+    TRENDS = {"none": 0, "constant": 1, "linear": 2}
+
+    def set_trend(self, name):
+        """The prior mean of the model (option 50 of mi_gp_set_option): "none", zero; "constant", h(x) = [1]; "linear",
+        h(x) = [1, x_1 .. x_d] (d <= 127).  The coefficients carry a vague prior and are integrated out in closed form (Rasmussen &
+        Williams section 2.7): theta keeps its layout.  lml_grad then returns the trend's marginal likelihood (eq. 2.45) and its
+        exact theta gradient, factor + predict the trend's conditional (eqs. 2.41-2.42); every other evaluation raises
+        ValueError until the trend is "none" again.  A change ends the resident factorisation."""
+        if name not in self.TRENDS:
+            raise ValueError(f"trend must be one of {list(self.TRENDS)}")
+        if self.TRENDS[name] != self._trend:
+            self.set_option(50, self.TRENDS[name])
+            self._trend = self.TRENDS[name]
+            self._factored_ok = False
+            self._u_theta_ok = False
+
+    _trend = 0
+
+    def _no_trend(self, what):
+        """Raised before the call by everything that has no form under a trend."""
+        if self._trend != 0:
+            name = [k for k, v in self.TRENDS.items() if v == self._trend][0]
+            raise ValueError(f"{what} has no form under a trend (set_trend({name!r}) is in force): set_trend('none') first")
 
     def loo_grad(self, theta):
         """(L_LOO, dL_LOO/dtheta) at natural-scale theta, whatever objective is set (it is the same afterwards); (-inf, zeros)
@@ -252,6 +279,7 @@ class MiGP:
         """LML at k hyper-parameter vectors of the same data in ONE lockstep evaluation (mi_gp_lml_batch): every launch
         carries blockIdx.z = problem.  Returns (k,) values, -inf where the covariance is not positive definite; the
         values are those lml() returns one at a time."""
+        self._no_trend("lml_batch")
         th = self._thetas(thetas)
         k = th.shape[0]
         self._ensure_batch(k, False)
@@ -269,6 +297,7 @@ class MiGP:
     def lml_grad_batch(self, thetas):
         """(LML (k,), dLML/dtheta (k, ntheta)) at k hyper-parameter vectors in one lockstep evaluation
         (mi_gp_lml_grad_batch); rows of non-positive-definite problems are (-inf, zeros)."""
+        self._no_trend("lml_grad_batch")
         th = self._thetas(thetas)
         k = th.shape[0]
         self._ensure_batch(k, True)
@@ -289,6 +318,7 @@ class MiGP:
         """Factorise k covariances in the conditional form (mi_gp_factor_batch), one theta each, in one lockstep evaluation.
         Returns the (k,) info array (0, or the 1-based first bad pivot).  The factors stay in the batch buffers for
         predict_batch; the single-evaluation factor is gone, so a later predict() refactorises."""
+        self._no_trend("factor_batch")
         th = self._thetas(thetas)
         k = th.shape[0]
         self._ensure_batch(k, False)
@@ -322,6 +352,7 @@ class MiGP:
         ``max_batch``) and over points by ``chunk``.  Returns (means[k, m], vars[k, m]) and, with ``mixture``, also the
         equal-weight mixture (mix_mean[m], mix_var[m]) over the positive-definite draws: each draw-chunk's mixture
         comes from the device, chunks are combined here in chunk order (law of total variance)."""
+        self._no_trend("predict_batch")
         th = self._thetas(thetas)
         k = th.shape[0]
         Xnew = np.ascontiguousarray(Xnew, dtype=np.float64)
@@ -381,6 +412,7 @@ class MiGP:
     def lml_grad_data(self, theta, want_x=True):
         """(LML, dLML/dtheta, dLML/dy, dLML/dX) -- the data-side gradients drive the chain rule through
         warps (cwgp / iwgp) and free input rows (inverse_opt).  dLML/dX is None unless want_x."""
+        self._no_trend("lml_grad_data")
         val, grad = self.lml_grad(theta)
         if not np.isfinite(val):
             return val, grad, np.zeros(self.n), (np.zeros((self.n, self.d)) if want_x else None)
@@ -471,6 +503,7 @@ class MiGP:
         buffers grow about 1.5x and the handle is refactorised once at the factored theta (``append_refactors`` counts
         these).  Returns 0, or the LAPACK-style info of a chunk whose block is not positive definite: that chunk and the
         ones after it are not appended (``self.n`` says how many points are resident), the factor stays usable."""
+        self._no_trend("append")
         Xnew = np.ascontiguousarray(np.atleast_2d(np.asarray(Xnew, dtype=np.float64)))
         ynew = np.ascontiguousarray(np.asarray(ynew, dtype=np.float64).reshape(-1))
         if Xnew.ndim != 2 or Xnew.shape[1] != self.d or Xnew.shape[0] != ynew.shape[0]:
@@ -519,6 +552,7 @@ class MiGP:
         (logp, dX [k, d], dy [k]); dX and dy are None with ``grad=False``.  Nothing is committed: the resident factor serves any
         number of trial sets.  ``diag``: the trial points' entries of the per-point diagonal, required exactly when one is
         set.  A trial block that is not positive definite gives (-inf, zeros, zeros), ``self.info`` its pivot."""
+        self._no_trend("logpdf")
         Xnew = np.ascontiguousarray(np.atleast_2d(np.asarray(Xnew, dtype=np.float64)))
         ynew = np.ascontiguousarray(np.asarray(ynew, dtype=np.float64).reshape(-1))
         if Xnew.ndim != 2 or Xnew.shape[1] != self.d or Xnew.shape[0] != ynew.shape[0]:
@@ -578,6 +612,7 @@ class MiGP:
         the fold's observations and ``info`` 0 or the 1-based position of the fold's first non-positive pivot (logp = -inf and
         NaN moments for that fold alone).  ``resident=True`` skips ``lml_grad(theta)``: K^-1 of the last ``lml_grad`` is used
         as it is (theta is ignored).  The hyper-parameters are the same for every fold: nothing is refitted."""
+        self._no_trend("kfold")
         if self.Z_t is None:
             raise RuntimeError("this MiGP was created with need_grad=False")
         if isinstance(folds, np.ndarray) and folds.ndim == 2 and folds.shape[0] > 0:
@@ -657,7 +692,12 @@ class MiGP:
         """Posterior mean and diagonal variance at Xnew (converted inputs), chunked over points.
         ``via_inverse``: use U = L^-T and one GEMM per chunk (mi_gp_predict_u) instead of the blocked triangular
         solve; default: when the gradient buffers exist and the sweep is large enough to pay for forming U
-        (or U is already resident from an earlier sweep at this theta)."""
+        (or U is already resident from an earlier sweep at this theta).  Under a trend (set_trend) the blocked solve is the only
+        route: ``via_inverse=True`` raises ValueError."""
+        if via_inverse:
+            self._no_trend("predict(via_inverse=True)")
+        if self._trend != 0:
+            via_inverse = False
         self._ensure_factored(theta)
         Xnew = np.ascontiguousarray(Xnew, dtype=np.float64)
         if Xnew.ndim != 2 or Xnew.shape[1] != self.d:
@@ -717,6 +757,7 @@ class MiGP:
         """Posterior mean / variance at a few points and their gradients w.r.t. the points:
         (mean[m], var[m], dmean[m,d], dvar[m,d]).  ``refactor=False`` reuses the resident factorisation
         (same theta as the previous predict / predict_grad call)."""
+        self._no_trend("predict_grad")
         if self.Z_t is None:
             raise RuntimeError("this MiGP was created with need_grad=False")
         if refactor:
@@ -799,6 +840,7 @@ class MiGP:
         -- Sigma = K(X*, X*) - A^T A with A = L^-1 K(X, X*), plus sqrt(gv)^2 I with pred_noise, else jitter I.  Returns
         (mu [M], cov [M, M]), cov symmetric (mirrored from the lower triangle the device computes); mu is predict()'s mean
         through the blocked solve, bit for bit."""
+        self._no_trend("predict_cov")
         self._ensure_factored(theta)
         mu_t, cov_t = self._joint_device(Xnew, pred_noise)
         m = mu_t.shape[0]
@@ -816,6 +858,7 @@ class MiGP:
         is not positive definite, it is rebuilt and factored again with an extra diagonal of 1e-12 kd, 1e-10 kd, ... up to
         1e-4 kd (kd the composite prior variance), then FloatingPointError.  ``self.sample_info`` records the seed, offset and
         extra jitter used."""
+        self._no_trend("sample_posterior")
         nsamples = int(nsamples)
         if nsamples < 1:
             raise ValueError("nsamples must be >= 1")

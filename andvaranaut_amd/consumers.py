@@ -246,6 +246,8 @@ class ConsumersMixin:
         ``method="TS"`` (Thompson sampling, beyond the reference): each proposal is the optimum of ONE joint posterior draw
         of the latent function over the ``predict_samps`` LHC candidates (GPMCMC.sample_posterior); only with
         opt_method="predict", and ``refine`` does not apply."""
+        if getattr(self, "trend", None) is not None:
+            raise ValueError(f"BO has no form under trend={self.trend!r}: fit without a trend to use it")
         if method == "TS" and opt_method != "predict":
             raise ValueError("method='TS' (Thompson sampling) takes one joint posterior draw over the predict_samps candidates: "
                              f"it needs opt_method='predict', not {opt_method!r}")
@@ -394,6 +396,8 @@ class ConsumersMixin:
         ``resident=True``: the N training rows are factorised ONCE and every potential evaluation is LML(N) + the joint log
         predictive density of the nobs observation rows (MiGP.logpdf): O(N^2) per step instead of O(N^3), the same
         potential to rounding."""
+        if getattr(self, "trend", None) is not None:
+            raise ValueError(f"inverse_opt has no form under trend={self.trend!r}: fit without a trend to use it")
         if self.m is None:
             raise Exception("Model must be fitted before running Bayesian optimisation")
         if self.verbose:

@@ -65,7 +65,7 @@ static void release_handle(mi_gp_handle* h) {
   free_scratch(h->one);
   free_scratch(h->batch);
   (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev); (void)hipFree(h->loo_vec_dev);
-  (void)hipFree(h->cv_dev);
+  (void)hipFree(h->cv_dev); (void)hipFree(h->trend_dev);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -221,6 +221,29 @@ static int special_option(mi_gp_handle* h, int what, const int* set, int* get) {
         h->cv_block = *set;
       } else {
         *get = h->cv_block;
+      }
+      return 1;
+    case 50:  // the TREND (a change ends the resident state as mi_gp_set_data does)
+      if (set) {
+        if (*set < 0 || *set > 2) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 50 is 0 (no trend), 1 (constant) or 2 (linear), got %d", *set);
+          return -1;
+        }
+        if (*set == 2 && h->cfg.d > 127) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the linear trend (option 50 = 2) needs d <= 127, got %d", h->cfg.d);
+          return -1;
+        }
+        if (*set != 0 && !(trend_objective && trend_factor && trend_predict_reduce)) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the trend (option 50 = %d) is not part of this build", *set);
+          return -1;
+        }
+        if (*set != h->trend) {
+          h->trend = *set;
+          h->factored = h->have_kinv = h->have_u = false;
+          h->b_cond_k = 0;
+        }
+      } else {
+        *get = h->trend;
       }
       return 1;
   }
@@ -448,6 +471,7 @@ static int factor_internal(mi_gp_handle* h, const double* theta, int what) {
 
 extern "C" int mi_gp_lml(mi_gp_handle* h, const double* theta, double* lml_out) {
   if (!h || !theta || !lml_out) return -1;
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_lml");
   const int r = factor_internal(h, theta, 0);
   if (r < 0) return r;
   if (r > 0) { *lml_out = -INFINITY; return r; }
@@ -481,6 +505,14 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
     snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad needs Z_dev and W_dev in mi_gp_set_data");
     return -1;
   }
+  if (h->trend != 0 && (h->objective == 1 || h->n <= trend_columns(h))) {
+    if (h->objective == 1)
+      snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad: no cross-validation objective (option 48 = 1) under a trend (option 50 = %d)", h->trend);
+    else
+      snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad: the trend (option 50 = %d) has %d coefficients, n = %d must exceed that", h->trend,
+               trend_columns(h), h->n);
+    return -1;
+  }
   // the gradient kernels run unconditionally behind the factorisation (one captured DAG); on a
   // non-positive-definite K their output is discarded
   const int r = factor_internal(h, theta, 2);
@@ -490,6 +522,11 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
   *lml_out = h->one.out_host[0];
   for (int i = 0; i < h->ntheta; ++i) grad_out[i] = h->one.grad_host[i];
   h->have_kinv = true;
+  // option 50 != 0: the same evaluation, then the trend's tail on the resident K^-1 and alpha (api_trend.hip); W_dev then holds P~
+  if (h->trend != 0) {
+    h->have_kinv = false;
+    return trend_objective(h, lml_out, grad_out);
+  }
   // option 48 = 1: the same evaluation, then the leave-one-out tail on the resident K^-1 and alpha (api_loo.hip)
   if (h->objective == 1) return loo_objective(h, lml_out, grad_out);
   return 0;
@@ -501,6 +538,7 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
 // (gpmcmc.py:1096-1101), which PyMC differentiates by autodiff through the same Cholesky.
 extern "C" int mi_gp_alpha(mi_gp_handle* h, double* alpha_host) {
   if (!h || !alpha_host) return -1;
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_alpha");
   if (!h->have_kinv) { snprintf(h->err, sizeof(h->err), "mi_gp_alpha: call mi_gp_lml_grad first"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
   HCK(hipMemcpyAsync(alpha_host, h->one.alpha_dev, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream), "alpha download");
@@ -510,6 +548,7 @@ extern "C" int mi_gp_alpha(mi_gp_handle* h, double* alpha_host) {
 
 extern "C" int mi_gp_grad_x(mi_gp_handle* h, double* gx_dev) {
   if (!h || !gx_dev) return -1;
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_grad_x");
   if (!h->have_kinv) { snprintf(h->err, sizeof(h->err), "mi_gp_grad_x: call mi_gp_lml_grad first"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
   const int nsplit = grad_x_splits(h->n, h->cfg.d);
@@ -605,11 +644,13 @@ static int batch_internal(mi_gp_handle* h, int k, const double* thetas, int what
 
 extern "C" int mi_gp_lml_batch(mi_gp_handle* h, int k, const double* thetas, double* lml_out, int* info_out) {
   if (!h || !thetas || !lml_out) return -1;
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_lml_batch");
   return batch_internal(h, k, thetas, 0, lml_out, nullptr, info_out);
 }
 
 extern "C" int mi_gp_lml_grad_batch(mi_gp_handle* h, int k, const double* thetas, double* lml_out, double* grad_out, int* info_out) {
   if (!h || !thetas || !lml_out || !grad_out) return -1;
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_lml_grad_batch");
   if (h->objective == 1) {
     snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad_batch: the leave-one-out objective (option 48 = 1) has no batched form");
     return -1;
@@ -620,14 +661,24 @@ extern "C" int mi_gp_lml_grad_batch(mi_gp_handle* h, int k, const double* thetas
 // ---------------------------------------------------------------- conditional (K8)
 extern "C" int mi_gp_factor(mi_gp_handle* h, const double* theta) {
   if (!h || !theta) return -1;
+  if (h->trend != 0 && h->n <= trend_columns(h)) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_factor: the trend (option 50 = %d) has %d coefficients, n = %d must exceed that", h->trend,
+             trend_columns(h), h->n);
+    return -1;
+  }
   const int r = factor_internal(h, theta, 1);
   h->factored = (r == 0);
+  if (r == 0 && h->trend != 0) {  // G = L^-1 H, chol(G^T G), beta^ and b~ (api_trend.hip)
+    const int rt = trend_factor(h);
+    h->factored = (rt == 0);
+    return rt;
+  }
   return r;
 }
 
 // solve X L^T = B in place for tile columns [c0, c0+w) of the mp x np work matrix (a batch: every problem's, work
 // blocks bt.swork apart, L_p and its leaf inverses in the batch buffers; the GEMMs take the single problem's tile form)
-static hipError_t trsm_rec(mi_gp_handle* h, const Eval& E, double* Bw, long ldw, int mp, int c0, int w) {
+hipError_t trsm_rec(mi_gp_handle* h, const Eval& E, double* Bw, long ldw, int mp, int c0, int w) {
   const double* L = E.K;
   const long lda = h->buf.lda;
   const long zW = E.bt.swork, zK = E.bt.sK;
@@ -648,13 +699,10 @@ static hipError_t trsm_rec(mi_gp_handle* h, const Eval& E, double* Bw, long ldw,
 // composite diagonal is the +/* fold of kv; pred_noise adds sqrt(gv)^2
 static hipError_t predict_reduce(const mi_gp_handle* h, const double* work_dev, long ldw, int m, double* mean_dev, double* var_dev,
                                  int pred_noise) {
-  const int nk = h->spec.nkern, d = h->spec.d;
-  const double* th = h->one.theta_host;
-  double kd = th[nk * d];
-  for (int c = 1; c < nk; ++c) kd = (h->spec.op[c - 1] == 0) ? kd + th[nk * d + c] : kd * th[nk * d + c];
-  const double sg = std::sqrt(th[nk * d + 2 * nk]);
-  return launch_predict_reduce(work_dev, ldw, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, m, kd, pred_noise ? sg * sg : 0.0,
-                               mean_dev, var_dev, h->stream);
+  double kd, noise;
+  predict_scalars(h, pred_noise, &kd, &noise);
+  return launch_predict_reduce(work_dev, ldw, h->buf.K_dev + (long)h->np * h->buf.lda, h->n, m, kd, noise, mean_dev, var_dev,
+                               h->stream);
 }
 
 extern "C" int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw,
@@ -668,7 +716,8 @@ extern "C" int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, dou
   HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, mp, h->np, 0, 0, h->stream),
       "assemble cross");
   HCK(trsm_rec(h, one_eval(h), work_dev, ldw, mp, 0, h->ntc), "trsm");
-  HCK(predict_reduce(h, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "predict_reduce");
+  if (h->trend != 0) HCK(trend_predict_reduce(h, Xnew_dev, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "trend predict_reduce");
+  else HCK(predict_reduce(h, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "predict_reduce");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
   return 0;
 }
@@ -685,6 +734,7 @@ extern "C" int mi_gp_predict_cov(mi_gp_handle* h, const double* Xnew_dev, int m,
                   : m <= 0 ? "m must be >= 1"
                   : (ldc < mp || (ldc & 1)) ? "ldc must be even and >= ceil(m/128)*128"
                   : !h ? "null handle"
+                  : h->trend != 0 ? "no form under a trend (option 50): set option 50 to 0 first"
                   : !h->factored ? "call mi_gp_factor first"
                   : (ldw < h->np || (ldw & 1)) ? "ldw must be even and >= padded n" : nullptr;
   if (why) {
@@ -783,6 +833,7 @@ extern "C" int mi_gp_sample_cov(mi_gp_handle* h, double* cov_dev, long ldc, int 
 // mi_gp_predict's bits: same kernels, same per-element arithmetic, and the solve's GEMMs take the single problem's tile form.
 extern "C" int mi_gp_factor_batch(mi_gp_handle* h, int k, const double* thetas, int* info_out) {
   if (!h) return -1;
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_factor_batch");
   if (k < 1 || !thetas) { snprintf(h->err, sizeof(h->err), "mi_gp_factor_batch: k >= 1 and thetas are required"); return -1; }
   return batch_internal(h, k, thetas, 1, nullptr, nullptr, info_out);
 }
@@ -791,6 +842,7 @@ extern "C" int mi_gp_predict_batch(mi_gp_handle* h, int k, const double* Xnew_de
                                    long stride_work, double* mean_dev, double* var_dev, int pred_noise, double* mix_mean_dev,
                                    double* mix_var_dev) {
   if (!h) return -1;
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_batch");
   if (k < 1 || !Xnew_dev || !work_dev || !mean_dev || !var_dev || m <= 0) {
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_batch: k >= 1, m >= 1 and the point / work / output buffers are required");
     return -1;
@@ -866,6 +918,7 @@ static int predict_via_u(mi_gp_handle* h, const double* Xnew_dev, int m, double*
 extern "C" int mi_gp_predict_u(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw,
                                double* mean_dev, double* var_dev, int pred_noise) {
   if (!h || !Xnew_dev || !work_dev || !mean_dev || !var_dev || m <= 0) return -1;
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_u");
   if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_predict_u: call mi_gp_factor first"); return -1; }
   if (!h->buf.Z_dev || !h->buf.W_dev) {
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_u needs Z_dev and W_dev in mi_gp_set_data");
@@ -887,6 +940,7 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
                                   double* mean_dev, double* var_dev, int pred_noise, double* dmean_dev,
                                   double* dvar_dev) {
   if (!h || !dmean_dev || !dvar_dev) return -1;
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_grad");
   if (!h->buf.Z_dev || !h->buf.W_dev) {
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_grad needs Z_dev and W_dev in mi_gp_set_data");
     return -1;
@@ -917,14 +971,18 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
   return 0;
 }
 
-// The vectors of the leave-one-out objective (api_loo.hip), all zero: the zero vector among them is never written again
+// The vectors of the leave-one-out objective (api_loo.hip), all zero: the zero vector among them is never written again.
+// They are cleared ON THE HANDLE'S STREAM, in front of the tail's kernels: hipMemset of device memory returns before the fill has
+// run, and the handle's streams are non-blocking, so a fill on the null stream can land behind the first tail's kernels and wipe
+// what they wrote (e, s, q and the scalars: a first evaluation with L_LOO = 0 and a zero gradient, and a MAP fit that ends
+// elsewhere).
 hipError_t size_loo_vectors(mi_gp_handle* h, int cap) {
   const size_t len = (size_t)LOO_VECS * ((cap + 127) / 128 * 128) + 8;
   (void)hipFree(h->loo_vec_dev);
   h->loo_vec_dev = nullptr;
   h->loo_cap = 0;
   hipError_t e = hipMalloc(&h->loo_vec_dev, sizeof(double) * len);
-  if (e == hipSuccess) e = hipMemset(h->loo_vec_dev, 0, sizeof(double) * len);
+  if (e == hipSuccess) e = hipMemsetAsync(h->loo_vec_dev, 0, sizeof(double) * len, h->stream);
   if (e == hipSuccess) h->loo_cap = cap;
   return e;
 }
@@ -970,6 +1028,7 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   h->cap = capacity;
   if (h->loo_vec_dev) HCK(size_loo_vectors(h, capacity), "mi_gp_reserve");
   if (h->cv_dev) HCK(size_cv_scratch(h, capacity), "mi_gp_reserve");
+  if (h->trend_dev && trend_reserve) HCK(trend_reserve(h, capacity), "mi_gp_reserve");  // (keeps the conditional's G^T, beta^ and b~)
   return 0;
 }
 
@@ -1027,6 +1086,7 @@ int conditional_block(mi_gp_handle* h, const double* Xnew_dev, const double* yne
 extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
                             double* work_dev, long ldw) {
   if (!h) { set_global_error("mi_gp_append: null handle"); return -1; }
+  if (h->trend != 0) return refuse_trend(h, "mi_gp_append");
   if (!Xnew_dev || !ynew_dev || !work_dev) { snprintf(h->err, sizeof(h->err), "mi_gp_append: null point, value or work buffer"); return -1; }
   if (k < 1 || k > 128) { snprintf(h->err, sizeof(h->err), "mi_gp_append: 1 <= k <= 128 (got %d)", k); return -1; }
   if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_append: call mi_gp_factor first"); return -1; }

@@ -126,6 +126,11 @@ struct mi_gp_handle {
   double* cv_dev;          // the fold pass of that objective (CvScratch; allocated by the first evaluation with b > 1, re-sized like
                            // loo_vec_dev)
   int cv_cap;              // points cv_dev is sized for
+  int trend;               // option 50: the TREND whose coefficients are integrated out -- 0 none, 1 constant h = [1], 2 linear
+                           // h = [1, x_1 .. x_d] (mi_gp_lml_grad, mi_gp_factor and mi_gp_predict; api_trend.hip)
+  double* trend_dev;       // its scratch (TrendScratch, api_trend.hip; allocated by the first use, dropped by mi_gp_reserve and
+                           // re-sized by the next use)
+  int trend_cap;           // points trend_dev is sized for
   char err[256];
 };
 
@@ -247,3 +252,44 @@ hipError_t size_cv_scratch(mi_gp_handle* h, int cap);
 // behind another B; the return value is then the index of the point at the bad pivot of a fold's block).  Weak: api_gp.hip also
 // links without it (the host-only schedule-trace program), and option 48 = 1 and option 49 > 1 are refused there.
 int loo_objective(mi_gp_handle* h, double* value, double* grad) __attribute__((weak));
+
+// api_trend.hip: the trend of option 50 (include/mi_gp.h has the algebra).  Weak like loo_objective: without the file option
+// 50 != 0 is refused.
+inline int trend_columns(const mi_gp_handle* h) { return h->trend == 1 ? 1 : h->trend == 2 ? 1 + h->cfg.d : 0; }
+// the tail of mi_gp_lml_grad behind a successful ordinary evaluation (K^-1 in W_dev, alpha resident): *value = L_T and grad[ntheta]
+// its gradient, W_dev's lower triangle then holds P~; 0, n + j for a bad pivot j of A = H^T K^-1 H (-inf, zero gradient) or a C-ABI
+// error code
+int trend_objective(mi_gp_handle* h, double* value, double* grad) __attribute__((weak));
+// behind a successful mi_gp_factor: G^T = (L^-1 H)^T, C_A = chol(G^T G), its inverse, beta^ and b~ in the handle's scratch; 0,
+// n + j or a C-ABI error code
+int trend_factor(mi_gp_handle* h) __attribute__((weak));
+// mi_gp_predict's reduction under a trend (the rows L^-1 k(X, x*) are in work_dev)
+hipError_t trend_predict_reduce(mi_gp_handle* h, const double* Xnew_dev, const double* work_dev, long ldw, int m, double* mean_dev,
+                                double* var_dev, int pred_noise) __attribute__((weak));
+// mi_gp_reserve's part: the scratch re-sized for `capacity` points, the conditional's state (G^T, C_A^-1, beta^, b~) kept
+hipError_t trend_reserve(mi_gp_handle* h, int capacity) __attribute__((weak));
+// doubles of the trend's scratch for up to cap points (TrendScratch, api_trend.hip)
+constexpr int TREND_PARTS = 65;
+inline size_t trend_scratch_len(int cap) {
+  const size_t vl = (size_t)(cap + 127) / 128 * 128;
+  return 128 * (vl + 16) + 2 * vl * 128 + (size_t)(TREND_PARTS + 3) * MINV_ELEMS + 3 * 128 + 2 * vl + 8 + 2;
+}
+// the -1 of an entry point that has no form under a trend
+inline int refuse_trend(mi_gp_handle* h, const char* entry) {
+  snprintf(h->err, sizeof(h->err), "%s has no form under a trend (option 50 = %d): set option 50 to 0 first", entry, h->trend);
+  return -1;
+}
+
+// api_gp.hip
+hipError_t trsm_rec(mi_gp_handle* h, const Eval& E, double* Bw, long ldw, int mp, int c0, int w);  // X L^T = B in place
+// mi_gp_predict's scalars at the factored theta: the composite prior variance (Stationary.diag == 1: the +/* fold of kv) and
+// sqrt(gv)^2 with pred_noise
+inline void predict_scalars(const mi_gp_handle* h, int pred_noise, double* kdiag, double* noise) {
+  const int nk = h->spec.nkern, d = h->spec.d;
+  const double* th = h->one.theta_host;
+  double kd = th[nk * d];
+  for (int c = 1; c < nk; ++c) kd = (h->spec.op[c - 1] == 0) ? kd + th[nk * d + c] : kd * th[nk * d + c];
+  const double sg = std::sqrt(th[nk * d + 2 * nk]);
+  *kdiag = kd;
+  *noise = pred_noise ? sg * sg : 0.0;
+}

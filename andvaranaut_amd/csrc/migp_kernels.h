@@ -333,6 +333,33 @@ hipError_t launch_loo_gemv(const double* B, long ld, const double* q, int n, dou
 // G[i][j] = -(alpha_i w_j + w_i alpha_j) over the 128 x 128 tiles on and below the block diagonal (whole tiles), zeros up to np
 hipError_t launch_loo_rank2_init(const double* alpha, const double* w, int n, int np, double* G, long ld, hipStream_t stream);
 
+// ---------------------------------------------------------------- trend_f64.hip (option 50: the GP trend, api_trend.hip)
+// The basis h(x) = [1] (p = 1) or [1, x_1 .. x_d] (p = 1 + d <= 128) as H^T: HT[c * ldg + i] = h_c(x_i) for c < p, i < n, zeros up to
+// row 127 and column np - 1
+hipError_t launch_trend_basis(const double* X, int n, int d, int p, int np, double* HT, long ldg, hipStream_t stream);
+// V (np x 128 row-major, all of it written) = Pfull H: Pfull[i][j] = W[max(i, j)][min(i, j)] for i, j < n (the LOWER triangle of W
+// alone) and zero beyond, H^T as launch_trend_basis left it
+// parts: np x 128 doubles of scratch (the k range runs in slices whose partial products are added in index order)
+hipError_t launch_trend_symm(const double* W, long ldw, const double* HT, long ldg, int n, int np, int p, double* V, double* parts,
+                             hipStream_t stream);
+// A (128 x 128 row-major) = sum of nparts partial products (MINV_ELEMS apart, in index order) over the leading p x p block, the
+// identity beyond it
+hipError_t launch_trend_gram_sum(const double* parts, int nparts, int p, double* A, hipStream_t stream);
+// u[c] = sum_{i < n} M[c * ld + i] x[i], c < 128
+hipError_t launch_trend_rowdot(const double* M, long ld, const double* x, int n, double* u, hipStream_t stream);
+// behind the leaf on A (C = chol(A) in place, Cinv its row-major inverse): cvec = C^-1 u, beta = C^-T cvec (128 each, zeros from p
+// on), scal = {1/2 |cvec|^2, sum_{j < p} log C_jj, (double)*info}
+hipError_t launch_trend_solve(const double* C, const double* Cinv, const double* u, const int* info, int p, double* cvec, double* beta,
+                              double* scal, hipStream_t stream);
+// out[i] = base[i] - sum_{a < p} M[i * si + a * sa] beta[a] for i < n, zeros up to np
+hipError_t launch_trend_project(const double* base, const double* M, long si, long sa, const double* beta, int p, int n, int np,
+                                double* out, hipStream_t stream);
+// mi_gp_predict's reduction under a trend over the m rows a* of A (lda apart; GT = (L^-1 H)^T, bt = b - G beta):
+// mean = a* . bt + h(x*)^T beta, var = kdiag - |a*|^2 + |Cinv (h(x*) - G^T a*)|^2 + noise; each output is written once
+hipError_t launch_trend_predict_reduce(const double* A, long lda, const double* Xnew, int d, int p, const double* GT, long ldg,
+                                       const double* bt, const double* beta, const double* Cinv, int n, int m, double kdiag,
+                                       double noise, double* mean, double* var, hipStream_t stream);
+
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)
 void set_global_error(const char* text);

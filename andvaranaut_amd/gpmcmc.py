@@ -247,12 +247,15 @@ class GPMCMC(ConsumersMixin):
         """The numeric half of ``test_plots`` (gpmcmc.py:933-976; the plots are out of scope): condition the model on the
         training split (``train_test``; refitted there with ``method``, 'none' = the stored hypers), predict the held-out
         points and return RMSE, mean absolute / percentage error and R^2 with the arrays ``returndat`` hands back."""
+        trend = getattr(self, "trend", None)  # (an object fitted with a trend is tested with it)
+        if trend is not None and (method not in ("none", "map") or iwgp or cwgp):
+            raise ValueError(f"test_stats under trend={trend!r} needs method='none' or 'map' and neither iwgp nor cwgp")
         if getattr(self, "train", None) is None:
             self.train_test()
         xtrain, xtest = self.x[self.train, :], self.x[self.test, :]
         ytrain, ytest = self.y[self.train, :], self.y[self.test, :]
         ymtrain, ymtest = self.ym[self.train, :], self.ym[self.test, :]
-        m, gp, hypers, _ = self.__fit(xtrain, ytrain - ymtrain, method, iwgp, cwgp, jitter)
+        m, gp, hypers, _ = self.__fit(xtrain, ytrain - ymtrain, method, iwgp, cwgp, jitter, trend=trend)
         try:
             xctest = np.column_stack([self.xconrevs[i].con(xtest[:, i]) for i in range(self.nx)])
             saved = self.m, self.hypers
@@ -296,6 +299,7 @@ class GPMCMC(ConsumersMixin):
         in the original output units (with the Jacobian sum log|d y_con / d y| when the output conversion has ``der``, as in
         ``log_predictive``), ``lpd_folds`` (per fold, its Jacobian included), ``folds`` and ``info`` (0 per fold, or the
         pivot at which the fold's block of K^-1 was not positive definite)."""
+        self._no_trend("cv_stats")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before cross-validating")
         n = len(self.x)
@@ -392,6 +396,7 @@ class GPMCMC(ConsumersMixin):
         self.__release()
         self.m = None
         self.hypers = None
+        self.trend = None
 
     def __release(self):
         gp = getattr(self, "gp", None)
@@ -411,11 +416,18 @@ class GPMCMC(ConsumersMixin):
         if self.gp is None and self.hypers is not None and self.m is not None:
             xin, yin = self._converted(self.x, self.y - self.ym)
             self.gp = MiGP(xin, yin, self.kernel, device=self.device)
+            if getattr(self, "trend", None) is not None:
+                self.gp.set_trend(self.trend)
         return self.gp
+
+    def _no_trend(self, what):
+        """Raised, before any device call, by what has no form under a fitted trend."""
+        if getattr(self, "trend", None) is not None:
+            raise ValueError(f"{what} has no form under trend={self.trend!r}: fit without a trend to use it")
 
     # ------------------------------------------------------------------ fit
     def fit(self, method="map", return_data=False, iwgp=False, cwgp=False, jitter=1e-6, truncate=False,
-            restarts=1, objective="lml", nfolds=10, fold_seed=None, **kwargs):
+            restarts=1, objective="lml", nfolds=10, fold_seed=None, trend=None, **kwargs):
         """gpmcmc.py:175-182.  ``objective="loo"`` (with ``method="map"``) maximises the leave-one-out log predictive density
         sum_i log p(y_i | y_-i) plus the priors instead of the log marginal likelihood (Rasmussen & Williams section 5.4.2: the
         criterion for a misspecified kernel family); the hyper-parameters are stored as a MAP fit stores them.  It has no
@@ -424,7 +436,17 @@ class GPMCMC(ConsumersMixin):
         same conditions: the remedy where points cluster and every left-out point is predicted by its twin.  The folds are a
         random partition, ``np.random.default_rng(fold_seed).permutation`` cut into blocks of b = ceil(n / nfolds) points (the
         last fold may be smaller; a fold holds at most 128 points); ``return_data`` carries them as ``data["folds"]``, index
-        arrays into the data as given, for ``cv_stats(folds=...)``."""
+        arrays into the data as given, for ``cv_stats(folds=...)``.
+        ``trend="constant"`` or ``"linear"`` (with ``method="map"``, ``objective="lml"``, no warps) gives the GP a prior mean
+        h(x)^T beta with h = [1] or [1, x_1 .. x_nx] in the converted inputs, whose coefficients carry a vague prior and are
+        integrated out (Rasmussen & Williams section 2.7): the hyper-parameters are those of a zero-mean fit, the fit maximises
+        the trend's marginal likelihood, and ``predict`` returns the trend's conditional.  The choice is part of the object's
+        state (``self.trend``).  Restarts run one after the other."""
+        if trend is not None:
+            if trend not in ("constant", "linear"):
+                raise ValueError(f"trend must be None, 'constant' or 'linear' (got {trend!r})")
+            if method != "map" or objective != "lml" or iwgp or cwgp:
+                raise ValueError("trend needs method='map', objective='lml' and neither iwgp nor cwgp")
         cv = None
         if objective == "kfold":
             cv = self._kfold_plan(method, iwgp, cwgp, nfolds, fold_seed)
@@ -433,7 +455,8 @@ class GPMCMC(ConsumersMixin):
         if objective == "loo" and (method != "map" or iwgp or cwgp):
             raise ValueError("objective='loo' needs method='map' and neither iwgp nor cwgp")
         self.m, self.gp, self.hypers, data = self.__fit(self.x, self.y - self.ym, method, iwgp, cwgp, jitter,
-                                                        truncate, restarts, objective=objective, cv=cv, **kwargs)
+                                                        truncate, restarts, objective=objective, cv=cv, trend=trend, **kwargs)
+        self.trend = trend
         if return_data:
             return data
 
@@ -560,13 +583,16 @@ class GPMCMC(ConsumersMixin):
 
         return likelihood
 
-    def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", cv=None, **kwargs):
+    def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", cv=None, trend=None,
+              **kwargs):
         n_i, n_pos, n_free = self._warp_sizes(iwgp, cwgp)
         model = HyperModel(self.nx, self.kerns, noise=self.noise, truncate=truncate, jitter=jitter, n_iwgp=n_i,
                            n_cwgp_pos=n_pos, n_cwgp=n_free)
         xin, yin = self._converted(x, y)
         self.__release()
         gp = MiGP(xin, yin, self.kernel, device=self.device)
+        if trend is not None:
+            gp.set_trend(trend)  # (gp.lml_grad then returns the trend's marginal likelihood; the stored handle keeps the trend)
         lik = self._warp_likelihood(gp, x, y, xin, iwgp, cwgp) if (iwgp or cwgp) else None
         # pm.find_MAP maximises without the transform Jacobian, pm.sample with it (priors.py header)
         fun_map = lambda q: model.logp_dlogp(q, gp.lml_grad, jacobian=False, likelihood=lik)  # noqa: E731
@@ -865,6 +891,7 @@ class GPMCMC(ConsumersMixin):
         gp.predict(x, point, diag=False, pred_noise=...); the diagonal agrees with predict(revert=False, return_var=True).
         A covariance has no image under a nonlinear output reversion, so there is no ``revert`` here (sample_posterior
         reverts draws instead)."""
+        self._no_trend("predict_joint")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
         xarg, _ = self._converted_x(np.asarray(x, dtype=np.float64), convert)
@@ -875,6 +902,7 @@ class GPMCMC(ConsumersMixin):
         """Held-out JOINT log predictive density of up to 128 points (x [M, nx], y [M] or [M, 1]) in the original output
         units, at ``self.hypers``: log N(y_con | conditional of the fitted GP at x_con, with observation noise) plus the
         Jacobian sum log|d y_con / d y| when the output conversion has ``der`` (MiGP.logpdf; nothing is appended)."""
+        self._no_trend("log_predictive")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
         x = np.asarray(x, dtype=np.float64)
@@ -895,6 +923,7 @@ class GPMCMC(ConsumersMixin):
         by default (pred_noise=False), of noisy observations with pred_noise=True.  revert=True maps each draw through the
         output reversion point by point and adds the mean function -- exact for sample paths, no quadrature.  ``seed``: see
         MiGP.sample_posterior (None: fresh draws on every call)."""
+        self._no_trend("sample_posterior")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
         xarg, xorig = self._converted_x(np.asarray(x, dtype=np.float64), convert)
@@ -942,6 +971,7 @@ class GPMCMC(ConsumersMixin):
         ``self.posterior_info``; none left raises FloatingPointError.  One distinct draw reproduces predict() at its hypers: the
         unreverted moments bit for bit where predict() takes the triangular solve (not U = L^-T, MiGP.predict), the reverted
         ones to rounding."""
+        self._no_trend("predict_posterior")
         if self._ensure_gp() is None or self.m is None:
             raise Exception("Error: fit the GP before predicting")
         thetas, idx = self._posterior_thetas(data, ndraws, jitter)

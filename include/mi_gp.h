@@ -437,6 +437,48 @@ MI_GP_API int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host,
  *      option changes no resident state and has no effect at all under 48 = 0; values outside 1..128 return -1, and so does a
  *      value other than 1 in a build without the tail.  Out of scope: arbitrary index sets (permute the data: the contiguous
  *      folds of a random permutation are random folds), folds of more than 128 points, a batched or sharded form.
+ *   50 (not a tuning knob) the TREND: a prior mean h(x)^T beta whose coefficients carry a vague prior and are integrated out in
+ *      closed form (universal kriging; Rasmussen & Williams section 2.7, eqs. 2.41-2.45), so theta and mi_gp_num_theta() stay as
+ *      they are.  0 (default) no trend; 1 constant, h = [1], p = 1; 2 linear, h = [1, x_1 .. x_d], p = 1 + d (needs d <= 127).
+ *      H is n x p with rows h(x_i)^T from the bound X_dev (converted inputs); K_y is the noisy covariance of the entry point's own
+ *      form (marginal in mi_gp_lml_grad, conditional in mi_gp_factor; the diagonal of mi_gp_set_diag included), alpha = K_y^-1 y.
+ *      mi_gp_lml_grad (option 48 = 0) runs the ordinary evaluation first (same launches, same schedule), then a tail on the
+ *      handle's stream:
+ *          V = K_y^-1 H,  A = H^T V,  C_A = chol(A),  Q = V C_A^-T,  c = Q^T y
+ *          L_T = LML + 1/2 |c|^2 - sum_j log (C_A)_jj + p/2 log 2 pi                                      (R & W eq. 2.45)
+ *          P~ = K_y^-1 - Q Q^T,   alpha~ = alpha - Q c  (= P~ y)
+ *          dL_T/dtheta_k = 1/2 sum_ij (alpha~_i alpha~_j - P~_ij) dK_ij/dtheta_k              (d/d jitter = d/d gv)
+ *      -- V by a symmetric thin multiply on the fp64 matrix cores that reads the lower triangle of W_dev alone (it streams the
+ *      matrix once, about 8 N^2 bytes, in slices of k whose partial products are added in index order; measured at about a
+ *      quarter of the HBM peak: bound by the latency of its loads, not yet by the bandwidth), A in k segments that are added in index order, the rank-128 update
+ *      W -= Q Q^T over the lower trapezoid on the GEMM, and the LML gradient's contraction kernel with P~ and alpha~.
+ *      *lml_out = L_T, grad_out its gradient in theta order; the call returns with the stream synchronised.  Afterwards the lower
+ *      triangle of W_dev holds P~, not K^-1: the handle marks K^-1 not resident, as after mi_gp_lml (mi_gp_kfold and the data-side
+ *      gradients need option 50 = 0 and a new mi_gp_lml_grad); mi_gp_lml_parts keeps the factorisation's logdet and quad.
+ *      With option 48 = 1 the call returns -1 (no cross-validation objective under a trend).
+ *      mi_gp_factor additionally forms G^T = (L^-1 H)^T (the blocked solve of mi_gp_predict on 128 rows), A = G^T G = C_A C_A^T,
+ *      its inverse, beta^ = A^-1 G^T b and b~ = b - G beta^ (b = L^-1 y, the beta row) in scratch the handle owns, and
+ *      mi_gp_predict returns the trend's conditional: per point, with a* = L^-1 k(X, x*) (the row the call forms in work_dev)
+ *          r = h(x*) - G^T a*,   mean = a* . b~ + h(x*)^T beta^,   var = kdiag - |a*|^2 + |C_A^-1 r|^2 (+ gv if pred_noise)
+ *                                                                                                       (R & W eqs. 2.41-2.42)
+ *      in one reduction over the rows of work_dev, whose contract (size, layout) does not change; mean_dev / var_dev are written
+ *      once and may be pinned host addresses.  n <= p returns -1.  If A is not positive definite the call returns n + j, j the
+ *      1-based pivot in the basis (L_T = -inf and a zero gradient; after mi_gp_factor the handle is then not factored).
+ *      Refused (-1, before any device call, with a text that names option 50) while the option is not 0: mi_gp_lml,
+ *      mi_gp_lml_batch, mi_gp_lml_grad_batch, mi_gp_factor_batch, mi_gp_predict_batch, mi_gp_predict_u, mi_gp_predict_grad,
+ *      mi_gp_predict_cov, mi_gp_append, mi_gp_logpdf, mi_gp_kfold, mi_gp_alpha and mi_gp_grad_x.  mi_gp_sample_cov,
+ *      mi_gp_set_data, mi_gp_set_diag, mi_gp_reserve and the block-level entries are not affected.  The handle owns the scratch
+ *      (H^T / G^T as 128 rows, V and Q as padded capacity x 128, the partial products and three 128 x 128 blocks of A, a few
+ *      vectors): allocated by the first use, freed by mi_gp_destroy; mi_gp_reserve re-sizes it and keeps what mi_gp_predict needs
+ *      (G^T, C_A^-1, beta^, b~), so the handle stays factored.  No refusal changes the handle's state.  The same call in the same state returns the same bits; every element a launch
+ *      reads is written earlier in the same call (NaN in the strict upper triangle of W_dev, in work_dev or in the scratch
+ *      changes nothing); the scheduling options change no bit; no sum uses atomics, every one runs in a fixed order.  Values
+ *      outside 0..2 return -1, and so do 2 with d > 127 and 1 or 2 in a build without the tail (the host-only schedule-trace
+ *      program).  Setting a value other than the current one ends the resident state exactly as mi_gp_set_data does; setting the
+ *      current value changes nothing; with 0 the library enqueues exactly what it enqueues without the option.  Out of scope:
+ *      the batched and sharded forms; cross-validation objectives, mi_gp_kfold, mi_gp_append and mi_gp_logpdf under a trend;
+ *      data-side gradients (and with them warped fits under a trend); reading beta^ out; quadratic or user-supplied bases; a
+ *      rank-deficiency test beyond n <= p.
  * 8, 14, 16, 18, 19, 21, 26, 27, 30, 31, 38, 45 and 47 only change scheduling (bit-identical results); 20 moves tiles between the
  * two GEMM kernels (same k order); 2, 4-7, 9, 32, 35, 37 and 46 regroup sums (agreement to rounding), and so does 0 where it changes
  * the super-panel width (20 to 60 tile columns).
