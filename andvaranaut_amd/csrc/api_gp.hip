@@ -64,8 +64,8 @@ static void release_handle(mi_gp_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   free_scratch(h->one);
   free_scratch(h->batch);
-  (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev); (void)hipFree(h->loo_vec_dev);
-  (void)hipFree(h->cv_dev); (void)hipFree(h->trend_dev);
+  (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
+  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk}) (void)hipFree(b->p);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -517,10 +517,7 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
   // non-positive-definite K their output is discarded
   const int r = factor_internal(h, theta, 2);
   if (r < 0) return r;
-  for (int i = 0; i < h->ntheta; ++i) grad_out[i] = 0.0;
-  if (r > 0) { *lml_out = -INFINITY; return r; }
-  *lml_out = h->one.out_host[0];
-  for (int i = 0; i < h->ntheta; ++i) grad_out[i] = h->one.grad_host[i];
+  if (finish_objective(h, r, h->one.out_host[0], lml_out, grad_out)) return r;
   h->have_kinv = true;
   // option 50 != 0: the same evaluation, then the trend's tail on the resident K^-1 and alpha (api_trend.hip); W_dev then holds P~
   if (h->trend != 0) {
@@ -971,32 +968,6 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
   return 0;
 }
 
-// The vectors of the leave-one-out objective (api_loo.hip), all zero: the zero vector among them is never written again.
-// They are cleared ON THE HANDLE'S STREAM, in front of the tail's kernels: hipMemset of device memory returns before the fill has
-// run, and the handle's streams are non-blocking, so a fill on the null stream can land behind the first tail's kernels and wipe
-// what they wrote (e, s, q and the scalars: a first evaluation with L_LOO = 0 and a zero gradient, and a MAP fit that ends
-// elsewhere).
-hipError_t size_loo_vectors(mi_gp_handle* h, int cap) {
-  const size_t len = (size_t)LOO_VECS * ((cap + 127) / 128 * 128) + 8;
-  (void)hipFree(h->loo_vec_dev);
-  h->loo_vec_dev = nullptr;
-  h->loo_cap = 0;
-  hipError_t e = hipMalloc(&h->loo_vec_dev, sizeof(double) * len);
-  if (e == hipSuccess) e = hipMemsetAsync(h->loo_vec_dev, 0, sizeof(double) * len, h->stream);
-  if (e == hipSuccess) h->loo_cap = cap;
-  return e;
-}
-
-// The scratch of the k-fold objective's fold pass (cv_scratch(), gp_handle.h): every element is written before it is read
-hipError_t size_cv_scratch(mi_gp_handle* h, int cap) {
-  (void)hipFree(h->cv_dev);
-  h->cv_dev = nullptr;
-  h->cv_cap = 0;
-  const hipError_t e = hipMalloc(&h->cv_dev, sizeof(double) * cv_scratch_len(cap));
-  if (e == hipSuccess) h->cv_cap = cap;
-  return e;
-}
-
 // ---------------------------------------------------------------- appending points at fixed theta
 // The handle's n-dependent scratch for up to `capacity` points; the resident contents (leaf inverses, alpha) are kept.
 extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
@@ -1026,10 +997,24 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   (void)hipFree(s.dinv_dev); (void)hipFree(s.alpha_dev); (void)hipFree(s.part_dev);
   s.dinv_dev = dinv; s.alpha_dev = alpha; s.part_dev = part;
   h->cap = capacity;
-  if (h->loo_vec_dev) HCK(size_loo_vectors(h, capacity), "mi_gp_reserve");
-  if (h->cv_dev) HCK(size_cv_scratch(h, capacity), "mi_gp_reserve");
-  if (h->trend_dev && trend_reserve) HCK(trend_reserve(h, capacity), "mi_gp_reserve");  // (keeps the conditional's G^T, beta^ and b~)
+  // the capacity-sized blocks: the objectives' hold nothing between calls and are dropped (their next use re-sizes them), the
+  // trend's keeps the conditional's G^T, beta^ and b~
+  for (CapBlock* b : {&h->loo, &h->cv}) (void)resize_block(*b, 0, 0);
+  if (h->trend_blk.p && trend_reserve) HCK(trend_reserve(h, capacity), "mi_gp_reserve");
   return 0;
+}
+
+// The k-segmented 128 x 128 Gram product (gp_handle.h).  Segment g of an operand starts g * seg * 128 columns of k in: that many
+// doubles along a row of A (and of B under bk = 0), that many rows of 128 doubles of B under bk = 1.
+hipError_t gram_segments(mi_gp_handle* h, const Eval& E, In A, In B, int bk, double* parts, int* nparts) {
+  const int ntc = h->ntc, seg = (ntc + 63) / 64, nfull = ntc / seg, rem = ntc - nfull * seg;
+  const long ka = seg * 128L, kb = bk ? ka * 128 : ka;
+  *nparts = nfull + (rem > 0 ? 1 : 0);
+  hipError_t e = gemm_call(h, E, 0, bk, {A.p, A.ld, ka}, {B.p, B.ld, kb}, {parts, 128, MINV_ELEMS}, 1, 1, seg * 128, 0, 0, 1.0, 0.0, nfull);
+  if (e == hipSuccess && rem > 0)
+    e = gemm_call(h, E, 0, bk, {A.p + nfull * ka, A.ld}, {B.p + nfull * kb, B.ld}, {parts + (long)nfull * MINV_ELEMS, 128}, 1, 1, rem * 128,
+                  0, 0, 1.0, 0.0, 1);
+  return e;
 }
 
 // Phase 1 of mi_gp_append, shared with mi_gp_logpdf (api_logpdf.hip): the conditional of k new points given the resident
@@ -1057,19 +1042,12 @@ int conditional_block(mi_gp_handle* h, const double* Xnew_dev, const double* yne
     HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, k, h->buf.X_dev, n, L21, ldw, 128, np, 0, 0, st), "assemble K21");
     HCK(trsm_rec(h, E, L21, ldw, 128, 0, ntc), "trsm L21");
   }
-  // L21 L21^T in k segments of st_tiles tile columns (a single 128 x 128 output over k = n would run on 4 workgroups)
-  const int st_tiles = (ntc + 63) / 64, nfull = ntc / st_tiles, rem = ntc - nfull * st_tiles;
-  HCK(gemm_call(h, E, 0, 0, {L21, ldw, st_tiles * 128L}, {L21, ldw, st_tiles * 128L}, {parts, 128, MINV_ELEMS}, 1, 1, st_tiles * 128, 0, 0,
-                1.0, 0.0, nfull), "syrk segments");
-  if (rem > 0) {
-    const long off = (long)nfull * st_tiles * 128;
-    HCK(gemm_call(h, E, 0, 0, {L21 + off, ldw}, {L21 + off, ldw}, {parts + (long)nfull * MINV_ELEMS, 128}, 1, 1, rem * 128, 0, 0,
-                  1.0, 0.0, 1), "syrk tail");
-  }
+  int nparts = 0;
+  HCK(gram_segments(h, E, {L21, ldw}, {L21, ldw}, 0, parts, &nparts), "L21 L21^T segments");
   HCK(hipMemsetAsync(S, 0, sizeof(double) * 2 * MINV_ELEMS, st), "S clear");
   HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, k, Xnew_dev, k, S, 128, 128, 128, 1, 1, st, -2147483647 - 1, diag_new_dev),
       "assemble K22");
-  HCK(launch_append_schur(S, parts, nfull + (rem > 0 ? 1 : 0), L21, ldw, beta1, np, ynew_dev, k, st), "schur");
+  HCK(launch_append_schur(S, parts, nparts, L21, ldw, beta1, np, ynew_dev, k, st), "schur");
   HCK(hipMemsetAsync(h->one.info_dev, 0x7f, sizeof(int), st), "info reset");
   HCK(launch_potrf_leaf128(S, 128, Sinv, n, h->one.info_dev, st, S + MINV_ELEMS), "leaf S");
   HCK(launch_append_stats(S, k, h->one.info_dev, h->app_stats_dev, st), "append stats");
@@ -1141,7 +1119,7 @@ extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const doubl
   h->ntc = np2 / 128;
   h->one.out_host[1] += stats[0];
   h->one.out_host[2] += stats[1];
-  h->one.out_host[0] = -0.5 * (double)n2 * 1.8378770664093453 - 0.5 * h->one.out_host[2] - h->one.out_host[1];
+  h->one.out_host[0] = -0.5 * (double)n2 * LOG_2PI - 0.5 * h->one.out_host[2] - h->one.out_host[1];
   h->have_kinv = false;
   // the caller's batch buffers were sized for the old n: every batch call is refused until mi_gp_set_batch (which re-sizes the
   // batch scratch for the new n)

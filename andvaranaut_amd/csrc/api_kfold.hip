@@ -11,13 +11,28 @@
 //   log p(y_I | y_-I) = -1/2 alpha_I^T Sigma_I alpha_I + 1/2 log det K^-1_II - |I|/2 log 2 pi.
 // With C = chol(K^-1_II) and M = C^-1 from the leaf: Sigma_I = M^T M, t = M alpha_I, the quadratic form is |t|^2, the
 // log-determinant term sum log C_ii.
-// Work block, for P folds per pass: P gathered blocks (the leaf factorises them in place), P leaf inverses, P x 256 gathered
-// alpha_I / y_I, then as ints the staged fold_idx [total], fold_ptr [nfolds + 1] and one bad-pivot word per fold [nfolds]
-// (nfolds <= total: 2 * total + 2 doubles hold them).
-constexpr long KFOLD_PER_FOLD = 2 * MINV_ELEMS + 256;
-static long kfold_tail(long total) { return 2 * total + 2; }
+// The work block for P folds per pass: fold_layout() (gp_handle.h).
 extern "C" long mi_gp_kfold_work(int folds_per_pass, long total_idx) {
-  return (folds_per_pass < 1 || total_idx < 1) ? -1 : (long)folds_per_pass * KFOLD_PER_FOLD + kfold_tail(total_idx);
+  return (folds_per_pass < 1 || total_idx < 1) ? -1 : fold_work_len(folds_per_pass, total_idx);
+}
+
+int fold_pass(mi_gp_handle* h, const FoldWork& w, int nfolds, const int* ptr_host, const int* idx_host,
+              const std::function<hipError_t(int, int)>& step) {
+  const hipStream_t st = h->stream;
+  HCK(hipMemcpyAsync(w.idx, idx_host, sizeof(int) * ptr_host[nfolds], hipMemcpyHostToDevice, st), "index upload");
+  HCK(hipMemcpyAsync(w.ptr, ptr_host, sizeof(int) * (nfolds + 1), hipMemcpyHostToDevice, st), "fold upload");
+  for (int f0 = 0; f0 < nfolds; f0 += w.pass) {
+    const int nf = nfolds - f0 < w.pass ? nfolds - f0 : w.pass;
+    Batch bt;
+    bt.nb = nf;
+    bt.sK = bt.sdinv = MINV_ELEMS;
+    bt.sinfo = 1;
+    HCK(launch_kfold_gather(h->buf.W_dev, h->buf.lda, h->one.alpha_dev, h->buf.y_dev, w.idx, w.ptr, f0, nf, w.blocks, w.vecs, w.info,
+                            st), "kfold_gather");
+    HCK(launch_potrf_leaf128(w.blocks, 128, w.minv, 0, w.info + f0, st, nullptr, &bt), "kfold leaf");
+    HCK(step(f0, nf), "fold step");
+  }
+  return 0;
 }
 
 namespace {
@@ -56,10 +71,12 @@ extern "C" int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host
   }
   long P = 0;
   if (!why[0] && !singletons) {
-    P = work_dev ? (work_len - kfold_tail(total)) / KFOLD_PER_FOLD : 0;
+    // the most folds per pass whose work block fits work_len
+    const long tail = fold_work_len(0, total), per_fold = fold_work_len(1, total) - tail;
+    P = work_dev ? (work_len - tail) / per_fold : 0;
     if (!work_dev) snprintf(why, sizeof(why), "null work buffer");
     else if ((uintptr_t)work_dev & 15) snprintf(why, sizeof(why), "work_dev must be 16-byte aligned");
-    else if (work_len < kfold_tail(total) || P < 1)
+    else if (work_len < tail || P < 1)
       snprintf(why, sizeof(why), "work_len %ld is too small for one fold (mi_gp_kfold_work(1, %ld) = %ld)", work_len, total,
                mi_gp_kfold_work(1, total));
   }
@@ -79,22 +96,12 @@ extern "C" int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host
     HCK(hipStreamSynchronize(st), "stream sync");
   } else {
     if (P > nfolds) P = nfolds;
-    double *blocks = work_dev, *minv = blocks + P * MINV_ELEMS, *vecs = minv + P * MINV_ELEMS;
-    int* idx_dev = reinterpret_cast<int*>(vecs + P * 256);
-    int *ptr_dev = idx_dev + total, *info_dev = ptr_dev + nfolds + 1;
-    HCK(hipMemcpyAsync(idx_dev, fold_idx_host, sizeof(int) * total, hipMemcpyHostToDevice, st), "index upload");
-    HCK(hipMemcpyAsync(ptr_dev, fold_ptr_host, sizeof(int) * (nfolds + 1), hipMemcpyHostToDevice, st), "fold upload");
-    for (int f0 = 0; f0 < nfolds; f0 += (int)P) {
-      const int nf = nfolds - f0 < P ? nfolds - f0 : (int)P;
-      Batch bt;
-      bt.nb = nf;
-      bt.sK = bt.sdinv = MINV_ELEMS;
-      bt.sinfo = 1;
-      HCK(launch_kfold_gather(W, ld, alpha, y, idx_dev, ptr_dev, f0, nf, blocks, vecs, info_dev, st), "kfold_gather");
-      HCK(launch_potrf_leaf128(blocks, 128, minv, 0, info_dev + f0, st, nullptr, &bt), "kfold leaf");
-      HCK(launch_kfold_moments(blocks, minv, vecs, ptr_dev, info_dev, f0, nf, logp_dev, mean_dev, var_dev, st), "kfold_moments");
-    }
-    HCK(hipMemcpyAsync(info.data(), info_dev, sizeof(int) * nfolds, hipMemcpyDeviceToHost, st), "info download");
+    const FoldWork w = fold_layout(work_dev, P, total, nfolds);
+    const int r = fold_pass(h, w, nfolds, fold_ptr_host, fold_idx_host, [&](int f0, int nf) {
+      return launch_kfold_moments(w.blocks, w.minv, w.vecs, w.ptr, w.info, f0, nf, logp_dev, mean_dev, var_dev, st);
+    });
+    if (r != 0) return r;
+    HCK(hipMemcpyAsync(info.data(), w.info, sizeof(int) * nfolds, hipMemcpyDeviceToHost, st), "info download");
     HCK(hipStreamSynchronize(st), "stream sync");
     for (int f = 0; f < nfolds; ++f) info[f] = info[f] == INFO_OK ? 0 : info[f];
   }

@@ -50,7 +50,7 @@ extern "C" int mi_gp_logpdf(mi_gp_handle* h, const double* Xnew_dev, const doubl
     snprintf(h->err, sizeof(h->err), "mi_gp_logpdf: the trial block is not positive definite (pivot %d)", info);
     return info;
   }
-  *logp_out = -0.5 * stats[1] - stats[0] - 0.5 * (double)k * 1.8378770664093453;
+  *logp_out = -0.5 * stats[1] - stats[0] - 0.5 * (double)k * LOG_2PI;
   if (grad) {
     const int n = h->n, np = h->np, ntc = h->ntc;
     const long ld = h->buf.lda, R = 128L * ldw;

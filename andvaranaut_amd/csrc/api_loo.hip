@@ -20,33 +20,36 @@
 // launch for launch.  b = 1 takes the leave-one-out path itself; b >= n is the log marginal likelihood by another route.
 #include "gp_handle.h"
 
+// The handle's scratch of option 49's fold pass for up to cap points: a work block as mi_gp_kfold lays it out (fold_layout(), for
+// cv_pass(cap) folds per pass: no result depends on it), behind it what the objective adds -- R [padded cap][128] and the
+// per-fold logp [padded cap].  Every element is written before it is read.
+constexpr int CV_PASS_MAX = 128;
+static int cv_pass(int cap) { return cap / 2 + 1 < CV_PASS_MAX ? cap / 2 + 1 : CV_PASS_MAX; }  // (folds of two points or more)
+static long cv_padded(int cap) { return (cap + 127) / 128 * 128; }
+static double* cv_R(const mi_gp_handle* h) { return h->cv.p + fold_work_len(cv_pass(h->cv.cap), cv_padded(h->cv.cap)); }
+
 // The fold pass of option 49: mi_gp_kfold's gather and batched leaf over passes of the handle's scratch, then per fold t, e_I,
 // q_I, R_f and the logp (cv_fold_kernel); the folds' sum and the first bad index in one launch behind the last pass.  idx / ptr:
 // the caller's host lists, staged from here (they live until the caller synchronises the stream).
 static int cv_fold_pass(mi_gp_handle* h, int b, std::vector<int>& idx, std::vector<int>& ptr, double* e, double* q, double* scal) {
   const int n = h->n;
   const hipStream_t st = h->stream;
-  if (!h->cv_dev || h->cv_cap < h->cap) HCK(size_cv_scratch(h, h->cap), "k-fold scratch");
-  const CvScratch c = cv_scratch(h);
+  if (stale_block(h, h->cv)) {
+    const long vl = cv_padded(h->cap);
+    HCK(resize_block(h->cv, h->cap, fold_work_len(cv_pass(h->cap), vl) + vl * 128 + vl), "k-fold scratch");
+  }
   const int nfolds = (n + b - 1) / b;
+  const FoldWork w = fold_layout(h->cv.p, cv_pass(h->cv.cap), n, nfolds);
+  double *R = cv_R(h), *flogp = R + cv_padded(h->cv.cap) * 128;
   idx.resize(n);
   ptr.resize(nfolds + 1);
   for (int i = 0; i < n; ++i) idx[i] = i;
   for (int f = 0; f <= nfolds; ++f) ptr[f] = f * b < n ? f * b : n;
-  HCK(hipMemcpyAsync(c.idx, idx.data(), sizeof(int) * n, hipMemcpyHostToDevice, st), "index upload");
-  HCK(hipMemcpyAsync(c.ptr, ptr.data(), sizeof(int) * (nfolds + 1), hipMemcpyHostToDevice, st), "fold upload");
-  for (int f0 = 0; f0 < nfolds; f0 += c.pass) {
-    const int nf = nfolds - f0 < c.pass ? nfolds - f0 : c.pass;
-    Batch bt;
-    bt.nb = nf;
-    bt.sK = bt.sdinv = MINV_ELEMS;
-    bt.sinfo = 1;
-    HCK(launch_kfold_gather(h->buf.W_dev, h->buf.lda, h->one.alpha_dev, h->buf.y_dev, c.idx, c.ptr, f0, nf, c.blocks, c.vecs, c.info,
-                            st), "kfold_gather");
-    HCK(launch_potrf_leaf128(c.blocks, 128, c.minv, 0, c.info + f0, st, nullptr, &bt), "k-fold leaf");
-    HCK(launch_cv_fold(c.blocks, c.minv, c.vecs, c.ptr, c.info, f0, nf, c.flogp, e, q, c.R, st), "cv_fold");
-  }
-  HCK(launch_cv_reduce(c.flogp, c.ptr, c.info, nfolds, scal, st), "cv_reduce");
+  const int r = fold_pass(h, w, nfolds, ptr.data(), idx.data(), [&](int f0, int nf) {
+    return launch_cv_fold(w.blocks, w.minv, w.vecs, w.ptr, w.info, f0, nf, flogp, e, q, R, st);
+  });
+  if (r != 0) return r;
+  HCK(launch_cv_reduce(flogp, w.ptr, w.info, nfolds, scal, st), "cv_reduce");
   return 0;
 }
 
@@ -54,10 +57,19 @@ int loo_objective(mi_gp_handle* h, double* value, double* grad) {
   const int n = h->n, np = h->np;
   const long ld = h->buf.lda;
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  if (!h->loo_vec_dev || h->loo_cap < h->cap) HCK(size_loo_vectors(h, h->cap), "leave-one-out vectors");
-  const long vl = (h->loo_cap + 127) / 128 * 128;
-  double *e = h->loo_vec_dev, *s = e + vl, *q = s + vl, *w = q + vl, *logp = w + 2 * vl, *scal = logp + vl;
-  const double* zero = w + vl;  // (zeroed by size_loo_vectors, never written)
+  // The vectors e, s, q, w, the zero vector and the per-point logp (vl apart), then 8 scalars, all zero: the zero vector among them
+  // is never written again.  They are cleared ON THE HANDLE'S STREAM, in front of the tail's kernels: hipMemset of device memory
+  // returns before the fill has run, and the handle's streams are non-blocking, so a fill on the null stream can land behind the
+  // first tail's kernels and wipe what they wrote (e, s, q and the scalars: a first evaluation with L_LOO = 0 and a zero
+  // gradient, and a MAP fit that ends elsewhere).
+  if (stale_block(h, h->loo)) {
+    const size_t len = (size_t)6 * ((h->cap + 127) / 128 * 128) + 8;
+    HCK(resize_block(h->loo, h->cap, len), "leave-one-out vectors");
+    HCK(hipMemsetAsync(h->loo.p, 0, sizeof(double) * len, h->stream), "leave-one-out vectors");
+  }
+  const long vl = (h->loo.cap + 127) / 128 * 128;
+  double *e = h->loo.p, *s = e + vl, *q = s + vl, *w = q + vl, *logp = w + 2 * vl, *scal = logp + vl;
+  const double* zero = w + vl;  // (zeroed with the block, never written)
   const hipStream_t st = h->stream;
   const Eval E = one_eval(h);
   const double *P = h->buf.W_dev, *alpha = h->one.alpha_dev;
@@ -67,7 +79,7 @@ int loo_objective(mi_gp_handle* h, double* value, double* grad) {
   if (h->cv_block > 1) {
     const int r = cv_fold_pass(h, h->cv_block, fold_idx, fold_ptr, e, q, scal);
     if (r != 0) return r;
-    HCK(launch_cv_mirror_multiply(P, ld, cv_scratch(h).R, h->cv_block, n, np, B, ld, st), "cv_mirror_multiply");
+    HCK(launch_cv_mirror_multiply(P, ld, cv_R(h), h->cv_block, n, np, B, ld, st), "cv_mirror_multiply");
   } else {
     HCK(launch_loo_weights(P, ld, alpha, n, e, s, q, logp, scal, st), "loo_weights");
     HCK(launch_loo_scale_mirror(P, ld, s, n, np, B, ld, st), "loo_scale_mirror");
@@ -84,13 +96,5 @@ int loo_objective(mi_gp_handle* h, double* value, double* grad) {
   // below them, which hold zeros (include/mi_gp.h): B is taken out again, all of it
   HCK(hipMemset2DAsync(B, sizeof(double) * ld, 0, sizeof(double) * np, np, st), "Z_dev restore");
   HCK(hipStreamSynchronize(st), "stream sync");
-  const int bad = (int)sc[1];
-  if (bad != 0) {
-    *value = -INFINITY;
-    for (int i = 0; i < h->ntheta; ++i) grad[i] = 0.0;
-    return bad;
-  }
-  *value = sc[0];
-  for (int i = 0; i < h->ntheta; ++i) grad[i] = h->one.grad_host[i];
-  return 0;
+  return finish_objective(h, (int)sc[1], sc[0], value, grad);
 }

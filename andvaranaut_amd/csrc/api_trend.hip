@@ -52,39 +52,17 @@ TrendScratch trend_layout(double* base, int cap) {
   t.info = reinterpret_cast<int*>(t.scal + 8);
   return t;
 }
-TrendScratch trend_scratch(const mi_gp_handle* h) { return trend_layout(h->trend_dev, h->trend_cap); }
-
-int ensure_trend_scratch(mi_gp_handle* h) {
-  if (h->trend_dev && h->trend_cap >= h->cap) return 0;
-  (void)hipFree(h->trend_dev);
-  h->trend_dev = nullptr;
-  h->trend_cap = 0;
-  HCK(hipMalloc(&h->trend_dev, sizeof(double) * trend_scratch_len(h->cap)), "trend scratch");
-  h->trend_cap = h->cap;
-  return 0;
-}
+TrendScratch trend_scratch(const mi_gp_handle* h) { return trend_layout(h->trend_blk.p, h->trend_blk.cap); }
 
 // A = sum over k segments of GT[:, seg] B[seg]^T (B = V stored [k][x] for the fit, G^T itself for the conditional), C_A = chol(A)
 // in place, its row-major inverse, then u = GT x, c, beta^ and the scalars
 int trend_block(mi_gp_handle* h, const Eval& E, const TrendScratch& t, bool fit, const double* x) {
-  const int n = h->n, ntc = h->ntc, p = trend_columns(h);
+  const int n = h->n, p = trend_columns(h);
   const hipStream_t st = h->stream;
-  const int seg = (ntc + 63) / 64, nfull = ntc / seg, rem = ntc - nfull * seg;
-  const long kcols = seg * 128L;
-  if (fit) {
-    HCK(gemm_call(h, E, 0, 1, {t.GT, t.ldg, kcols}, {t.V, 128, kcols * 128}, {t.parts, 128, MINV_ELEMS}, 1, 1, seg * 128, 0, 0, 1.0, 0.0,
-                  nfull), "trend gram segments");
-    if (rem > 0)
-      HCK(gemm_call(h, E, 0, 1, {t.GT + nfull * kcols, t.ldg}, {t.V + nfull * kcols * 128, 128}, {t.parts + (long)nfull * MINV_ELEMS, 128}, 1,
-                    1, rem * 128, 0, 0, 1.0, 0.0, 1), "trend gram tail");
-  } else {
-    HCK(gemm_call(h, E, 0, 0, {t.GT, t.ldg, kcols}, {t.GT, t.ldg, kcols}, {t.parts, 128, MINV_ELEMS}, 1, 1, seg * 128, 0, 0, 1.0, 0.0, nfull),
-        "trend gram segments");
-    if (rem > 0)
-      HCK(gemm_call(h, E, 0, 0, {t.GT + nfull * kcols, t.ldg}, {t.GT + nfull * kcols, t.ldg}, {t.parts + (long)nfull * MINV_ELEMS, 128}, 1, 1,
-                    rem * 128, 0, 0, 1.0, 0.0, 1), "trend gram tail");
-  }
-  HCK(launch_trend_gram_sum(t.parts, nfull + (rem > 0 ? 1 : 0), p, t.A, st), "trend_gram_sum");
+  int nparts = 0;
+  if (fit) HCK(gram_segments(h, E, {t.GT, t.ldg}, {t.V, 128}, 1, t.parts, &nparts), "trend gram segments");
+  else HCK(gram_segments(h, E, {t.GT, t.ldg}, {t.GT, t.ldg}, 0, t.parts, &nparts), "trend gram segments");
+  HCK(launch_trend_gram_sum(t.parts, nparts, p, t.A, st), "trend_gram_sum");
   HCK(hipMemsetAsync(t.info, 0x7f, sizeof(int), st), "info reset");
   HCK(launch_potrf_leaf128(t.A, 128, t.minv, 0, t.info, st), "trend leaf");
   HCK(launch_tile_inverse_rows(t.A, 128, 0, t.Cinv, 0, 0, 1, 1, st), "trend inverse");
@@ -99,7 +77,7 @@ int trend_objective(mi_gp_handle* h, double* value, double* grad) {
   const int n = h->n, np = h->np, ntc = h->ntc, p = trend_columns(h);
   const long ld = h->buf.lda;
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  if (int r = ensure_trend_scratch(h)) return r;
+  if (stale_block(h, h->trend_blk)) HCK(resize_block(h->trend_blk, h->cap, trend_scratch_len(h->cap)), "trend scratch");
   const TrendScratch t = trend_scratch(h);
   const hipStream_t st = h->stream;
   const Eval E = one_eval(h);
@@ -119,20 +97,15 @@ int trend_objective(mi_gp_handle* h, double* value, double* grad) {
   const int info = (int)sc[2];
   if (info != INFO_OK) {
     snprintf(h->err, sizeof(h->err), "the trend's block H^T K^-1 H is not positive definite (pivot %d of the basis)", info);
-    *value = -INFINITY;
-    for (int i = 0; i < h->ntheta; ++i) grad[i] = 0.0;
-    return n + info;
   }
-  *value = h->one.out_host[0] + sc[0] - sc[1] + 0.5 * (double)p * 1.8378770664093453;
-  for (int i = 0; i < h->ntheta; ++i) grad[i] = h->one.grad_host[i];
-  return 0;
+  return finish_objective(h, info != INFO_OK ? n + info : 0, h->one.out_host[0] + sc[0] - sc[1] + 0.5 * (double)p * LOG_2PI, value, grad);
 }
 
 int trend_factor(mi_gp_handle* h) {
   const int n = h->n, np = h->np, p = trend_columns(h);
   const long ld = h->buf.lda;
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  if (int r = ensure_trend_scratch(h)) return r;
+  if (stale_block(h, h->trend_blk)) HCK(resize_block(h->trend_blk, h->cap, trend_scratch_len(h->cap)), "trend scratch");
   const TrendScratch t = trend_scratch(h);
   const hipStream_t st = h->stream;
   const Eval E = one_eval(h);
@@ -154,7 +127,7 @@ int trend_factor(mi_gp_handle* h) {
 
 hipError_t trend_predict_reduce(mi_gp_handle* h, const double* Xnew_dev, const double* work_dev, long ldw, int m, double* mean_dev,
                                 double* var_dev, int pred_noise) {
-  if (!h->trend_dev) return hipErrorInvalidValue;  // (mi_gp_factor under a trend allocates it; mi_gp_reserve ends `factored`)
+  if (!h->trend_blk.p) return hipErrorInvalidValue;  // (mi_gp_factor under a trend allocates it; mi_gp_reserve ends `factored`)
   const TrendScratch t = trend_scratch(h);
   double kd, noise;
   predict_scalars(h, pred_noise, &kd, &noise);
@@ -166,7 +139,7 @@ hipError_t trend_predict_reduce(mi_gp_handle* h, const double* Xnew_dev, const d
 // mi_gp_factor -- moves into the new block (the layout depends on the capacity), as mi_gp_reserve moves the leaf inverses and
 // alpha; everything else is written by the next call before it is read.  The handle's stream is idle (mi_gp_reserve).
 hipError_t trend_reserve(mi_gp_handle* h, int capacity) {
-  if (!h->trend_dev) return hipSuccess;
+  if (!h->trend_blk.p) return hipSuccess;
   double* fresh = nullptr;
   hipError_t e = hipMalloc(&fresh, sizeof(double) * trend_scratch_len(capacity));
   if (e != hipSuccess) return e;
@@ -181,8 +154,7 @@ hipError_t trend_reserve(mi_gp_handle* h, int capacity) {
     (void)hipFree(fresh);
     return e;
   }
-  (void)hipFree(h->trend_dev);
-  h->trend_dev = fresh;
-  h->trend_cap = capacity;
+  (void)hipFree(h->trend_blk.p);
+  h->trend_blk = {fresh, capacity};
   return hipSuccess;
 }

@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256) void lml_reduce_kernel(const double* __restric
     if (threadIdx.x == 0) {
       out[1] = s1[0];
       out[2] = s2[0];
-      out[0] = -0.5 * (double)n * 1.8378770664093453 - 0.5 * s2[0] - s1[0];
+      out[0] = -0.5 * (double)n * LOG_2PI - 0.5 * s2[0] - s1[0];
       if (info) out[3] = (double)info[0];
     }
     return;
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void lml_reduce_kernel(const double* __restric
     }
     out[1] = t1;
     out[2] = t2;
-    out[0] = -0.5 * (double)n * 1.8378770664093453 - 0.5 * t2 - t1;
+    out[0] = -0.5 * (double)n * LOG_2PI - 0.5 * t2 - t1;
     if (info) out[3] = (double)info[0];  // the bad-pivot word rides in the same download as the scalars
     *sync = 0u;                          // ready for the next evaluation
     // the evaluation's sequence number, LAST and released at system scope: a host that spins on it (pinned, coherent memory)

@@ -7,11 +7,9 @@
 // and from B on the tail is the leave-one-out one.  The fold kernel is memory-bound; the multiply runs on
 // v_mfma_f64_16x16x4_f64 (2 * 128 * np * n flops whatever b is).  Every sum runs in a fixed order.
 #include <cmath>
-#include "migp_kernels.h"
+#include "symm_chunk.h"
 
 namespace migp {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 // One workgroup per fold, thread j = position j of the fold (kfold_moments_kernel's layout, and its density: kfold_fold_logp).
 // Row i of R_f goes to row p0 + i of R (128 columns, zeros from the fold's size on).
@@ -52,8 +50,6 @@ __global__ __launch_bounds__(128) void cv_fold_kernel(const double* __restrict__
 // reduction over folds).
 __global__ __launch_bounds__(256) void cv_reduce_kernel(const double* __restrict__ flogp, const int* __restrict__ ptr,
                                                         const int* __restrict__ info, int nfolds, double* __restrict__ scal) {
-  __shared__ double sum[256];
-  __shared__ int bad[256];
   const int t = threadIdx.x;
   double acc = 0.0;
   int first = 0x7fffffff;
@@ -61,37 +57,25 @@ __global__ __launch_bounds__(256) void cv_reduce_kernel(const double* __restrict
     acc += flogp[f];
     if (info[f] != INFO_OK) first = min(first, ptr[f] + info[f]);
   }
-  sum[t] = acc;
-  bad[t] = first;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      sum[t] += sum[t + w];
-      bad[t] = min(bad[t], bad[t + w]);
-    }
-    __syncthreads();
-  }
+  tree_sum_first_256(acc, first);
   if (t == 0) {
-    scal[0] = sum[0];
-    scal[1] = bad[0] == 0x7fffffff ? 0.0 : (double)bad[0];
+    scal[0] = acc;
+    scal[1] = first == 0x7fffffff ? 0.0 : (double)first;
   }
 }
 
 // Workgroup (g, rb): rows 64 rb .. 64 rb + 63 of B in the columns of fold group g -- as many whole folds as fit 128 columns
 // (gb = max(1, 128 / b) * b columns from c0 = g gb; the last group is ragged), which are not aligned to tiles.  The group's factor
 // is the block-diagonal matrix of its folds' R_f, so B[rows, c0 .. c0 + cw) = Pfull[rows, c0 .. c0 + cw) blockdiag(R_f): k runs in
-// chunks of 32 through LDS, As = the chunk's columns of Pfull for the 64 rows, element (i, j) from W[max(i, j)][min(i, j)]
-// (straight part read along rows of W, mirrored part along columns: the strict upper triangle of W is scratch and never read;
-// zeros in the rows from n on and in the k padding), Rs = the chunk's rows of the block-diagonal factor.  Wave w takes the rows
-// 16 w .. 16 w + 15 and every 16-column block; a block whose folds do not meet the chunk adds nothing and is passed over.
-// Lane maps (gemm_f64.hip): A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], D[(l >> 4) + 4 r][l & 15].
-// LDS: rows of 34 doubles in As (the 16 rows x 2 k of a half-wave's A read land on 32 distinct bank pairs) and 144 in Rs (two k
-// rows of a half-wave's B read 16 bank pairs apart).  The group one past the last (np > n) writes the zero columns n .. np - 1.
-constexpr int CV_KC = 32, CV_ALD = 34, CV_RLD = 144;
+// chunks of 32 through LDS (symm_chunk.h), As = the chunk's columns of Pfull for the 64 rows (zeros in the rows from n on and in
+// the k padding), Rs = the chunk's rows of the block-diagonal factor.  Every 16-column block is a candidate; one whose folds do
+// not meet the chunk adds nothing and is passed over.  Rs has rows of 144 doubles (two k rows of a half-wave's B read 16 bank
+// pairs apart).  The group one past the last (np > n) writes the zero columns n .. np - 1.
+constexpr int CV_RLD = 144;
 __global__ __launch_bounds__(256) void cv_mirror_multiply_kernel(const double* __restrict__ W, long ldw, const double* __restrict__ R,
                                                                  int b, int gb, int ngroups, int n, double* __restrict__ B, long ldb) {
-  __shared__ double As[64 * CV_ALD];
-  __shared__ double Rs[CV_KC * CV_RLD];
+  __shared__ double As[64 * SYMM_ALD];
+  __shared__ double Rs[SYMM_KC * CV_RLD];
   const int g = blockIdx.x, i0 = blockIdx.y * 64, t = threadIdx.x;
   if (g == ngroups) {
     const int cw = gridDim.y * 64 - n;
@@ -106,35 +90,19 @@ __global__ __launch_bounds__(256) void cv_mirror_multiply_kernel(const double* _
   double4_t acc[8];
 #pragma unroll
   for (int cb = 0; cb < 8; ++cb) acc[cb] = double4_t{0.0, 0.0, 0.0, 0.0};
-  for (int kc = 0; kc < cw; kc += CV_KC) {
-    for (int x = t; x < 64 * CV_KC; x += 256) {  // on and below the diagonal: along the rows of W
-      const int r = x >> 5, kk = x & 31, i = i0 + r, j = c0 + kc + kk;
-      if (kc + kk >= cw || i >= n) As[r * CV_ALD + kk] = 0.0;
-      else if (i >= j) As[r * CV_ALD + kk] = W[(long)i * ldw + j];
-    }
-    for (int x = t; x < 64 * CV_KC; x += 256) {  // above it: the mirror image, along the rows of W again
-      const int kk = x >> 6, r = x & 63, i = i0 + r, j = c0 + kc + kk;
-      if (kc + kk < cw && i < n && i < j) As[r * CV_ALD + kk] = W[(long)j * ldw + i];
-    }
-    for (int x = t; x < CV_KC * 128; x += 256) {
+  for (int kc = 0; kc < cw; kc += SYMM_KC) {
+    symm_stage_chunk(W, ldw, n, i0, c0 + kc, c0 + cw, As);
+    for (int x = t; x < SYMM_KC * 128; x += 256) {
       const int kk = x >> 7, k = kc + kk;
       if (rc < ncb * 16)
         Rs[kk * CV_RLD + rc] = (rlive && k < cw && k >= rlo && k < rlo + b) ? R[(long)(c0 + k) * 128 + (rc - rlo)] : 0.0;
     }
     __syncthreads();
-    double a[CV_KC / 4];
-#pragma unroll
-    for (int ks = 0; ks < CV_KC / 4; ++ks) a[ks] = As[(16 * wv + l15) * CV_ALD + 4 * ks + l4];
-#pragma unroll
-    for (int cb = 0; cb < 8; ++cb) {
+    symm_chunk_mfma(As, Rs, CV_RLD, [&](int cb) {
       // the k range of the folds that meet this column block
       const int klo = 16 * cb / b * b, khi = ((16 * cb + 15) / b + 1) * b;
-      if (cb < ncb && khi > kc && klo < kc + CV_KC) {
-#pragma unroll
-        for (int ks = 0; ks < CV_KC / 4; ++ks)
-          acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], Rs[(4 * ks + l4) * CV_RLD + 16 * cb + l15], acc[cb], 0, 0, 0);
-      }
-    }
+      return cb < ncb && khi > kc && klo < kc + SYMM_KC;
+    }, acc);
     __syncthreads();
   }
 #pragma unroll

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <vector>
 #include "migp_kernels.h"
 #include "../../include/mi_gp.h"
@@ -28,6 +29,13 @@ struct Scratch {
   double* grad_host = nullptr;  // pinned [k][ntheta]
   double* out_host = nullptr;   // pinned [k][16] scalar records
   double* theta_host = nullptr; // pinned [k][ntheta]
+};
+
+// A device block sized by point capacity.  Its owner re-sizes it before use once the handle's capacity has outgrown it
+// (stale_block / resize_block); mi_gp_reserve drops it, or moves what must outlive the call (trend_reserve).
+struct CapBlock {
+  double* p = nullptr;
+  int cap = 0;  // points p is sized for
 };
 
 struct mi_gp_handle {
@@ -118,19 +126,14 @@ struct mi_gp_handle {
   double* app_stats_dev;   // [4] mi_gp_append's scalar increments and bad-pivot word
   int objective;           // option 48: what mi_gp_lml_grad returns -- 0 the log marginal likelihood, 1 the leave-one-out log
                            // predictive density (loo_objective() behind the ordinary evaluation)
-  double* loo_vec_dev;     // [LOO_VECS][padded loo_cap] e, s, q, w, the zero vector and the per-point logp, then [8] scalars
-                           // (allocated by the first evaluation under option 48 = 1; mi_gp_reserve drops it, the next one re-sizes it)
-  int loo_cap;             // points loo_vec_dev is sized for
+  CapBlock loo;            // [6][padded loo.cap] e, s, q, w, the zero vector and the per-point logp, then [8] scalars
+                           // (api_loo.hip; allocated by the first evaluation under option 48 = 1)
   int cv_block;            // option 49: the fold size b of the objective under option 48 = 1 -- 1 (default) leave-one-out, 2..128 the
                            // leave-block-out density over the contiguous folds [f b, min((f + 1) b, n))
-  double* cv_dev;          // the fold pass of that objective (CvScratch; allocated by the first evaluation with b > 1, re-sized like
-                           // loo_vec_dev)
-  int cv_cap;              // points cv_dev is sized for
+  CapBlock cv;             // the fold pass of that objective (cv_fold_pass(), api_loo.hip; allocated by the first evaluation with b > 1)
   int trend;               // option 50: the TREND whose coefficients are integrated out -- 0 none, 1 constant h = [1], 2 linear
                            // h = [1, x_1 .. x_d] (mi_gp_lml_grad, mi_gp_factor and mi_gp_predict; api_trend.hip)
-  double* trend_dev;       // its scratch (TrendScratch, api_trend.hip; allocated by the first use, dropped by mi_gp_reserve and
-                           // re-sized by the next use)
-  int trend_cap;           // points trend_dev is sized for
+  CapBlock trend_blk;      // its scratch (TrendScratch, api_trend.hip; allocated by the first use)
   char err[256];
 };
 
@@ -138,6 +141,17 @@ inline int hfail(mi_gp_handle* h, hipError_t e, const char* where) {
   snprintf(h->err, sizeof(h->err), "%s: %s", where, hipGetErrorString(e));
   return -2;
 }
+
+// frees b, then allocates len doubles for cap points (len = 0: none); what it held is not kept
+inline hipError_t resize_block(CapBlock& b, int cap, size_t len) {
+  (void)hipFree(b.p);
+  b = CapBlock();
+  const hipError_t e = len ? hipMalloc(&b.p, sizeof(double) * len) : hipSuccess;
+  if (e == hipSuccess && len) b.cap = cap;
+  return e;
+}
+inline bool stale_block(const mi_gp_handle* h, const CapBlock& b) { return !b.p || b.cap < h->cap; }
+
 #define HCK(call, where)                          \
   do {                                            \
     hipError_t e__ = (call);                      \
@@ -212,39 +226,45 @@ int make_u_resident(mi_gp_handle* h);  // U = L^-T in Z_dev and alpha = U beta, 
 // stats = {sum log diag L22, |beta2|^2, bad-pivot word}; 0 or a C-ABI error code
 int conditional_block(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
                       double* work_dev, long ldw, double stats[3]);
-// the handle's vectors of the leave-one-out objective for up to cap points (zeroed; what they held is not kept)
-constexpr int LOO_VECS = 6;
-hipError_t size_loo_vectors(mi_gp_handle* h, int cap);
-// The handle's scratch of the k-fold objective's fold pass for up to cap points, as mi_gp_kfold lays a work block out: `pass`
-// gathered blocks, `pass` leaf inverses and `pass` x 256 gathered vectors (pass = the folds of one pass: no result depends on it),
-// then R [padded cap][128], the per-fold logp [padded cap] and as ints the contiguous index list, the fold pointers and one
-// bad-pivot word per fold.  What it held is not kept.
-struct CvScratch {
+// What mi_gp_lml_grad and the objectives behind it hand back: a bad code gives -inf, a zero gradient and the code, 0 the value and
+// the gradient the contraction left in grad_host
+inline int finish_objective(const mi_gp_handle* h, int bad, double value, double* value_out, double* grad_out) {
+  *value_out = bad ? -INFINITY : value;
+  for (int i = 0; i < h->ntheta; ++i) grad_out[i] = bad ? 0.0 : h->one.grad_host[i];
+  return bad;
+}
+
+// The k-segmented 128 x 128 Gram product A B^T (bk = 0: B stored like A, [128][k]) or A B (bk = 1: B stored [k][128]) over
+// k = 128 ntc (api_gp.hip): a single output tile over all of k would run on four workgroups, so k is cut into segments of
+// (ntc + 63) / 64 tile columns -- one node-batched launch over the full segments, one over the tail -- whose 128 x 128 products go
+// to parts, MINV_ELEMS apart (at most 65).  *nparts = how many there are, for a kernel that adds them in index order.
+hipError_t gram_segments(mi_gp_handle* h, const Eval& E, In A, In B, int bk, double* parts, int* nparts);
+
+// api_kfold.hip: the work block of a fold pass for `pass` folds at a time -- `pass` gathered blocks (the leaf factorises them in
+// place), `pass` leaf inverses and `pass` x 256 gathered alpha_I / y_I, then as ints the staged fold_idx [total], fold_ptr
+// [nfolds + 1] and one bad-pivot word per fold [nfolds] (nfolds <= total: 2 * total + 2 doubles hold them)
+struct FoldWork {
   int pass;
-  double *blocks, *minv, *vecs, *R, *flogp;
+  double *blocks, *minv, *vecs;
   int *idx, *ptr, *info;
 };
-constexpr int CV_PASS_MAX = 128;
-inline int cv_pass(int cap) { return cap / 2 + 1 < CV_PASS_MAX ? cap / 2 + 1 : CV_PASS_MAX; }  // (folds of two points or more)
-inline size_t cv_scratch_len(int cap) {
-  const size_t vl = (size_t)(cap + 127) / 128 * 128;
-  return (size_t)cv_pass(cap) * (2 * MINV_ELEMS + 256) + vl * 128 + vl + 2 * vl + 2;
+inline long fold_work_len(long pass, long total) { return pass * (2 * MINV_ELEMS + 256) + 2 * total + 2; }
+inline FoldWork fold_layout(double* base, long pass, long total, int nfolds) {
+  FoldWork w;
+  w.pass = (int)pass;
+  w.blocks = base;
+  w.minv = w.blocks + pass * MINV_ELEMS;
+  w.vecs = w.minv + pass * MINV_ELEMS;
+  w.idx = reinterpret_cast<int*>(w.vecs + pass * 256);
+  w.ptr = w.idx + total;
+  w.info = w.ptr + nfolds + 1;
+  return w;
 }
-inline CvScratch cv_scratch(const mi_gp_handle* h) {
-  const long vl = (h->cv_cap + 127) / 128 * 128, P = cv_pass(h->cv_cap);
-  CvScratch c;
-  c.pass = (int)P;
-  c.blocks = h->cv_dev;
-  c.minv = c.blocks + P * MINV_ELEMS;
-  c.vecs = c.minv + P * MINV_ELEMS;
-  c.R = c.vecs + P * 256;
-  c.flogp = c.R + vl * 128;
-  c.idx = reinterpret_cast<int*>(c.flogp + vl);
-  c.ptr = c.idx + vl;
-  c.info = c.ptr + vl + 1;
-  return c;
-}
-hipError_t size_cv_scratch(mi_gp_handle* h, int cap);
+// The fold pass over the resident K^-1 and alpha: the host lists go up (they must live until the stream is synchronised), then
+// per pass of w.pass folds launch_kfold_gather, the batched 128 x 128 leaf and the caller's step(f0, nf) for the folds
+// f0 .. f0 + nf - 1, all on the handle's stream; 0 or a C-ABI error code
+int fold_pass(mi_gp_handle* h, const FoldWork& w, int nfolds, const int* ptr_host, const int* idx_host,
+              const std::function<hipError_t(int, int)>& step);
 
 // api_loo.hip: the tail of mi_gp_lml_grad under option 48 = 1, behind a successful ordinary evaluation (K^-1 in W_dev, alpha
 // resident).  *value = L_LOO and grad[ntheta] its gradient; 0, the 1-based index of the first bad K^-1_ii (-inf, zero gradient) or

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void kfold_loo_kernel(const double* __restrict
   const bool ok = k > 0.0;
   const double v = 1.0 / k;
   info[f] = ok ? 0 : 1;
-  logp[f] = ok ? 0.5 * log(k) - 0.5 * a * a * v - 0.5 * KFOLD_LOG_2PI : -INFINITY;
+  logp[f] = ok ? 0.5 * log(k) - 0.5 * a * a * v - 0.5 * LOG_2PI : -INFINITY;
   if (mean != nullptr) {
     mean[f] = ok ? y[i] - a * v : NAN;
     var[f] = ok ? v : NAN;

@@ -11,7 +11,6 @@
 
 namespace migp {
 
-constexpr double LOO_LOG_2PI = 1.8378770664093453;
 constexpr int LT = 64;  // tile of the mirror / rank-2 kernels
 
 // One workgroup: thread t takes the points t, t + 256, ... in order, the 256 partial sums meet in a fixed tree.
@@ -21,8 +20,6 @@ __global__ __launch_bounds__(256) void loo_weights_kernel(const double* __restri
                                                           int n, double* __restrict__ e, double* __restrict__ s,
                                                           double* __restrict__ q, double* __restrict__ logp,
                                                           double* __restrict__ scal) {
-  __shared__ double sum[256];
-  __shared__ int bad[256];
   const int t = threadIdx.x;
   double acc = 0.0;
   int first = 0x7fffffff;
@@ -30,7 +27,7 @@ __global__ __launch_bounds__(256) void loo_weights_kernel(const double* __restri
     const double k = W[(long)i * ld + i], a = alpha[i];
     const bool ok = k > 0.0 && k < INFINITY;
     const double v = 1.0 / k;
-    const double lp = ok ? 0.5 * log(k) - 0.5 * a * a * v - 0.5 * LOO_LOG_2PI : -INFINITY;
+    const double lp = ok ? 0.5 * log(k) - 0.5 * a * a * v - 0.5 * LOG_2PI : -INFINITY;
     const double ei = a * v, si = sqrt((1.0 + a * a * v) * v);
     e[i] = ok ? ei : 0.0;
     s[i] = ok ? si : 0.0;
@@ -39,19 +36,10 @@ __global__ __launch_bounds__(256) void loo_weights_kernel(const double* __restri
     acc += lp;
     if (!ok && i < first) first = i;
   }
-  sum[t] = acc;
-  bad[t] = first;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      sum[t] += sum[t + w];
-      bad[t] = min(bad[t], bad[t + w]);
-    }
-    __syncthreads();
-  }
+  tree_sum_first_256(acc, first);
   if (t == 0) {
-    scal[0] = sum[0];
-    scal[1] = bad[0] == 0x7fffffff ? 0.0 : (double)(bad[0] + 1);
+    scal[0] = acc;
+    scal[1] = first == 0x7fffffff ? 0.0 : (double)(first + 1);
   }
 }
 

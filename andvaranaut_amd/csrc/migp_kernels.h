@@ -19,6 +19,28 @@ struct Batch {
   long swork = 0;               // ... prediction work blocks (mi_gp_predict_batch: K(X*, X) -> L^-1 K(X, X*), one per problem)
 };
 
+constexpr double LOG_2PI = 1.8378770664093453;
+
+// The (sum, first bad index) pairs of a workgroup of 256 threads meet in a fixed tree: every thread gets the sum and the
+// smallest index (a thread without one passes 0x7fffffff).
+__device__ __forceinline__ void tree_sum_first_256(double& acc, int& first) {
+  __shared__ double sum[256];
+  __shared__ int bad[256];
+  const int t = threadIdx.x;
+  sum[t] = acc;
+  bad[t] = first;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+      sum[t] += sum[t + w];
+      bad[t] = min(bad[t], bad[t + w]);
+    }
+    __syncthreads();
+  }
+  acc = sum[0];
+  first = bad[0];
+}
+
 // ---------------------------------------------------------------- gemm_f64.hip
 // C[mt*128 x nt*128] = beta*C + alpha * op(A) * op(B), all fp64 row-major with leading dimensions.
 struct GemmParams {
@@ -287,7 +309,6 @@ hipError_t launch_kfold_loo(const double* W, long ld, const double* alpha, const
 // a workgroup of 128 threads, thread j = position j of a fold of s points, C = chol(K^-1_II) row-major, M = C^-1 in minv_index
 // order, al = alpha_I.  tv / s1 / s2: 128 doubles of LDS each.  Returns logp on every thread; afterwards tv holds t = M alpha_I
 // (zeros from s on) and s2[0] = |t|^2.  Every sum runs in a fixed order.
-constexpr double KFOLD_LOG_2PI = 1.8378770664093453;
 __device__ __forceinline__ double kfold_fold_logp(const double* __restrict__ C, const double* __restrict__ M,
                                                   const double* __restrict__ al, int j, int s, double* tv, double* s1, double* s2) {
   double t = 0.0;
@@ -301,7 +322,7 @@ __device__ __forceinline__ double kfold_fold_logp(const double* __restrict__ C, 
     if (j < w) { s1[j] += s1[j + w]; s2[j] += s2[j + w]; }
     __syncthreads();
   }
-  return -0.5 * s2[0] + s1[0] - 0.5 * (double)s * KFOLD_LOG_2PI;
+  return -0.5 * s2[0] + s1[0] - 0.5 * (double)s * LOG_2PI;
 }
 
 // ---------------------------------------------------------------- cvobj_f64.hip (option 49: the k-fold objective, api_loo.hip)

@@ -5,11 +5,9 @@
 // each lower element once straight and once mirrored) for 2 * 16 ceil(p/16) np^2 flops on v_mfma_f64_16x16x4_f64.  Every sum runs in a
 // fixed order; nothing is accumulated with atomics.
 #include <cmath>
-#include "migp_kernels.h"
+#include "symm_chunk.h"
 
 namespace migp {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 // HT[c][i] = h_c(x_i) for c < p, i < n; zeros up to row 127 and column np - 1
 __global__ __launch_bounds__(256) void trend_basis_kernel(const double* __restrict__ X, int n, int d, int p, int np,
@@ -21,63 +19,38 @@ __global__ __launch_bounds__(256) void trend_basis_kernel(const double* __restri
 }
 
 // Workgroup (rb, s): rows 64 rb .. 64 rb + 63 of slice s of V = Pfull H in the 16 ncb leading columns, Pfull[i][j] =
-// W[max(i, j)][min(i, j)] for i, j < n and zero beyond.  k runs in chunks of 32 through LDS: As = the chunk's columns of Pfull for
-// the 64 rows, Hs = the chunk's rows of H (columns of HT).  A chunk left of the diagonal block is read along the rows of W (32
-// consecutive doubles per row), one right of it is the mirror image and is read along the rows of W again (64 consecutive
-// doubles per row); only the chunks that cross the diagonal mix both.  The strict upper triangle of W is never read.  Wave w
-// takes the rows 16 w .. 16 w + 15 and every 16-column block.  Lane maps (gemm_f64.hip): A[i = l & 15][k = l >> 4],
-// B[k = l >> 4][j = l & 15], D[(l >> 4) + 4 r][l & 15].  LDS rows of 34 doubles in As (as cv_mirror_multiply_kernel's) and of
-// 16 ncb + 16 or + 32 in Hs (an odd number of 16-double groups: the two k rows of a half-wave's B read land on disjoint banks).
+// W[max(i, j)][min(i, j)] for i, j < n and zero beyond.  k runs in chunks of 32 through LDS (symm_chunk.h): As = the chunk's
+// columns of Pfull for the 64 rows, Hs = the chunk's rows of H (columns of HT), in rows of 16 ncb + 16 or + 32 doubles (an odd
+// number of 16-double groups: the two k rows of a half-wave's B read land on disjoint banks).
 // The kernel is bound by the latency of its loads, so the k range is cut into nslice slices of whole chunks that run side by
 // side (a workgroup keeps 16 KB in flight; four or five of them fit a CU): slice s writes its partial product, 16 ncb columns
 // wide, to out + s np ldo, and trend_slice_sum_kernel adds the slices in index order.  nslice == 1 writes V itself (ldo = 128),
 // with zeros in the columns from 16 ncb on: all of the np x 128 block is written either way.
-constexpr int TR_KC = 32, TR_ALD = 34;
 __host__ __device__ inline int trend_hld(int ncb) { return 16 * ncb + ((ncb & 1) ? 32 : 16); }
 __global__ __launch_bounds__(256) void trend_symm_kernel(const double* __restrict__ W, long ldw, const double* __restrict__ HT,
                                                          long ldg, int n, int np, int ncb, int nslice, double* __restrict__ out,
                                                          int ldo) {
   extern __shared__ double tr_lds[];
   double* As = tr_lds;
-  double* Hs = tr_lds + 64 * TR_ALD;
+  double* Hs = tr_lds + 64 * SYMM_ALD;
   const int hld = trend_hld(ncb);
   const int i0 = blockIdx.x * 64, t = threadIdx.x;
   const int lane = t & 63, wv = t >> 6, l15 = lane & 15, l4 = lane >> 4;
-  const int nch = np / TR_KC, sl = blockIdx.y;
+  const int nch = np / SYMM_KC, sl = blockIdx.y;
   const int ch0 = (int)((long)sl * nch / nslice), ch1 = (int)((long)(sl + 1) * nch / nslice);
   out += (long)sl * np * ldo;
   double4_t acc[8];
 #pragma unroll
   for (int cb = 0; cb < 8; ++cb) acc[cb] = double4_t{0.0, 0.0, 0.0, 0.0};
   for (int ch = ch0; ch < ch1; ++ch) {
-    const int kc = ch * TR_KC;
-    if (kc > i0 + 63) {  // every column of the chunk lies right of every row: the mirror image
-      for (int x = t; x < 64 * TR_KC; x += 256) {
-        const int kk = x >> 6, r = x & 63, i = i0 + r, j = kc + kk;
-        As[r * TR_ALD + kk] = (i < n && j < n) ? W[(long)j * ldw + i] : 0.0;
-      }
-    } else {
-      for (int x = t; x < 64 * TR_KC; x += 256) {
-        const int r = x >> 5, kk = x & 31, i = i0 + r, j = kc + kk;
-        As[r * TR_ALD + kk] = (i < n && j < n) ? (i >= j ? W[(long)i * ldw + j] : W[(long)j * ldw + i]) : 0.0;
-      }
-    }
-    for (int x = t; x < 16 * ncb * TR_KC; x += 256) {
+    const int kc = ch * SYMM_KC;
+    symm_stage_chunk(W, ldw, n, i0, kc, n, As);
+    for (int x = t; x < 16 * ncb * SYMM_KC; x += 256) {
       const int c = x >> 5, kk = x & 31;
       Hs[kk * hld + c] = HT[c * ldg + kc + kk];
     }
     __syncthreads();
-    double a[TR_KC / 4];
-#pragma unroll
-    for (int ks = 0; ks < TR_KC / 4; ++ks) a[ks] = As[(16 * wv + l15) * TR_ALD + 4 * ks + l4];
-#pragma unroll
-    for (int cb = 0; cb < 8; ++cb) {
-      if (cb < ncb) {
-#pragma unroll
-        for (int ks = 0; ks < TR_KC / 4; ++ks)
-          acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], Hs[(4 * ks + l4) * hld + 16 * cb + l15], acc[cb], 0, 0, 0);
-      }
-    }
+    symm_chunk_mfma(As, Hs, hld, [&](int cb) { return cb < ncb; }, acc);
     __syncthreads();
   }
 #pragma unroll
@@ -250,13 +223,13 @@ hipError_t launch_trend_basis(const double* X, int n, int d, int p, int np, doub
 int trend_symm_slices(int np, int p) {
   const int ncb = (p + 15) / 16, fit = 128 / (16 * ncb), want = (1280 + np / 64 - 1) / (np / 64);
   const int s = want < fit ? want : fit;
-  return s < 1 ? 1 : s > np / TR_KC ? np / TR_KC : s;
+  return s < 1 ? 1 : s > np / SYMM_KC ? np / SYMM_KC : s;
 }
 
 hipError_t launch_trend_symm(const double* W, long ldw, const double* HT, long ldg, int n, int np, int p, double* V, double* parts,
                              hipStream_t stream) {
   const int ncb = (p + 15) / 16, ns = trend_symm_slices(np, p);
-  const size_t lds = sizeof(double) * (64 * TR_ALD + TR_KC * trend_hld(ncb));
+  const size_t lds = sizeof(double) * (64 * SYMM_ALD + SYMM_KC * trend_hld(ncb));
   if (ns == 1) {
     trend_symm_kernel<<<dim3(np / 64, 1), 256, lds, stream>>>(W, ldw, HT, ldg, n, np, ncb, 1, V, 128);
     return hipGetLastError();

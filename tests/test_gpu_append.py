@@ -101,6 +101,35 @@ def test_sequence_of_appends_matches_one_factorisation():
     fresh.close()
 
 
+def test_append_at_65_tile_columns_runs_the_tail_segment():
+    """n0 = 8200 pads to 65 tile columns: L21 L21^T is cut into 32 segments of two tile columns and a TAIL of one, the second
+    launch of gram_segments (csrc/api_gp.hip) that no smaller size reaches.  One append of 120 points to 8320 (65 tile columns
+    still), compared as test_sequence_of_appends_matches_one_factorisation compares: against a fresh factorisation of all points
+    on the device, through both prediction routes and the factorisation's parts."""
+    from andvaranaut_amd import MiGP
+
+    d, n0, n1 = 4, 8200, 8320
+    X, y = orc.synth_problem(n1, d, seed=17)
+    theta = orc.synth_theta(d, nkern=1, gv=1e-2, jitter=1e-6)
+    Xs = np.random.default_rng(3).random((37, d))
+    gp = MiGP(X[:n0], y[:n0], "Matern52", device=0, capacity=n1)
+    assert gp.factor(theta) == 0
+    gp.predict(theta, Xs, via_inverse=True)
+    assert gp.append(X[n0:], y[n0:]) == 0
+    assert gp.n == n1 and gp.append_refactors == 0
+    fresh = MiGP(X, y, "Matern52", device=0)
+    assert fresh.factor(theta) == 0
+    for via in (False, True):
+        for a, b in zip(gp.predict(theta, Xs, via_inverse=via), fresh.predict(theta, Xs, via_inverse=via)):
+            print("via_inverse", via, "error / bound %.3g" % (np.max(np.abs(a - b)) / (1e-10 * max(np.max(np.abs(b)), 1.0))))
+            assert _close(a, b, 1e-10)
+    for a, b in zip(gp.lml_parts(), fresh.lml_parts()):
+        print("part error / bound %.3g" % (abs(a - b) / (1e-10 * max(abs(b), 1.0))))
+        assert abs(a - b) <= 1e-10 * max(abs(b), 1.0)
+    gp.close()
+    fresh.close()
+
+
 def test_capacity_overflow_refactorises_once_with_the_same_results():
     from andvaranaut_amd import MiGP
 

@@ -108,6 +108,25 @@ def test_the_rank_128_update_on_128_tiles_at_46_tile_columns():
     gp.close()
 
 
+def test_the_gram_product_at_65_tile_columns_runs_the_tail_segment():
+    """N = 8320, d = 4, constant trend: 65 tile columns, so A = H^T V is cut into 32 segments of two tile columns and a TAIL of one,
+    the second launch of gram_segments (csrc/api_gp.hip) that no smaller size reaches.  The value against the projected-data
+    definition (trend_ref.trend_projected_large) under test_value_and_gradient_parity's bound for the value, with cond(K) by the
+    Gershgorin bound over the noise floor as in the test above.  No gradient: its references take minutes at this size."""
+    from oracle import gp_oracle as orc
+
+    kernel, n, d = "RBF", 8320, 4
+    X, y, theta, diag = loo_ref.make_problem(kernel, n, d, False, 1e-2, 65)
+    cond = np.abs(orc.noisy_cov(X, [kernel], [], theta, "marginal", diag)).sum(1).max() / (theta[-1] + theta[-2])
+    v_ref = ref.trend_projected_large(X, y, kernel, theta, 1, diag)
+    gp = _gp(X, y, kernel, diag, "constant")
+    val, _ = gp.lml_grad(theta)
+    rv = loo_ref.value_ratio(val, v_ref, cond)
+    print((kernel, n, d), "cond <= %.3g" % cond, "error / bound: value %.3g" % rv)
+    assert gp.info == 0 and rv <= 1.0, (rv, val, v_ref)
+    gp.close()
+
+
 @pytest.mark.parametrize("i,order", ref.CASE_IDS)
 def test_predict_parity_inside_and_outside_the_design(i, order):
     """m = 9 (the pinned route, an odd count) and m = 300 (device buffers, three tile rows of work_dev, the last one ragged)"""

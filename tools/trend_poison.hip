@@ -5,10 +5,10 @@
 
 extern "C" __attribute__((visibility("default"))) long trend_poison(mi_gp_handle* h) {
   if (!h) return -1;
-  if (!h->trend_dev) return 0;
-  const size_t len = trend_scratch_len(h->trend_cap);
+  if (!h->trend_blk.p) return 0;
+  const size_t len = trend_scratch_len(h->trend_blk.cap);
   if (hipSetDevice(h->device) != hipSuccess) return -1;
-  if (hipMemsetAsync(h->trend_dev, 0xff, sizeof(double) * len, h->stream) != hipSuccess) return -1;
+  if (hipMemsetAsync(h->trend_blk.p, 0xff, sizeof(double) * len, h->stream) != hipSuccess) return -1;
   if (hipStreamSynchronize(h->stream) != hipSuccess) return -1;
   return (long)len;
 }
