@@ -150,6 +150,7 @@ class MiGP:
     def lml(self, theta):
         """LML at natural-scale theta; -inf if K is not positive definite (info > 0)."""
         self._no_trend("lml")
+        self._no_outputs("lml")
         theta, tp = self._theta(theta)
         out = ctypes.c_double()
         self._factored_ok = False
@@ -168,8 +169,12 @@ class MiGP:
         """(LML, dLML/dtheta) at natural-scale theta; (-inf, zeros) if K is not positive definite."""
         if self.Z_t is None:
             raise RuntimeError("this MiGP was created with need_grad=False")
+        if self.nout > 1 and self._trend != 0:
+            self._no_outputs("a trend")
         if self._trend != 0 and self.get_option(48) == 1:
             self._no_trend("a cross-validation objective")
+        if self.nout > 1 and self.get_option(48) == 1:
+            self._no_outputs("a cross-validation objective")
         theta, tp = self._theta(theta)
         out = ctypes.c_double()
         grad = np.zeros(self.ntheta)
@@ -214,6 +219,45 @@ class MiGP:
         if self._trend != 0:
             name = [k for k, v in self.TRENDS.items() if v == self._trend][0]
             raise ValueError(f"{what} has no form under a trend (set_trend({name!r}) is in force): set_trend('none') first")
+
+    nout = 1
+
+    def set_outputs(self, Y):
+        """The outputs of the model (option 51 of mi_gp_set_option): Y is (n, q) float64, finite, 1 <= q <= 128.  Under q >= 2 the q
+        columns are modelled under ONE shared kernel and one noise, independent given theta: lml_grad returns the sum of the
+        outputs' log marginal likelihoods and its exact theta gradient, factor + predict a mean of shape (m, q) and the variance
+        (m,) every output shares; every other evaluation raises ValueError until set_outputs is called with one column, which
+        returns to the single-output state.  The columns live in one (q, lda) tensor, output o in row o; the data are rebound,
+        which ends the resident factorisation."""
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y.reshape(-1, 1)
+        if Y.ndim != 2 or Y.shape[0] != self.n or not 1 <= Y.shape[1] <= 128:
+            raise ValueError(f"the outputs Y must be (n, q) with n = {self.n} and 1 <= q <= 128")
+        if not np.isfinite(Y).all():
+            raise ValueError("the outputs Y must be finite")
+        q = Y.shape[1]
+        with torch.cuda.device(self.dev):
+            store = torch.zeros((q, self.lda), dtype=torch.float64, device=self.dev)
+            store[:, : self.n].copy_(torch.from_numpy(np.ascontiguousarray(Y.T)))
+            torch.cuda.synchronize(self.dev)
+        self._Y_store = store
+        if self.capacity is not None:  # (row 0 holds lda >= capacity doubles: room for appended points once q is 1 again)
+            self._y_store = store[0]
+        self.y_t = store[0, : self.n]
+        self._bad_y = False
+        self._bad_data = bool(getattr(self, "_bad_X", False))
+        self._factored_ok = False
+        self._u_theta_ok = False
+        self._bind()
+        self.set_option(51, q)
+        self.nout = q
+
+    def _no_outputs(self, what):
+        """Raised before the call by everything that has no form under several outputs."""
+        if self.nout > 1:
+            raise ValueError(f"{what} has no form under several outputs (set_outputs with {self.nout} columns is in force): "
+                             "call set_outputs with one column first")
 
     def loo_grad(self, theta):
         """(L_LOO, dL_LOO/dtheta) at natural-scale theta, whatever objective is set (it is the same afterwards); (-inf, zeros)
@@ -280,6 +324,7 @@ class MiGP:
         carries blockIdx.z = problem.  Returns (k,) values, -inf where the covariance is not positive definite; the
         values are those lml() returns one at a time."""
         self._no_trend("lml_batch")
+        self._no_outputs("lml_batch")
         th = self._thetas(thetas)
         k = th.shape[0]
         self._ensure_batch(k, False)
@@ -298,6 +343,7 @@ class MiGP:
         """(LML (k,), dLML/dtheta (k, ntheta)) at k hyper-parameter vectors in one lockstep evaluation
         (mi_gp_lml_grad_batch); rows of non-positive-definite problems are (-inf, zeros)."""
         self._no_trend("lml_grad_batch")
+        self._no_outputs("lml_grad_batch")
         th = self._thetas(thetas)
         k = th.shape[0]
         self._ensure_batch(k, True)
@@ -319,6 +365,7 @@ class MiGP:
         Returns the (k,) info array (0, or the 1-based first bad pivot).  The factors stay in the batch buffers for
         predict_batch; the single-evaluation factor is gone, so a later predict() refactorises."""
         self._no_trend("factor_batch")
+        self._no_outputs("factor_batch")
         th = self._thetas(thetas)
         k = th.shape[0]
         self._ensure_batch(k, False)
@@ -353,6 +400,7 @@ class MiGP:
         equal-weight mixture (mix_mean[m], mix_var[m]) over the positive-definite draws: each draw-chunk's mixture
         comes from the device, chunks are combined here in chunk order (law of total variance)."""
         self._no_trend("predict_batch")
+        self._no_outputs("predict_batch")
         th = self._thetas(thetas)
         k = th.shape[0]
         Xnew = np.ascontiguousarray(Xnew, dtype=np.float64)
@@ -413,6 +461,7 @@ class MiGP:
         """(LML, dLML/dtheta, dLML/dy, dLML/dX) -- the data-side gradients drive the chain rule through
         warps (cwgp / iwgp) and free input rows (inverse_opt).  dLML/dX is None unless want_x."""
         self._no_trend("lml_grad_data")
+        self._no_outputs("lml_grad_data")
         val, grad = self.lml_grad(theta)
         if not np.isfinite(val):
             return val, grad, np.zeros(self.n), (np.zeros((self.n, self.d)) if want_x else None)
@@ -433,6 +482,8 @@ class MiGP:
         posterior evaluation while the buffers, the handle and its streams stay.  Non-finite data (an overflowing warp)
         are not uploaded: until the next finite update lml / lml_grad return -inf like a non-positive-definite covariance
         (the reference's graph would produce NaN and PyMC's checks reject the point)."""
+        if y is not None:
+            self._no_outputs("update_data(y=...)")
         self._factored_ok = False
         # Each array carries its own state: a non-finite one is not uploaded and stays "bad" until a finite replacement
         # arrives, the finite member of a pair IS uploaded (round 4 dropped it: a later update of the other array then
@@ -483,6 +534,8 @@ class MiGP:
 
     def factor(self, theta):
         """Factorise for prediction (conditional form); returns LAPACK-style info."""
+        if self.nout > 1 and self._trend != 0:
+            self._no_outputs("a trend")
         theta, tp = self._theta(theta)
         self._factored_ok = False
         self._u_theta_ok = False
@@ -504,6 +557,7 @@ class MiGP:
         these).  Returns 0, or the LAPACK-style info of a chunk whose block is not positive definite: that chunk and the
         ones after it are not appended (``self.n`` says how many points are resident), the factor stays usable."""
         self._no_trend("append")
+        self._no_outputs("append")
         Xnew = np.ascontiguousarray(np.atleast_2d(np.asarray(Xnew, dtype=np.float64)))
         ynew = np.ascontiguousarray(np.asarray(ynew, dtype=np.float64).reshape(-1))
         if Xnew.ndim != 2 or Xnew.shape[1] != self.d or Xnew.shape[0] != ynew.shape[0]:
@@ -553,6 +607,7 @@ class MiGP:
         number of trial sets.  ``diag``: the trial points' entries of the per-point diagonal, required exactly when one is
         set.  A trial block that is not positive definite gives (-inf, zeros, zeros), ``self.info`` its pivot."""
         self._no_trend("logpdf")
+        self._no_outputs("logpdf")
         Xnew = np.ascontiguousarray(np.atleast_2d(np.asarray(Xnew, dtype=np.float64)))
         ynew = np.ascontiguousarray(np.asarray(ynew, dtype=np.float64).reshape(-1))
         if Xnew.ndim != 2 or Xnew.shape[1] != self.d or Xnew.shape[0] != ynew.shape[0]:
@@ -613,6 +668,7 @@ class MiGP:
         NaN moments for that fold alone).  ``resident=True`` skips ``lml_grad(theta)``: K^-1 of the last ``lml_grad`` is used
         as it is (theta is ignored).  The hyper-parameters are the same for every fold: nothing is refitted."""
         self._no_trend("kfold")
+        self._no_outputs("kfold")
         if self.Z_t is None:
             raise RuntimeError("this MiGP was created with need_grad=False")
         if isinstance(folds, np.ndarray) and folds.ndim == 2 and folds.shape[0] > 0:
@@ -696,7 +752,8 @@ class MiGP:
         route: ``via_inverse=True`` raises ValueError."""
         if via_inverse:
             self._no_trend("predict(via_inverse=True)")
-        if self._trend != 0:
+            self._no_outputs("predict(via_inverse=True)")
+        if self._trend != 0 or self.nout > 1:
             via_inverse = False
         self._ensure_factored(theta)
         Xnew = np.ascontiguousarray(Xnew, dtype=np.float64)
@@ -711,7 +768,8 @@ class MiGP:
                                                     or self._pred_count >= 3)
         if via_inverse and self.Z_t is None:
             raise RuntimeError("this MiGP was created with need_grad=False")
-        mean = np.empty(m)
+        q = self.nout  # (q >= 2: mi_gp_predict writes q * mc means, output-major, and mc variances)
+        mean = np.empty(m) if q == 1 else np.empty((m, q))
         var = np.empty(m)
         with torch.cuda.device(self.dev):
             for s in range(0, m, chunk):
@@ -726,21 +784,22 @@ class MiGP:
                     # moments come out through PINNED host memory the kernels address directly -- no torch copies, no torch
                     # synchronisation, one stream synchronisation inside the call (110 -> ~45 us per call at N = 512).  Same
                     # kernels on the same values: same bits as the device-buffer route below.
-                    io = self._pinned_io(mc * self.d + 2 * mc)
+                    io = self._pinned_io(mc * self.d + (q + 1) * mc)
                     io_np = io.numpy()
                     io_np[: mc * self.d] = Xnew[s : s + mc].ravel()
                     base = io.data_ptr()
                     fn = self.lib.mi_gp_predict_u if via_inverse else self.lib.mi_gp_predict
                     self._check(fn(self.h, base, mc, self._work.data_ptr(), self.lda, base + 8 * mc * self.d,
-                                   base + 8 * (mc * self.d + mc), 1 if pred_noise else 0),
+                                   base + 8 * (mc * self.d + q * mc), 1 if pred_noise else 0),
                                 "mi_gp_predict_u" if via_inverse else "mi_gp_predict")
                     if via_inverse:
                         self._u_theta_ok = True
-                    mean[s : s + mc] = io_np[mc * self.d : mc * self.d + mc]
-                    var[s : s + mc] = io_np[mc * self.d + mc : mc * self.d + 2 * mc]
+                    mu = io_np[mc * self.d : mc * self.d + q * mc]
+                    mean[s : s + mc] = mu if q == 1 else mu.reshape(q, mc).T
+                    var[s : s + mc] = io_np[mc * self.d + q * mc : mc * self.d + (q + 1) * mc]
                     continue
                 xn = torch.from_numpy(Xnew[s : s + mc]).to(self.dev)
-                mu_t = torch.empty(mc, dtype=torch.float64, device=self.dev)
+                mu_t = torch.empty(q * mc, dtype=torch.float64, device=self.dev)
                 var_t = torch.empty(mc, dtype=torch.float64, device=self.dev)
                 torch.cuda.synchronize(self.dev)
                 fn = self.lib.mi_gp_predict_u if via_inverse else self.lib.mi_gp_predict
@@ -749,7 +808,7 @@ class MiGP:
                             "mi_gp_predict_u" if via_inverse else "mi_gp_predict")
                 if via_inverse:
                     self._u_theta_ok = True
-                mean[s : s + mc] = mu_t.cpu().numpy()
+                mean[s : s + mc] = mu_t.cpu().numpy() if q == 1 else mu_t.cpu().numpy().reshape(q, mc).T
                 var[s : s + mc] = var_t.cpu().numpy()
         return mean, var
 
@@ -758,6 +817,7 @@ class MiGP:
         (mean[m], var[m], dmean[m,d], dvar[m,d]).  ``refactor=False`` reuses the resident factorisation
         (same theta as the previous predict / predict_grad call)."""
         self._no_trend("predict_grad")
+        self._no_outputs("predict_grad")
         if self.Z_t is None:
             raise RuntimeError("this MiGP was created with need_grad=False")
         if refactor:
@@ -841,6 +901,7 @@ class MiGP:
         (mu [M], cov [M, M]), cov symmetric (mirrored from the lower triangle the device computes); mu is predict()'s mean
         through the blocked solve, bit for bit."""
         self._no_trend("predict_cov")
+        self._no_outputs("predict_cov")
         self._ensure_factored(theta)
         mu_t, cov_t = self._joint_device(Xnew, pred_noise)
         m = mu_t.shape[0]
@@ -859,6 +920,7 @@ class MiGP:
         1e-4 kd (kd the composite prior variance), then FloatingPointError.  ``self.sample_info`` records the seed, offset and
         extra jitter used."""
         self._no_trend("sample_posterior")
+        self._no_outputs("sample_posterior")
         nsamples = int(nsamples)
         if nsamples < 1:
             raise ValueError("nsamples must be >= 1")
@@ -939,7 +1001,7 @@ class MiGP:
             self.h = None
         # the device buffers the handle borrowed (a batch holds K-fold copies of K, U, K^-1)
         for name in ("_bK", "_bZ", "_bW", "_bwork", "K_t", "Z_t", "W_t", "_work", "_work2", "_gx_t", "_pin_io", "_awork", "_lwork", "_X_store",
-                     "_y_store", "_diag_store"):
+                     "_y_store", "_diag_store", "_Y_store"):
             if hasattr(self, name):
                 setattr(self, name, None)
         self._batch_k = 0

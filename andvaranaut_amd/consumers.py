@@ -248,6 +248,8 @@ class ConsumersMixin:
         opt_method="predict", and ``refine`` does not apply."""
         if getattr(self, "trend", None) is not None:
             raise ValueError(f"BO has no form under trend={self.trend!r}: fit without a trend to use it")
+        if getattr(self, "outputs", "first") == "all":
+            raise ValueError("BO has no form under outputs='all': fit with outputs='first' to use it")
         if method == "TS" and opt_method != "predict":
             raise ValueError("method='TS' (Thompson sampling) takes one joint posterior draw over the predict_samps candidates: "
                              f"it needs opt_method='predict', not {opt_method!r}")
@@ -398,6 +400,8 @@ class ConsumersMixin:
         potential to rounding."""
         if getattr(self, "trend", None) is not None:
             raise ValueError(f"inverse_opt has no form under trend={self.trend!r}: fit without a trend to use it")
+        if getattr(self, "outputs", "first") == "all":
+            raise ValueError("inverse_opt has no form under outputs='all': fit with outputs='first' to use it")
         if self.m is None:
             raise Exception("Model must be fitted before running Bayesian optimisation")
         if self.verbose:

@@ -65,7 +65,7 @@ static void release_handle(mi_gp_handle* h) {
   free_scratch(h->one);
   free_scratch(h->batch);
   (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
-  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk}) (void)hipFree(b->p);
+  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk, &h->multi_blk}) (void)hipFree(b->p);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -151,6 +151,7 @@ static void special_defaults(mi_gp_handle* h) {
   h->use_smo = 2;  // (0 where the driver lacks stream memory operations: mi_gp_create)
   h->spin_us = 2000;
   h->cv_block = 1;
+  h->nout = 1;
 }
 
 // The options with behaviour beyond a clamp; `set` (or nullptr) is the new value, `get` (or nullptr) receives the current one.
@@ -244,6 +245,25 @@ static int special_option(mi_gp_handle* h, int what, const int* set, int* get) {
         }
       } else {
         *get = h->trend;
+      }
+      return 1;
+    case 51:  // the number of OUTPUTS (a change ends the resident state as mi_gp_set_data does)
+      if (set) {
+        if (*set < 1 || *set > 128) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 51 is a number of outputs of 1 (the single y) to 128, got %d", *set);
+          return -1;
+        }
+        if (*set != 1 && !(multi_objective && multi_factor && multi_predict_reduce)) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: several outputs (option 51 = %d) are not part of this build", *set);
+          return -1;
+        }
+        if (*set != h->nout) {
+          h->nout = *set;
+          h->factored = h->have_kinv = h->have_u = false;
+          h->b_cond_k = 0;
+        }
+      } else {
+        *get = h->nout;
       }
       return 1;
   }
@@ -472,6 +492,7 @@ static int factor_internal(mi_gp_handle* h, const double* theta, int what) {
 extern "C" int mi_gp_lml(mi_gp_handle* h, const double* theta, double* lml_out) {
   if (!h || !theta || !lml_out) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_lml");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_lml");
   const int r = factor_internal(h, theta, 0);
   if (r < 0) return r;
   if (r > 0) { *lml_out = -INFINITY; return r; }
@@ -505,6 +526,11 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
     snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad needs Z_dev and W_dev in mi_gp_set_data");
     return -1;
   }
+  if (h->nout > 1 && (h->objective == 1 || h->trend != 0)) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad: several outputs (option 51 = %d) have no form under %s", h->nout,
+             h->objective == 1 ? "a cross-validation objective (option 48 = 1)" : "a trend (option 50)");
+    return -1;
+  }
   if (h->trend != 0 && (h->objective == 1 || h->n <= trend_columns(h))) {
     if (h->objective == 1)
       snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad: no cross-validation objective (option 48 = 1) under a trend (option 50 = %d)", h->trend);
@@ -524,6 +550,11 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
     h->have_kinv = false;
     return trend_objective(h, lml_out, grad_out);
   }
+  // option 51 >= 2: the same evaluation, then the outputs' tail on the resident K^-1 (api_multi.hip); W_dev then holds q K^-1 - V V^T
+  if (h->nout > 1) {
+    h->have_kinv = false;
+    return multi_objective(h, lml_out, grad_out);
+  }
   // option 48 = 1: the same evaluation, then the leave-one-out tail on the resident K^-1 and alpha (api_loo.hip)
   if (h->objective == 1) return loo_objective(h, lml_out, grad_out);
   return 0;
@@ -536,6 +567,7 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
 extern "C" int mi_gp_alpha(mi_gp_handle* h, double* alpha_host) {
   if (!h || !alpha_host) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_alpha");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_alpha");
   if (!h->have_kinv) { snprintf(h->err, sizeof(h->err), "mi_gp_alpha: call mi_gp_lml_grad first"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
   HCK(hipMemcpyAsync(alpha_host, h->one.alpha_dev, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream), "alpha download");
@@ -546,6 +578,7 @@ extern "C" int mi_gp_alpha(mi_gp_handle* h, double* alpha_host) {
 extern "C" int mi_gp_grad_x(mi_gp_handle* h, double* gx_dev) {
   if (!h || !gx_dev) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_grad_x");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_grad_x");
   if (!h->have_kinv) { snprintf(h->err, sizeof(h->err), "mi_gp_grad_x: call mi_gp_lml_grad first"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
   const int nsplit = grad_x_splits(h->n, h->cfg.d);
@@ -642,12 +675,14 @@ static int batch_internal(mi_gp_handle* h, int k, const double* thetas, int what
 extern "C" int mi_gp_lml_batch(mi_gp_handle* h, int k, const double* thetas, double* lml_out, int* info_out) {
   if (!h || !thetas || !lml_out) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_lml_batch");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_lml_batch");
   return batch_internal(h, k, thetas, 0, lml_out, nullptr, info_out);
 }
 
 extern "C" int mi_gp_lml_grad_batch(mi_gp_handle* h, int k, const double* thetas, double* lml_out, double* grad_out, int* info_out) {
   if (!h || !thetas || !lml_out || !grad_out) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_lml_grad_batch");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_lml_grad_batch");
   if (h->objective == 1) {
     snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad_batch: the leave-one-out objective (option 48 = 1) has no batched form");
     return -1;
@@ -658,6 +693,10 @@ extern "C" int mi_gp_lml_grad_batch(mi_gp_handle* h, int k, const double* thetas
 // ---------------------------------------------------------------- conditional (K8)
 extern "C" int mi_gp_factor(mi_gp_handle* h, const double* theta) {
   if (!h || !theta) return -1;
+  if (h->nout > 1 && h->trend != 0) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_factor: several outputs (option 51 = %d) have no form under a trend (option 50)", h->nout);
+    return -1;
+  }
   if (h->trend != 0 && h->n <= trend_columns(h)) {
     snprintf(h->err, sizeof(h->err), "mi_gp_factor: the trend (option 50 = %d) has %d coefficients, n = %d must exceed that", h->trend,
              trend_columns(h), h->n);
@@ -665,6 +704,11 @@ extern "C" int mi_gp_factor(mi_gp_handle* h, const double* theta) {
   }
   const int r = factor_internal(h, theta, 1);
   h->factored = (r == 0);
+  if (r == 0 && h->nout > 1) {  // B^T = Y^T L^-T (api_multi.hip)
+    const int rm = multi_factor(h);
+    h->factored = (rm == 0);
+    return rm;
+  }
   if (r == 0 && h->trend != 0) {  // G = L^-1 H, chol(G^T G), beta^ and b~ (api_trend.hip)
     const int rt = trend_factor(h);
     h->factored = (rt == 0);
@@ -713,7 +757,8 @@ extern "C" int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, dou
   HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, mp, h->np, 0, 0, h->stream),
       "assemble cross");
   HCK(trsm_rec(h, one_eval(h), work_dev, ldw, mp, 0, h->ntc), "trsm");
-  if (h->trend != 0) HCK(trend_predict_reduce(h, Xnew_dev, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "trend predict_reduce");
+  if (h->nout > 1) HCK(multi_predict_reduce(h, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "outputs predict_reduce");
+  else if (h->trend != 0) HCK(trend_predict_reduce(h, Xnew_dev, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "trend predict_reduce");
   else HCK(predict_reduce(h, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "predict_reduce");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
   return 0;
@@ -732,6 +777,7 @@ extern "C" int mi_gp_predict_cov(mi_gp_handle* h, const double* Xnew_dev, int m,
                   : (ldc < mp || (ldc & 1)) ? "ldc must be even and >= ceil(m/128)*128"
                   : !h ? "null handle"
                   : h->trend != 0 ? "no form under a trend (option 50): set option 50 to 0 first"
+                  : h->nout > 1 ? "no form under several outputs (option 51): set option 51 to 1 first"
                   : !h->factored ? "call mi_gp_factor first"
                   : (ldw < h->np || (ldw & 1)) ? "ldw must be even and >= padded n" : nullptr;
   if (why) {
@@ -831,6 +877,7 @@ extern "C" int mi_gp_sample_cov(mi_gp_handle* h, double* cov_dev, long ldc, int 
 extern "C" int mi_gp_factor_batch(mi_gp_handle* h, int k, const double* thetas, int* info_out) {
   if (!h) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_factor_batch");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_factor_batch");
   if (k < 1 || !thetas) { snprintf(h->err, sizeof(h->err), "mi_gp_factor_batch: k >= 1 and thetas are required"); return -1; }
   return batch_internal(h, k, thetas, 1, nullptr, nullptr, info_out);
 }
@@ -840,6 +887,7 @@ extern "C" int mi_gp_predict_batch(mi_gp_handle* h, int k, const double* Xnew_de
                                    double* mix_var_dev) {
   if (!h) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_batch");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_predict_batch");
   if (k < 1 || !Xnew_dev || !work_dev || !mean_dev || !var_dev || m <= 0) {
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_batch: k >= 1, m >= 1 and the point / work / output buffers are required");
     return -1;
@@ -916,6 +964,7 @@ extern "C" int mi_gp_predict_u(mi_gp_handle* h, const double* Xnew_dev, int m, d
                                double* mean_dev, double* var_dev, int pred_noise) {
   if (!h || !Xnew_dev || !work_dev || !mean_dev || !var_dev || m <= 0) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_u");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_predict_u");
   if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_predict_u: call mi_gp_factor first"); return -1; }
   if (!h->buf.Z_dev || !h->buf.W_dev) {
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_u needs Z_dev and W_dev in mi_gp_set_data");
@@ -938,6 +987,7 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
                                   double* dvar_dev) {
   if (!h || !dmean_dev || !dvar_dev) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_grad");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_predict_grad");
   if (!h->buf.Z_dev || !h->buf.W_dev) {
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_grad needs Z_dev and W_dev in mi_gp_set_data");
     return -1;
@@ -1001,6 +1051,7 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   // trend's keeps the conditional's G^T, beta^ and b~
   for (CapBlock* b : {&h->loo, &h->cv}) (void)resize_block(*b, 0, 0);
   if (h->trend_blk.p && trend_reserve) HCK(trend_reserve(h, capacity), "mi_gp_reserve");
+  if (h->multi_blk.p && multi_reserve) HCK(multi_reserve(h, capacity), "mi_gp_reserve");  // (keeps the conditional's B^T)
   return 0;
 }
 
@@ -1065,6 +1116,7 @@ extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const doubl
                             double* work_dev, long ldw) {
   if (!h) { set_global_error("mi_gp_append: null handle"); return -1; }
   if (h->trend != 0) return refuse_trend(h, "mi_gp_append");
+  if (h->nout > 1) return refuse_multi(h, "mi_gp_append");
   if (!Xnew_dev || !ynew_dev || !work_dev) { snprintf(h->err, sizeof(h->err), "mi_gp_append: null point, value or work buffer"); return -1; }
   if (k < 1 || k > 128) { snprintf(h->err, sizeof(h->err), "mi_gp_append: 1 <= k <= 128 (got %d)", k); return -1; }
   if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_append: call mi_gp_factor first"); return -1; }

@@ -134,6 +134,9 @@ struct mi_gp_handle {
   int trend;               // option 50: the TREND whose coefficients are integrated out -- 0 none, 1 constant h = [1], 2 linear
                            // h = [1, x_1 .. x_d] (mi_gp_lml_grad, mi_gp_factor and mi_gp_predict; api_trend.hip)
   CapBlock trend_blk;      // its scratch (TrendScratch, api_trend.hip; allocated by the first use)
+  int nout;                // option 51: the number of OUTPUTS q under one shared kernel -- 1 (default) the single y, 2..128 the vectors
+                           // y_dev[o * lda ..) (mi_gp_lml_grad, mi_gp_factor and mi_gp_predict; api_multi.hip)
+  CapBlock multi_blk;      // its scratch (MultiScratch, api_multi.hip; allocated by the first use)
   char err[256];
 };
 
@@ -297,6 +300,24 @@ inline size_t trend_scratch_len(int cap) {
 // the -1 of an entry point that has no form under a trend
 inline int refuse_trend(mi_gp_handle* h, const char* entry) {
   snprintf(h->err, sizeof(h->err), "%s has no form under a trend (option 50 = %d): set option 50 to 0 first", entry, h->trend);
+  return -1;
+}
+
+// api_multi.hip: several outputs under one shared kernel (option 51; include/mi_gp.h has the algebra).  Weak like loo_objective:
+// without the file option 51 >= 2 is refused.
+// the tail of mi_gp_lml_grad behind a successful ordinary evaluation (K^-1 in W_dev; out_host[1] the factorisation's logdet):
+// *value = L_MO and grad[ntheta] its gradient, W_dev's lower triangle then holds q K^-1 - V V^T; 0 or a C-ABI error code
+int multi_objective(mi_gp_handle* h, double* value, double* grad) __attribute__((weak));
+// behind a successful mi_gp_factor: B^T = Y^T L^-T (128 rows, rows from q on zero) in the handle's scratch; 0 or a C-ABI error code
+int multi_factor(mi_gp_handle* h) __attribute__((weak));
+// mi_gp_predict's reduction under q outputs (the rows L^-1 k(X, x*) are in work_dev): mean[o * m + i], var[i]
+hipError_t multi_predict_reduce(mi_gp_handle* h, const double* work_dev, long ldw, int m, double* mean_dev, double* var_dev,
+                                int pred_noise) __attribute__((weak));
+// mi_gp_reserve's part: the scratch re-sized for `capacity` points, the conditional's B^T kept
+hipError_t multi_reserve(mi_gp_handle* h, int capacity) __attribute__((weak));
+// the -1 of an entry point that has no form under several outputs
+inline int refuse_multi(mi_gp_handle* h, const char* entry) {
+  snprintf(h->err, sizeof(h->err), "%s has no form under several outputs (option 51 = %d): set option 51 to 1 first", entry, h->nout);
   return -1;
 }
 

@@ -381,6 +381,16 @@ hipError_t launch_trend_predict_reduce(const double* A, long lda, const double* 
                                        const double* bt, const double* beta, const double* Cinv, int n, int m, double kdiag,
                                        double noise, double* mean, double* var, hipStream_t stream);
 
+// ---------------------------------------------------------------- multi_f64.hip (option 51: several outputs, api_multi.hip)
+// Y^T in launch_trend_basis's layout: YT[o * ldg + i] = y[o * ldy + i] for o < q, i < n, zeros up to row 127 and column np - 1
+hipError_t launch_multi_stage(const double* y, long ldy, int q, int n, int np, double* YT, long ldg, hipStream_t stream);
+// quad[o] = sum_{i < n} YT[o * ldg + i] V[i * 128 + o] for o < q, zeros up to 127; every sum in a fixed order
+hipError_t launch_multi_quad(const double* YT, long ldg, const double* V, int q, int n, double* quad, hipStream_t stream);
+// mi_gp_predict's reduction under q outputs, ONE pass over the m rows a* of A (lda apart; BT = (L^-1 Y)^T, 128 rows ldg apart):
+// mean[o * m + i] = a*_i . b_o for o < q, var[i] = kdiag - |a*_i|^2 + noise; each output is written once
+hipError_t launch_multi_predict(const double* A, long lda, const double* BT, long ldg, int q, int n, int m, double kdiag, double noise,
+                                double* mean, double* var, hipStream_t stream);
+
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)
 void set_global_error(const char* text);

@@ -247,6 +247,7 @@ class GPMCMC(ConsumersMixin):
         """The numeric half of ``test_plots`` (gpmcmc.py:933-976; the plots are out of scope): condition the model on the
         training split (``train_test``; refitted there with ``method``, 'none' = the stored hypers), predict the held-out
         points and return RMSE, mean absolute / percentage error and R^2 with the arrays ``returndat`` hands back."""
+        self._no_all_outputs("test_stats")
         trend = getattr(self, "trend", None)  # (an object fitted with a trend is tested with it)
         if trend is not None and (method not in ("none", "map") or iwgp or cwgp):
             raise ValueError(f"test_stats under trend={trend!r} needs method='none' or 'map' and neither iwgp nor cwgp")
@@ -300,6 +301,7 @@ class GPMCMC(ConsumersMixin):
         ``log_predictive``), ``lpd_folds`` (per fold, its Jacobian included), ``folds`` and ``info`` (0 per fold, or the
         pivot at which the fold's block of K^-1 was not positive definite)."""
         self._no_trend("cv_stats")
+        self._no_all_outputs("cv_stats")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before cross-validating")
         n = len(self.x)
@@ -397,6 +399,7 @@ class GPMCMC(ConsumersMixin):
         self.m = None
         self.hypers = None
         self.trend = None
+        self.outputs = "first"
 
     def __release(self):
         gp = getattr(self, "gp", None)
@@ -418,6 +421,8 @@ class GPMCMC(ConsumersMixin):
             self.gp = MiGP(xin, yin, self.kernel, device=self.device)
             if getattr(self, "trend", None) is not None:
                 self.gp.set_trend(self.trend)
+            if getattr(self, "outputs", "first") == "all":
+                self.gp.set_outputs(self._converted_outputs(self.y - self.ym))
         return self.gp
 
     def _no_trend(self, what):
@@ -425,9 +430,18 @@ class GPMCMC(ConsumersMixin):
         if getattr(self, "trend", None) is not None:
             raise ValueError(f"{what} has no form under trend={self.trend!r}: fit without a trend to use it")
 
+    def _no_all_outputs(self, what):
+        """Raised, before any device call, by what has no form once every output is modelled (fit(outputs="all"))."""
+        if getattr(self, "outputs", "first") == "all":
+            raise ValueError(f"{what} has no form under outputs='all': fit with outputs='first' to use it")
+
+    def _converted_outputs(self, y):
+        """Every column of y through its own yconrevs[i]: the (n, ny) outputs of a fit with outputs="all"."""
+        return np.ascontiguousarray(np.column_stack([self.yconrevs[i].con(y[:, i]) for i in range(self.ny)]))
+
     # ------------------------------------------------------------------ fit
     def fit(self, method="map", return_data=False, iwgp=False, cwgp=False, jitter=1e-6, truncate=False,
-            restarts=1, objective="lml", nfolds=10, fold_seed=None, trend=None, **kwargs):
+            restarts=1, objective="lml", nfolds=10, fold_seed=None, trend=None, outputs="first", **kwargs):
         """gpmcmc.py:175-182.  ``objective="loo"`` (with ``method="map"``) maximises the leave-one-out log predictive density
         sum_i log p(y_i | y_-i) plus the priors instead of the log marginal likelihood (Rasmussen & Williams section 5.4.2: the
         criterion for a misspecified kernel family); the hyper-parameters are stored as a MAP fit stores them.  It has no
@@ -441,7 +455,19 @@ class GPMCMC(ConsumersMixin):
         h(x)^T beta with h = [1] or [1, x_1 .. x_nx] in the converted inputs, whose coefficients carry a vague prior and are
         integrated out (Rasmussen & Williams section 2.7): the hyper-parameters are those of a zero-mean fit, the fit maximises
         the trend's marginal likelihood, and ``predict`` returns the trend's conditional.  The choice is part of the object's
-        state (``self.trend``).  Restarts run one after the other."""
+        state (``self.trend``).  Restarts run one after the other.
+        ``outputs="first"`` (default) models y[:, 0] alone, whatever ``ny`` is.  ``outputs="all"`` (``ny >= 2``, with
+        ``method="map"``, ``objective="lml"``, no trend, no warps) models every column under ONE shared kernel and one noise,
+        column i converted by ``yconrevs[i]``, the outputs independent given the hyper-parameters: the fit maximises the sum of
+        the columns' log marginal likelihoods plus the priors on one factorisation per evaluation, and ``predict`` returns
+        (M, ny) arrays.  The choice is part of the object's state (``self.outputs``)."""
+        if outputs not in ("first", "all"):
+            raise ValueError(f"outputs must be 'first' or 'all' (got {outputs!r})")
+        if outputs == "all":
+            if self.ny < 2:
+                raise ValueError("outputs='all' needs ny >= 2")
+            if method != "map" or objective != "lml" or trend is not None or iwgp or cwgp:
+                raise ValueError("outputs='all' needs method='map', objective='lml', trend=None and neither iwgp nor cwgp")
         if trend is not None:
             if trend not in ("constant", "linear"):
                 raise ValueError(f"trend must be None, 'constant' or 'linear' (got {trend!r})")
@@ -455,8 +481,10 @@ class GPMCMC(ConsumersMixin):
         if objective == "loo" and (method != "map" or iwgp or cwgp):
             raise ValueError("objective='loo' needs method='map' and neither iwgp nor cwgp")
         self.m, self.gp, self.hypers, data = self.__fit(self.x, self.y - self.ym, method, iwgp, cwgp, jitter,
-                                                        truncate, restarts, objective=objective, cv=cv, trend=trend, **kwargs)
+                                                        truncate, restarts, objective=objective, cv=cv, trend=trend, outputs=outputs,
+                                                        **kwargs)
         self.trend = trend
+        self.outputs = outputs
         if return_data:
             return data
 
@@ -584,7 +612,7 @@ class GPMCMC(ConsumersMixin):
         return likelihood
 
     def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", cv=None, trend=None,
-              **kwargs):
+              outputs="first", **kwargs):
         n_i, n_pos, n_free = self._warp_sizes(iwgp, cwgp)
         model = HyperModel(self.nx, self.kerns, noise=self.noise, truncate=truncate, jitter=jitter, n_iwgp=n_i,
                            n_cwgp_pos=n_pos, n_cwgp=n_free)
@@ -593,6 +621,8 @@ class GPMCMC(ConsumersMixin):
         gp = MiGP(xin, yin, self.kernel, device=self.device)
         if trend is not None:
             gp.set_trend(trend)  # (gp.lml_grad then returns the trend's marginal likelihood; the stored handle keeps the trend)
+        if outputs == "all":
+            gp.set_outputs(self._converted_outputs(y))  # (gp.lml_grad then returns the sum of the columns' marginal likelihoods)
         lik = self._warp_likelihood(gp, x, y, xin, iwgp, cwgp) if (iwgp or cwgp) else None
         # pm.find_MAP maximises without the transform Jacobian, pm.sample with it (priors.py header)
         fun_map = lambda q: model.logp_dlogp(q, gp.lml_grad, jacobian=False, likelihood=lik)  # noqa: E731
@@ -850,7 +880,10 @@ class GPMCMC(ConsumersMixin):
 
     def predict(self, x, return_var=False, convert=True, revert=True, normvar=False, jitter=1e-6, EI=False,
                 EIopt=None, deg=8):
-        """gpmcmc.py:522-542."""
+        """gpmcmc.py:522-542.  Under ``outputs="all"`` the mean and the variance are (M, ny): column i is reverted through its
+        own ``yconrevs[i]`` by the same Gauss-Hermite reversion and the mean function's column i is added to it."""
+        if EI:
+            self._no_all_outputs("predict(EI=True)")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
         if convert:
@@ -868,6 +901,12 @@ class GPMCMC(ConsumersMixin):
         mu, var = self.gp.predict(self._theta_from_hypers(self.hypers, jitter), xarg, pred_noise=True)
         if self.verbose:
             print(f"Time taken: {stopwatch() - t0:0.2f} s")
+        if getattr(self, "outputs", "first") == "all":
+            cols = [(mu[:, i : i + 1], var.reshape((-1, 1))) for i in range(self.ny)]
+            if revert:
+                cols = [self.__gh_stats(x, yi, yvi, normvar, deg, col=i) for i, (yi, yvi) in enumerate(cols)]
+            y, yv = np.hstack([c[0] for c in cols]), np.hstack([c[1] for c in cols])
+            return (y, yv) if return_var else y
         y, yv = mu.reshape((-1, 1)), var.reshape((-1, 1))
         if revert:
             y, yv = self.__gh_stats(x, y, yv, normvar, deg, EI=EI, EIopt=EIopt)
@@ -892,6 +931,7 @@ class GPMCMC(ConsumersMixin):
         A covariance has no image under a nonlinear output reversion, so there is no ``revert`` here (sample_posterior
         reverts draws instead)."""
         self._no_trend("predict_joint")
+        self._no_all_outputs("predict_joint")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
         xarg, _ = self._converted_x(np.asarray(x, dtype=np.float64), convert)
@@ -903,6 +943,7 @@ class GPMCMC(ConsumersMixin):
         units, at ``self.hypers``: log N(y_con | conditional of the fitted GP at x_con, with observation noise) plus the
         Jacobian sum log|d y_con / d y| when the output conversion has ``der`` (MiGP.logpdf; nothing is appended)."""
         self._no_trend("log_predictive")
+        self._no_all_outputs("log_predictive")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
         x = np.asarray(x, dtype=np.float64)
@@ -924,6 +965,7 @@ class GPMCMC(ConsumersMixin):
         output reversion point by point and adds the mean function -- exact for sample paths, no quadrature.  ``seed``: see
         MiGP.sample_posterior (None: fresh draws on every call)."""
         self._no_trend("sample_posterior")
+        self._no_all_outputs("sample_posterior")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
         xarg, xorig = self._converted_x(np.asarray(x, dtype=np.float64), convert)
@@ -972,6 +1014,7 @@ class GPMCMC(ConsumersMixin):
         unreverted moments bit for bit where predict() takes the triangular solve (not U = L^-T, MiGP.predict), the reverted
         ones to rounding."""
         self._no_trend("predict_posterior")
+        self._no_all_outputs("predict_posterior")
         if self._ensure_gp() is None or self.m is None:
             raise Exception("Error: fit the GP before predicting")
         thetas, idx = self._posterior_thetas(data, ndraws, jitter)
@@ -1015,26 +1058,26 @@ class GPMCMC(ConsumersMixin):
             yvout = yvout / np.power(yout, 2)
         return (yout, yvout) if return_var else yout
 
-    def __gh_stats(self, x, y, yv, normvar=True, deg=8, EI=False, EIopt=None):
+    def __gh_stats(self, x, y, yv, normvar=True, deg=8, EI=False, EIopt=None, col=0):
         """Gauss-Hermite mean / variance (or EI) of the reverted variable (gpmcmc.py:545-569),
         vectorised over the prediction points instead of the reference's per-point Python loop."""
-        ymean, ym2 = self._gh_moments(self._mean_at(x), y, yv, deg, EI, EIopt)
+        ymean, ym2 = self._gh_moments(self._mean_at(x, col), y, yv, deg, EI, EIopt, col=col)
         yout = ymean.reshape((-1, 1))
         yvout = (ym2 - ymean ** 2).reshape((-1, 1))
         if normvar:
             yvout = yvout / np.power(yout, 2)
         return yout, yvout
 
-    def _mean_at(self, x):
-        """The mean function at every row of x (0.0 for the zero mean)."""
-        return np.array([self.mean(x[i, :])[0] for i in range(len(x))]) if self.mean != self.zero_mean else 0.0
+    def _mean_at(self, x, col=0):
+        """Output ``col`` of the mean function at every row of x (0.0 for the zero mean)."""
+        return np.array([self.mean(x[i, :])[col] for i in range(len(x))]) if self.mean != self.zero_mean else 0.0
 
-    def _gh_moments(self, means, y, yv, deg=8, EI=False, EIopt=None):
+    def _gh_moments(self, means, y, yv, deg=8, EI=False, EIopt=None, col=0):
         """First moment (or EI) and second moment of the reverted variable per row, by Gauss-Hermite quadrature of the
         converted-space normal N(y, yv); ``means``: the mean function per row (or 0.0)."""
         xi, wi = np.polynomial.hermite.hermgauss(deg)
         yi = np.sqrt(2.0 * yv) * xi[None, :] + y  # [M, deg]
-        yir = self.yconrevs[0].rev(yi) + np.reshape(means, (-1, 1) if np.ndim(means) else ())
+        yir = self.yconrevs[col].rev(yi) + np.reshape(means, (-1, 1) if np.ndim(means) else ())
         if EI:
             ydiff = (yir - self.yopt) if EIopt == "max" else (self.yopt - yir)
             first = np.where(ydiff > 0.0, ydiff, 0.0)

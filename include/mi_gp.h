@@ -479,6 +479,47 @@ MI_GP_API int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host,
  *      the batched and sharded forms; cross-validation objectives, mi_gp_kfold, mi_gp_append and mi_gp_logpdf under a trend;
  *      data-side gradients (and with them warped fits under a trend); reading beta^ out; quadratic or user-supplied bases; a
  *      rank-deficiency test beyond n <= p.
+ *   51 (not a tuning knob) the OUTPUTS: the number q of outputs modelled under ONE shared kernel and one noise, independent
+ *      given theta, their log marginal likelihoods summed (the form scikit-learn's GaussianProcessRegressor gives a 2-D y);
+ *      theta and mi_gp_num_theta() stay as they are.  1 (default) the single y, today's behaviour bit for bit; 2..128 q outputs.
+ *      Y is n x q with columns y_o.  Under q >= 2 y_dev of mi_gp_buffers holds q vectors: output o occupies
+ *      y_dev[o * lda .. o * lda + n), lda the leading dimension bound by mi_gp_set_data (known when data are bound, >= the padded
+ *      capacity, so the layout survives mi_gp_reserve).  Output 0 is the y the factorisation reads as always.  The pointer is
+ *      borrowed and read at evaluation time.  K_y is the noisy covariance of the entry point's own form (marginal in
+ *      mi_gp_lml_grad, conditional in mi_gp_factor; the diagonal of mi_gp_set_diag included).
+ *      mi_gp_lml_grad (option 48 = 0, option 50 = 0) runs the ordinary evaluation first (same launches, same schedule), then a
+ *      tail on the handle's stream:
+ *          V = K_y^-1 Y,   quad_o = y_o . V[:, o]
+ *          L_MO = sum_o LML(y_o) = -q sum_i log L_ii - q n/2 log 2 pi - 1/2 sum_o quad_o
+ *          dL_MO/dtheta_k = 1/2 sum_ij (V V^T - q K_y^-1)_ij dK_ij/dtheta_k                      (d/d jitter = d/d gv)
+ *      -- Y^T staged as 128 rows (rows >= q and columns >= n zero), V by option 50's symmetric thin multiply on the fp64 matrix
+ *      cores (the lower triangle of W_dev alone), the q quads in one kernel, the update W <- q W - V V^T over the lower trapezoid
+ *      on the GEMM (alpha = -1, beta = q, k = 128), and the LML gradient's contraction kernel with that W and a zero vector in the
+ *      place of alpha.  *lml_out = L_MO, grad_out its gradient in theta order; the call returns with the stream synchronised.
+ *      Afterwards the lower triangle of W_dev holds q K^-1 - V V^T, not K^-1: the handle marks K^-1 not resident, as under a
+ *      trend; mi_gp_lml_parts keeps the factorisation's logdet and output 0's quad.  A bad pivot is reported as under q = 1:
+ *      info > 0, -inf, a zero gradient, no tail.
+ *      mi_gp_factor additionally forms B^T = Y^T L^-T (the blocked solve of mi_gp_predict on 128 rows; b_o = L^-1 y_o) in scratch
+ *      the handle owns, and mi_gp_predict returns, per point, with a* = L^-1 k(X, x*) (the row the call forms in work_dev)
+ *          mean_dev[o * m + i] = a*_i . b_o   (q * m doubles, output-major),   var_dev[i] = kdiag - |a*_i|^2 (+ gv if pred_noise)
+ *      (m doubles: the variance does not depend on y and is that of one output) from ONE pass over the rows of work_dev, whose
+ *      contract (size, layout) does not change: a workgroup reads the rows of 16 points once, chunk by chunk, and forms their
+ *      16 x q products with the rows of B^T on the fp64 matrix cores and |a*|^2 beside them.  mean_dev / var_dev are written once
+ *      and may be pinned host addresses.
+ *      Refused (-1, before any device call, with a text that names option 51) while q >= 2: mi_gp_lml, mi_gp_lml_batch,
+ *      mi_gp_lml_grad_batch, mi_gp_factor_batch, mi_gp_predict_batch, mi_gp_predict_u, mi_gp_predict_grad, mi_gp_predict_cov,
+ *      mi_gp_append, mi_gp_logpdf, mi_gp_kfold, mi_gp_alpha and mi_gp_grad_x; mi_gp_lml_grad under option 48 = 1 or option
+ *      50 != 0; mi_gp_factor under option 50 != 0.  No refusal changes the handle's state.  The handle owns the scratch (Y^T / B^T
+ *      as 128 rows, V and the multiply's partial products as padded capacity x 128, a zero vector, the q quads): allocated by the
+ *      first use, freed by mi_gp_destroy; mi_gp_reserve re-sizes it and moves B^T, so the handle stays factored.  The same call in
+ *      the same state returns the same bits; every element a launch reads is written earlier in the same call (NaN in the strict
+ *      upper triangle of W_dev, in work_dev or in the scratch changes nothing); the scheduling options change no bit; no sum uses
+ *      atomics, every one runs in a fixed order.  Values outside 1..128 return -1, and so does a value other than 1 in a build
+ *      without the tail (the host-only schedule-trace program).  Setting a value other than the current one ends the resident
+ *      state exactly as mi_gp_set_data does; setting the current value changes nothing; with 1 the library enqueues exactly what
+ *      it enqueues without the option.  Out of scope: a kernel variance or a noise per output; correlated outputs
+ *      (coregionalisation); the batched and sharded forms; data-side gradients and warps; cross-validation objectives and the
+ *      trend under several outputs; mi_gp_append, mi_gp_logpdf and the joint covariance under several outputs; q > 128.
  * 8, 14, 16, 18, 19, 21, 26, 27, 30, 31, 38, 45 and 47 only change scheduling (bit-identical results); 20 moves tiles between the
  * two GEMM kernels (same k order); 2, 4-7, 9, 32, 35, 37 and 46 regroup sums (agreement to rounding), and so does 0 where it changes
  * the super-panel width (20 to 60 tile columns).
