@@ -171,6 +171,7 @@ class MiGP:
             raise RuntimeError("this MiGP was created with need_grad=False")
         if self.nout > 1 and self._trend != 0:
             self._no_outputs("a trend")
+        self._outcov_needs_points()
         if self._trend != 0 and self.get_option(48) == 1:
             self._no_trend("a cross-validation objective")
         if self.nout > 1 and self.get_option(48) == 1:
@@ -252,6 +253,28 @@ class MiGP:
         self._bind()
         self.set_option(51, q)
         self.nout = q
+
+    OUTPUT_COVS = {"shared": 0, "integrated": 1}
+    _outcov = 0
+
+    def set_output_cov(self, name):
+        """The covariance between the outputs of set_outputs (option 52 of mi_gp_set_option): "shared" (default), the outputs
+        independent under one kernel variance; "integrated", vec(Y) ~ N(0, Sigma (x) K_y) with a q x q covariance Sigma between the
+        outputs under the Jeffreys prior |Sigma|^-(q+1)/2, integrated out in closed form (the separable emulator of Conti &
+        O'Hagan 2010).  Under "integrated" and q >= 2 outputs (n >= q + 2) lml_grad returns that marginal likelihood L_S and its
+        exact theta gradient, and predict the same means with a variance of shape (m, q): column o is the shared variance times
+        s_o = |L^-1 y_o|^2 / (n - q - 1).  L_S does not change under K_y -> c K_y: only their priors identify the overall scale
+        of kv, gv and the jitter.  With one output the choice is inert.  A change ends the resident factorisation."""
+        if name not in self.OUTPUT_COVS:
+            raise ValueError(f"the output covariance must be one of {list(self.OUTPUT_COVS)}")
+        if self.OUTPUT_COVS[name] != self._outcov:
+            self.set_option(52, self.OUTPUT_COVS[name])  # (set_option keeps _outcov, the mirror predict reads, in step)
+
+    def _outcov_needs_points(self):
+        """Raised before the call: the integrated covariance of q outputs needs n >= q + 2."""
+        if self._outcov and self.nout > 1 and self.n < self.nout + 2:
+            raise ValueError(f"the integrated covariance of {self.nout} outputs (set_output_cov('integrated')) needs n >= q + 2 points, "
+                             f"got n = {self.n}")
 
     def _no_outputs(self, what):
         """Raised before the call by everything that has no form under several outputs."""
@@ -536,6 +559,7 @@ class MiGP:
         """Factorise for prediction (conditional form); returns LAPACK-style info."""
         if self.nout > 1 and self._trend != 0:
             self._no_outputs("a trend")
+        self._outcov_needs_points()
         theta, tp = self._theta(theta)
         self._factored_ok = False
         self._u_theta_ok = False
@@ -749,7 +773,8 @@ class MiGP:
         ``via_inverse``: use U = L^-T and one GEMM per chunk (mi_gp_predict_u) instead of the blocked triangular
         solve; default: when the gradient buffers exist and the sweep is large enough to pay for forming U
         (or U is already resident from an earlier sweep at this theta).  Under a trend (set_trend) the blocked solve is the only
-        route: ``via_inverse=True`` raises ValueError."""
+        route: ``via_inverse=True`` raises ValueError.  Under several outputs the mean is (m, q); the variance is (m,), or (m, q)
+        under set_output_cov("integrated")."""
         if via_inverse:
             self._no_trend("predict(via_inverse=True)")
             self._no_outputs("predict(via_inverse=True)")
@@ -769,8 +794,9 @@ class MiGP:
         if via_inverse and self.Z_t is None:
             raise RuntimeError("this MiGP was created with need_grad=False")
         q = self.nout  # (q >= 2: mi_gp_predict writes q * mc means, output-major, and mc variances)
+        qv = q if (self._outcov and q > 1) else 1  # (set_output_cov("integrated"): q * mc variances, output-major)
         mean = np.empty(m) if q == 1 else np.empty((m, q))
-        var = np.empty(m)
+        var = np.empty(m) if qv == 1 else np.empty((m, q))
         with torch.cuda.device(self.dev):
             for s in range(0, m, chunk):
                 mc = min(chunk, m - s)
@@ -784,7 +810,7 @@ class MiGP:
                     # moments come out through PINNED host memory the kernels address directly -- no torch copies, no torch
                     # synchronisation, one stream synchronisation inside the call (110 -> ~45 us per call at N = 512).  Same
                     # kernels on the same values: same bits as the device-buffer route below.
-                    io = self._pinned_io(mc * self.d + (q + 1) * mc)
+                    io = self._pinned_io(mc * self.d + (q + qv) * mc)
                     io_np = io.numpy()
                     io_np[: mc * self.d] = Xnew[s : s + mc].ravel()
                     base = io.data_ptr()
@@ -796,11 +822,12 @@ class MiGP:
                         self._u_theta_ok = True
                     mu = io_np[mc * self.d : mc * self.d + q * mc]
                     mean[s : s + mc] = mu if q == 1 else mu.reshape(q, mc).T
-                    var[s : s + mc] = io_np[mc * self.d + q * mc : mc * self.d + (q + 1) * mc]
+                    vr = io_np[mc * self.d + q * mc : mc * self.d + (q + qv) * mc]
+                    var[s : s + mc] = vr if qv == 1 else vr.reshape(q, mc).T
                     continue
                 xn = torch.from_numpy(Xnew[s : s + mc]).to(self.dev)
                 mu_t = torch.empty(q * mc, dtype=torch.float64, device=self.dev)
-                var_t = torch.empty(mc, dtype=torch.float64, device=self.dev)
+                var_t = torch.empty(qv * mc, dtype=torch.float64, device=self.dev)
                 torch.cuda.synchronize(self.dev)
                 fn = self.lib.mi_gp_predict_u if via_inverse else self.lib.mi_gp_predict
                 self._check(fn(self.h, xn.data_ptr(), mc, self._work.data_ptr(), self.lda, mu_t.data_ptr(),
@@ -809,7 +836,7 @@ class MiGP:
                 if via_inverse:
                     self._u_theta_ok = True
                 mean[s : s + mc] = mu_t.cpu().numpy() if q == 1 else mu_t.cpu().numpy().reshape(q, mc).T
-                var[s : s + mc] = var_t.cpu().numpy()
+                var[s : s + mc] = var_t.cpu().numpy() if qv == 1 else var_t.cpu().numpy().reshape(q, mc).T
         return mean, var
 
     def predict_grad(self, theta, Xnew, pred_noise=True, refactor=True):
@@ -971,6 +998,11 @@ class MiGP:
         """Per-handle tuning knobs (include/mi_gp.h: 0 look-ahead, 2 super-panel width, 7 small-tile threshold,
         8 one-workgroup-per-CU bulk updates, 14 tile order); unknown ids raise."""
         self._check(self.lib.mi_gp_set_option(self.h, int(what), int(value)), "mi_gp_set_option")
+        if int(what) == 52 and int(value) != self._outcov:
+            # (predict sizes its variance from this mirror of the option; a change ends the resident factorisation)
+            self._outcov = int(value)
+            self._factored_ok = False
+            self._u_theta_ok = False
 
     def get_option(self, what, default=None):
         """Current value of a knob on this handle, the library's own defaults included (mi_gp_get_option; 40: 1 once the handle

@@ -266,6 +266,32 @@ static int special_option(mi_gp_handle* h, int what, const int* set, int* get) {
         *get = h->nout;
       }
       return 1;
+    case 52:  // the covariance BETWEEN the outputs (a change ends the resident state as mi_gp_set_data does)
+      if (set) {
+        if (*set != 0 && *set != 1) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 52 is 0 (independent outputs) or 1 (the between-output covariance "
+                   "integrated out), got %d", *set);
+          return -1;
+        }
+        if (*set != 0 && !(multi_objective && multi_factor && multi_predict_reduce)) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the between-output covariance (option 52 = %d) is not part of this build", *set);
+          return -1;
+        }
+        if (*set != h->outcov) {
+          h->outcov = *set;
+          h->factored = h->have_kinv = h->have_u = false;
+          h->b_cond_k = 0;
+          // the outputs' scratch is laid out for the option's value: its next use allocates it again (every entry point returns
+          // with the stream synchronised)
+          if (h->multi_blk.p) {
+            (void)hipSetDevice(h->device);
+            (void)resize_block(h->multi_blk, 0, 0);
+          }
+        }
+      } else {
+        *get = h->outcov;
+      }
+      return 1;
   }
   return 0;
 }
@@ -531,6 +557,7 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
              h->objective == 1 ? "a cross-validation objective (option 48 = 1)" : "a trend (option 50)");
     return -1;
   }
+  if (refuse_outcov(h, "mi_gp_lml_grad")) return -1;
   if (h->trend != 0 && (h->objective == 1 || h->n <= trend_columns(h))) {
     if (h->objective == 1)
       snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad: no cross-validation objective (option 48 = 1) under a trend (option 50 = %d)", h->trend);
@@ -697,6 +724,7 @@ extern "C" int mi_gp_factor(mi_gp_handle* h, const double* theta) {
     snprintf(h->err, sizeof(h->err), "mi_gp_factor: several outputs (option 51 = %d) have no form under a trend (option 50)", h->nout);
     return -1;
   }
+  if (refuse_outcov(h, "mi_gp_factor")) return -1;
   if (h->trend != 0 && h->n <= trend_columns(h)) {
     snprintf(h->err, sizeof(h->err), "mi_gp_factor: the trend (option 50 = %d) has %d coefficients, n = %d must exceed that", h->trend,
              trend_columns(h), h->n);

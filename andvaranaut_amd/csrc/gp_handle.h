@@ -137,6 +137,9 @@ struct mi_gp_handle {
   int nout;                // option 51: the number of OUTPUTS q under one shared kernel -- 1 (default) the single y, 2..128 the vectors
                            // y_dev[o * lda ..) (mi_gp_lml_grad, mi_gp_factor and mi_gp_predict; api_multi.hip)
   CapBlock multi_blk;      // its scratch (MultiScratch, api_multi.hip; allocated by the first use)
+  int outcov;              // option 52: the covariance BETWEEN the outputs of option 51 = q >= 2 -- 0 (default) none, the outputs
+                           // independent under one variance; 1 a q x q Sigma under the Jeffreys prior, integrated out (api_multi.hip).
+                           // Part of multi_blk's layout: a change drops the block
   char err[256];
 };
 
@@ -306,11 +309,15 @@ inline int refuse_trend(mi_gp_handle* h, const char* entry) {
 // api_multi.hip: several outputs under one shared kernel (option 51; include/mi_gp.h has the algebra).  Weak like loo_objective:
 // without the file option 51 >= 2 is refused.
 // the tail of mi_gp_lml_grad behind a successful ordinary evaluation (K^-1 in W_dev; out_host[1] the factorisation's logdet):
-// *value = L_MO and grad[ntheta] its gradient, W_dev's lower triangle then holds q K^-1 - V V^T; 0 or a C-ABI error code
+// *value = L_MO and grad[ntheta] its gradient, W_dev's lower triangle then holds q K^-1 - V V^T; 0 or a C-ABI error code.
+// Under option 52 = 1: *value = L_S, W_dev's lower triangle then holds q K^-1 - n V S^-1 V^T; 0, n + j for a bad pivot j of
+// S = Y^T K^-1 Y (-inf, zero gradient) or a C-ABI error code
 int multi_objective(mi_gp_handle* h, double* value, double* grad) __attribute__((weak));
-// behind a successful mi_gp_factor: B^T = Y^T L^-T (128 rows, rows from q on zero) in the handle's scratch; 0 or a C-ABI error code
+// behind a successful mi_gp_factor: B^T = Y^T L^-T (128 rows, rows from q on zero) in the handle's scratch, and under option
+// 52 = 1 the scales s_o = |b_o|^2 / (n - q - 1); 0 or a C-ABI error code
 int multi_factor(mi_gp_handle* h) __attribute__((weak));
-// mi_gp_predict's reduction under q outputs (the rows L^-1 k(X, x*) are in work_dev): mean[o * m + i], var[i]
+// mi_gp_predict's reduction under q outputs (the rows L^-1 k(X, x*) are in work_dev): mean[o * m + i], var[i] (option 52 = 1:
+// var[o * m + i])
 hipError_t multi_predict_reduce(mi_gp_handle* h, const double* work_dev, long ldw, int m, double* mean_dev, double* var_dev,
                                 int pred_noise) __attribute__((weak));
 // mi_gp_reserve's part: the scratch re-sized for `capacity` points, the conditional's B^T kept
@@ -319,6 +326,14 @@ hipError_t multi_reserve(mi_gp_handle* h, int capacity) __attribute__((weak));
 inline int refuse_multi(mi_gp_handle* h, const char* entry) {
   snprintf(h->err, sizeof(h->err), "%s has no form under several outputs (option 51 = %d): set option 51 to 1 first", entry, h->nout);
   return -1;
+}
+// option 52 = 1 under q >= 2 outputs integrates a q x q covariance out: n >= q + 2 (the predictive t has n - q + 1 degrees of
+// freedom, its variance needs more than two).  True -- and the text is set -- when the entry point must return -1
+inline bool refuse_outcov(mi_gp_handle* h, const char* entry) {
+  if (!(h->outcov && h->nout > 1) || h->n >= h->nout + 2) return false;
+  snprintf(h->err, sizeof(h->err), "%s: the between-output covariance (option 52 = 1) of q = %d outputs needs n >= q + 2, got n = %d",
+           entry, h->nout, h->n);
+  return true;
 }
 
 // api_gp.hip

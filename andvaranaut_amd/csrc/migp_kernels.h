@@ -387,9 +387,15 @@ hipError_t launch_multi_stage(const double* y, long ldy, int q, int n, int np, d
 // quad[o] = sum_{i < n} YT[o * ldg + i] V[i * 128 + o] for o < q, zeros up to 127; every sum in a fixed order
 hipError_t launch_multi_quad(const double* YT, long ldg, const double* V, int q, int n, double* quad, hipStream_t stream);
 // mi_gp_predict's reduction under q outputs, ONE pass over the m rows a* of A (lda apart; BT = (L^-1 Y)^T, 128 rows ldg apart):
-// mean[o * m + i] = a*_i . b_o for o < q, var[i] = kdiag - |a*_i|^2 + noise; each output is written once
+// mean[o * m + i] = a*_i . b_o for o < q, var[i] = kdiag - |a*_i|^2 + noise; each output is written once.  svar (option 52 = 1,
+// else nullptr): q scales s_o, and var[o * m + i] = (kdiag - |a*_i|^2 + noise) * s_o for o < q instead
 hipError_t launch_multi_predict(const double* A, long lda, const double* BT, long ldg, int q, int n, int m, double kdiag, double noise,
-                                double* mean, double* var, hipStream_t stream);
+                                const double* svar, double* mean, double* var, hipStream_t stream);
+// option 52 = 1: scal[0] = sum_{j < q} log C[j * 129] of the factored block of S = Y^T K^-1 Y in index order, scal[1] = its bad-pivot
+// word
+hipError_t launch_multi_cov_scal(const double* C, const int* info, int q, double* scal, hipStream_t stream);
+// option 52 = 1: s[o] = sum_{i < n} BT[o * ldg + i]^2 / dof for o < q, zeros up to 127; every sum in a fixed order
+hipError_t launch_multi_rowsq(const double* BT, long ldg, int q, int n, double dof, double* s, hipStream_t stream);
 
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)

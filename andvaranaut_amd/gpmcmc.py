@@ -400,6 +400,7 @@ class GPMCMC(ConsumersMixin):
         self.hypers = None
         self.trend = None
         self.outputs = "first"
+        self.output_cov = "shared"
 
     def __release(self):
         gp = getattr(self, "gp", None)
@@ -423,6 +424,7 @@ class GPMCMC(ConsumersMixin):
                 self.gp.set_trend(self.trend)
             if getattr(self, "outputs", "first") == "all":
                 self.gp.set_outputs(self._converted_outputs(self.y - self.ym))
+                self.gp.set_output_cov(getattr(self, "output_cov", "shared"))
         return self.gp
 
     def _no_trend(self, what):
@@ -441,7 +443,8 @@ class GPMCMC(ConsumersMixin):
 
     # ------------------------------------------------------------------ fit
     def fit(self, method="map", return_data=False, iwgp=False, cwgp=False, jitter=1e-6, truncate=False,
-            restarts=1, objective="lml", nfolds=10, fold_seed=None, trend=None, outputs="first", **kwargs):
+            restarts=1, objective="lml", nfolds=10, fold_seed=None, trend=None, outputs="first", output_cov="shared",
+            **kwargs):
         """gpmcmc.py:175-182.  ``objective="loo"`` (with ``method="map"``) maximises the leave-one-out log predictive density
         sum_i log p(y_i | y_-i) plus the priors instead of the log marginal likelihood (Rasmussen & Williams section 5.4.2: the
         criterion for a misspecified kernel family); the hyper-parameters are stored as a MAP fit stores them.  It has no
@@ -460,14 +463,27 @@ class GPMCMC(ConsumersMixin):
         ``method="map"``, ``objective="lml"``, no trend, no warps) models every column under ONE shared kernel and one noise,
         column i converted by ``yconrevs[i]``, the outputs independent given the hyper-parameters: the fit maximises the sum of
         the columns' log marginal likelihoods plus the priors on one factorisation per evaluation, and ``predict`` returns
-        (M, ny) arrays.  The choice is part of the object's state (``self.outputs``)."""
+        (M, ny) arrays.  The choice is part of the object's state (``self.outputs``).
+        ``output_cov="shared"`` (default) is that model: one variance for every output, in converted units.
+        ``output_cov="integrated"`` (with ``outputs="all"``, at least ny + 2 points) gives the outputs a ny x ny covariance Sigma,
+        vec(Y) ~ N(0, Sigma (x) K_y), under the Jeffreys prior |Sigma|^-(ny+1)/2 and integrates it out in closed form (the
+        separable emulator of Conti & O'Hagan 2010): the fit no longer depends on how the columns are scaled or mixed, and
+        ``predict(return_var=True)`` returns a variance per output, column i reverted through ``yconrevs[i]``.  That marginal
+        likelihood does not change under K_y -> c K_y, so only their priors identify the overall scale of kv, gv and the
+        jitter.  The choice is part of the object's state (``self.output_cov``)."""
         if outputs not in ("first", "all"):
             raise ValueError(f"outputs must be 'first' or 'all' (got {outputs!r})")
+        if output_cov not in MiGP.OUTPUT_COVS:
+            raise ValueError(f"output_cov must be one of {list(MiGP.OUTPUT_COVS)} (got {output_cov!r})")
+        if output_cov != "shared" and outputs != "all":
+            raise ValueError(f"output_cov={output_cov!r} needs outputs='all'")
         if outputs == "all":
             if self.ny < 2:
                 raise ValueError("outputs='all' needs ny >= 2")
             if method != "map" or objective != "lml" or trend is not None or iwgp or cwgp:
                 raise ValueError("outputs='all' needs method='map', objective='lml', trend=None and neither iwgp nor cwgp")
+            if output_cov != "shared" and self.x is not None and len(self.x) < self.ny + 2:
+                raise ValueError(f"output_cov={output_cov!r} needs at least ny + 2 = {self.ny + 2} points, got {len(self.x)}")
         if trend is not None:
             if trend not in ("constant", "linear"):
                 raise ValueError(f"trend must be None, 'constant' or 'linear' (got {trend!r})")
@@ -482,9 +498,10 @@ class GPMCMC(ConsumersMixin):
             raise ValueError("objective='loo' needs method='map' and neither iwgp nor cwgp")
         self.m, self.gp, self.hypers, data = self.__fit(self.x, self.y - self.ym, method, iwgp, cwgp, jitter,
                                                         truncate, restarts, objective=objective, cv=cv, trend=trend, outputs=outputs,
-                                                        **kwargs)
+                                                        output_cov=output_cov, **kwargs)
         self.trend = trend
         self.outputs = outputs
+        self.output_cov = output_cov
         if return_data:
             return data
 
@@ -612,7 +629,7 @@ class GPMCMC(ConsumersMixin):
         return likelihood
 
     def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", cv=None, trend=None,
-              outputs="first", **kwargs):
+              outputs="first", output_cov="shared", **kwargs):
         n_i, n_pos, n_free = self._warp_sizes(iwgp, cwgp)
         model = HyperModel(self.nx, self.kerns, noise=self.noise, truncate=truncate, jitter=jitter, n_iwgp=n_i,
                            n_cwgp_pos=n_pos, n_cwgp=n_free)
@@ -623,6 +640,7 @@ class GPMCMC(ConsumersMixin):
             gp.set_trend(trend)  # (gp.lml_grad then returns the trend's marginal likelihood; the stored handle keeps the trend)
         if outputs == "all":
             gp.set_outputs(self._converted_outputs(y))  # (gp.lml_grad then returns the sum of the columns' marginal likelihoods)
+            gp.set_output_cov(output_cov)  # ("integrated": the marginal likelihood with the between-output covariance integrated out)
         lik = self._warp_likelihood(gp, x, y, xin, iwgp, cwgp) if (iwgp or cwgp) else None
         # pm.find_MAP maximises without the transform Jacobian, pm.sample with it (priors.py header)
         fun_map = lambda q: model.logp_dlogp(q, gp.lml_grad, jacobian=False, likelihood=lik)  # noqa: E731
@@ -881,7 +899,8 @@ class GPMCMC(ConsumersMixin):
     def predict(self, x, return_var=False, convert=True, revert=True, normvar=False, jitter=1e-6, EI=False,
                 EIopt=None, deg=8):
         """gpmcmc.py:522-542.  Under ``outputs="all"`` the mean and the variance are (M, ny): column i is reverted through its
-        own ``yconrevs[i]`` by the same Gauss-Hermite reversion and the mean function's column i is added to it."""
+        own ``yconrevs[i]`` by the same Gauss-Hermite reversion and the mean function's column i is added to it.  Under
+        ``output_cov="integrated"`` column i starts from its own converted variance, otherwise every column from the shared one."""
         if EI:
             self._no_all_outputs("predict(EI=True)")
         if self._ensure_gp() is None or self.hypers is None:
@@ -902,7 +921,7 @@ class GPMCMC(ConsumersMixin):
         if self.verbose:
             print(f"Time taken: {stopwatch() - t0:0.2f} s")
         if getattr(self, "outputs", "first") == "all":
-            cols = [(mu[:, i : i + 1], var.reshape((-1, 1))) for i in range(self.ny)]
+            cols = [(mu[:, i : i + 1], var[:, i : i + 1] if var.ndim == 2 else var.reshape((-1, 1))) for i in range(self.ny)]
             if revert:
                 cols = [self.__gh_stats(x, yi, yvi, normvar, deg, col=i) for i, (yi, yvi) in enumerate(cols)]
             y, yv = np.hstack([c[0] for c in cols]), np.hstack([c[1] for c in cols])

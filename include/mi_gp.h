@@ -526,7 +526,47 @@ MI_GP_API int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host,
  * Unknown ids return -1.  (Round 1's options 1, 3, 10-13 -- GEMM variants, hipGraph replay, persistent bulk kernels,
  * exclusive leaf, fused leaf + strip -- and round 5's 29, 33, 34, 36, 39 -- forms that lost their A/B: the next-panel update's
  * occupancy as a knob, strided thin updates, that update in pieces, 64x128 tiles -- and round 3's 24, the assembly in two parts,
- * which stopped paying in round 6, are gone with the code they selected.) */
+ * which stopped paying in round 6, are gone with the code they selected.)
+ * Option 52 (not a tuning knob) the OUTPUT COVARIANCE of the q outputs of option 51: 0 (default) none -- the outputs independent
+ *      under one kernel variance, today's behaviour bit for bit and launch for launch; 1 the outputs share a q x q covariance
+ *      Sigma, vec(Y) ~ N(0, Sigma (x) K_y), under the Jeffreys prior p(Sigma) ~ |Sigma|^-(q+1)/2, and Sigma is integrated out in
+ *      closed form (the separable multi-output emulator; Conti & O'Hagan 2010).  theta and mi_gp_num_theta() stay as they are; Y
+ *      is bound as under option 51.  The option is read only while option 51 = q >= 2; with one output it is inert.  The result
+ *      does not change under an invertible re-mixing or re-scaling of the outputs (Y -> Y M moves L_S by -n log|det M| and leaves
+ *      the gradient), and it gives every output its own predictive variance.  It needs n >= q + 2: otherwise mi_gp_lml_grad and
+ *      mi_gp_factor return -1 before any device call, with a text that names option 52.
+ *      mi_gp_lml_grad runs the ordinary evaluation first (same launches, same schedule), then option 51's tail with S in the
+ *      place of the quads:
+ *          V = K_y^-1 Y,   S = Y^T V = C_S C_S^T                                                               (q x q)
+ *          L_S = -q sum_i log L_ii - n sum_j log (C_S)_jj + log Gamma_q(n/2) - n q/2 log pi
+ *          log Gamma_q(a) = q (q - 1) / 4 log pi + sum_{j = 1 .. q} lgamma(a + (1 - j) / 2)                     (on the host)
+ *          dL_S/dtheta_k = 1/2 sum_ij (n V S^-1 V^T - q K_y^-1)_ij dK_ij/dtheta_k               (d/d jitter = d/d gv)
+ *      -- S as option 50's block A: the k-segmented 128 x 128 Gram product Y^T V, its segments added in index order, the
+ *      identity in the padding; the 128 x 128 leaf factorises it in place and its row-major inverse follows; one small kernel
+ *      adds log (C_S)_jj in index order and forwards the bad-pivot word; Q = sqrt(n) V C_S^-T on the GEMM; the update
+ *      W <- q W - Q Q^T over the lower trapezoid (alpha = -1, beta = q, k = 128); and the LML gradient's contraction kernel with
+ *      that W and a zero vector in the place of alpha.  *lml_out = L_S.  Afterwards the lower triangle of W_dev holds
+ *      q K^-1 - n V S^-1 V^T, and the handle marks K^-1 not resident, as under option 51; mi_gp_lml_parts keeps the factorisation's
+ *      logdet and output 0's quad.  If S is not positive definite (a zero column of Y; collinear columns, as far as rounding
+ *      leaves the pivot non-positive) the call returns n + j, j the 1-based pivot among the outputs, with L_S = -inf and a
+ *      zero gradient, as option 50 does for its block; the handle stays usable.  A bad pivot of K_y is reported as always.
+ *      L_S does not change under K_y -> c K_y (S scales by 1/c, log|K_y| by n log c): kv, gv and the jitter are identified up to
+ *      a common factor only, which their priors must fix (for one kernel component without a diagonal of mi_gp_set_diag,
+ *      kv dL_S/dkv + gv dL_S/dgv + jitter dL_S/djitter = 0).
+ *      mi_gp_factor additionally keeps s_o = |b_o|^2 / (n - q - 1) for o < q (b_o = L^-1 y_o, the rows of option 51's B^T: the
+ *      diagonal of S in the conditional form) in the handle's scratch, and mi_gp_predict writes
+ *          mean_dev[o * m + i] exactly as under option 51, with the same bits,
+ *          var_dev[o * m + i] = (kdiag - |a*_i|^2 (+ gv if pred_noise)) * s_o          (q * m doubles, output-major)
+ *      -- the variance of the predictive multivariate t with n - q + 1 degrees of freedom -- from the same ONE pass over the
+ *      rows of work_dev, whose contract (size, layout) does not change; var_dev must hold q * m doubles.  mi_gp_reserve carries
+ *      s_o along with B^T, so the handle stays factored.
+ *      Everything option 51 refuses stays refused, with option 51's text.  The same call in the same state returns the same
+ *      bits; every element a launch reads is written earlier in the same call; the scheduling options change no bit; no sum
+ *      uses atomics.  Values outside 0..1 return -1, and so does 1 in a build without option 51's tail (the host-only
+ *      schedule-trace program).  Setting a value other than the current one ends the resident state exactly as mi_gp_set_data
+ *      does (and frees the outputs' scratch, whose layout the value is part of); setting the current value changes nothing.
+ *      Out of scope: the off-diagonal predictive covariance between outputs; reading Sigma out; q = 1 (the scale of one output
+ *      integrated out); the batched and sharded forms; everything option 51 already lists. */
 MI_GP_API int mi_gp_set_option(mi_gp_handle* h, int what, int value);
 /* current value of a knob, the library's own defaults included; 40 (read-only): 1 once the handle has switched its cross-stream
  * edges to events by itself (option 26) */
