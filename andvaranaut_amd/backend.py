@@ -884,6 +884,50 @@ class MiGP:
         return (o[:m], o[m : 2 * m], o[2 * m : 2 * m + m * self.d].reshape(m, self.d),
                 o[2 * m + m * self.d :].reshape(m, self.d))
 
+    def mean_sweep(self, theta, Xnew, grad=False, chunk=1 << 20):
+        """Posterior mean at Xnew (converted inputs) by the matrix-free sweep (option 53 of mi_gp_set_option): mu = sum_j k(x*, x_j)
+        alpha_j, O(n d) per point with no work rows -- the route of sensitivity sweeps of 1e5 .. 1e7 points that read no variance.
+        Returns mean (m,), or (mean, dmean (m, d)) with ``grad``: the gradient w.r.t. the points.  A point's bits do not depend on
+        the other points, on its position or on ``chunk``.  d <= 128.  The option is 0 again afterwards."""
+        self._no_trend("mean_sweep")
+        self._no_outputs("mean_sweep")
+        if self.Z_t is None:
+            raise RuntimeError("this MiGP was created with need_grad=False")
+        self._ensure_factored(theta)
+        Xnew = np.ascontiguousarray(Xnew, dtype=np.float64)
+        if Xnew.ndim != 2 or Xnew.shape[1] != self.d:
+            raise ValueError("Xnew must be (m, d)")
+        m, d = Xnew.shape
+        chunk = max(1, int(chunk))
+        mean = np.empty(m)
+        dmean = np.empty((m, d)) if grad else None
+        self.set_option(53, 1)
+        try:
+            with torch.cuda.device(self.dev):
+                for s in range(0, m, chunk):
+                    mc = min(chunk, m - s)
+                    nout = mc + (mc * d if grad else 0)
+                    if mc <= self.PINNED_IO_MAX_POINTS:  # (pinned I/O as in predict_grad)
+                        io = self._pinned_io(mc * d + nout)
+                        io_np = io.numpy()
+                        io_np[: mc * d] = Xnew[s : s + mc].ravel()
+                        x_p = io.data_ptr()
+                        o_p = x_p + 8 * mc * d
+                    else:
+                        xn = torch.from_numpy(Xnew[s : s + mc]).to(self.dev)
+                        out = torch.empty(nout, dtype=torch.float64, device=self.dev)
+                        torch.cuda.synchronize(self.dev)
+                        x_p, o_p = xn.data_ptr(), out.data_ptr()
+                    self._check(self.lib.mi_gp_predict_grad(self.h, x_p, mc, None, 0, o_p, None, 0, o_p + 8 * mc if grad else None,
+                                                            None), "mi_gp_predict_grad")
+                    o = io_np[mc * d : mc * d + nout] if mc <= self.PINNED_IO_MAX_POINTS else out.cpu().numpy()
+                    mean[s : s + mc] = o[:mc]
+                    if grad:
+                        dmean[s : s + mc] = o[mc:].reshape(mc, d)
+        finally:
+            self.set_option(53, 0)
+        return (mean, dmean) if grad else mean
+
     # ---------------------------------------------------------------- joint conditional and posterior draws
     # One call per request, nothing chunked: device memory bounds M.  predict_cov holds Sigma (mp^2 doubles, mp = M rounded up
     # to 128) beside the cross-covariance rows (mp x (padded n + 16)); sample_posterior adds mi_gp_sample_cov_work(M, s) =

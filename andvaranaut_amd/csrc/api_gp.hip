@@ -65,7 +65,7 @@ static void release_handle(mi_gp_handle* h) {
   free_scratch(h->one);
   free_scratch(h->batch);
   (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
-  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk, &h->multi_blk}) (void)hipFree(b->p);
+  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk, &h->multi_blk, &h->sweep_blk}) (void)hipFree(b->p);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -290,6 +290,21 @@ static int special_option(mi_gp_handle* h, int what, const int* set, int* get) {
         }
       } else {
         *get = h->outcov;
+      }
+      return 1;
+    case 53:  // what mi_gp_predict_grad is (no resident state changes with it)
+      if (set) {
+        if (*set != 0 && *set != 1) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 53 is 0 (the conditional and its gradients) or 1 (the mean sweep), got %d", *set);
+          return -1;
+        }
+        if (*set == 1 && !mean_sweep) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the mean sweep (option 53 = 1) is not part of this build");
+          return -1;
+        }
+        h->sweep = *set;
+      } else {
+        *get = h->sweep;
       }
       return 1;
   }
@@ -1013,7 +1028,9 @@ extern "C" int mi_gp_predict_u(mi_gp_handle* h, const double* Xnew_dev, int m, d
 extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw,
                                   double* mean_dev, double* var_dev, int pred_noise, double* dmean_dev,
                                   double* dvar_dev) {
-  if (!h || !dmean_dev || !dvar_dev) return -1;
+  if (!h) return -1;
+  if (h->sweep) return mean_sweep(h, Xnew_dev, m, mean_dev, dmean_dev);  // option 53 = 1: another call behind the same entry point
+  if (!dmean_dev || !dvar_dev) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_grad");
   if (h->nout > 1) return refuse_multi(h, "mi_gp_predict_grad");
   if (!h->buf.Z_dev || !h->buf.W_dev) {
@@ -1077,7 +1094,7 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   h->cap = capacity;
   // the capacity-sized blocks: the objectives' hold nothing between calls and are dropped (their next use re-sizes them), the
   // trend's keeps the conditional's G^T, beta^ and b~
-  for (CapBlock* b : {&h->loo, &h->cv}) (void)resize_block(*b, 0, 0);
+  for (CapBlock* b : {&h->loo, &h->cv, &h->sweep_blk}) (void)resize_block(*b, 0, 0);
   if (h->trend_blk.p && trend_reserve) HCK(trend_reserve(h, capacity), "mi_gp_reserve");
   if (h->multi_blk.p && multi_reserve) HCK(multi_reserve(h, capacity), "mi_gp_reserve");  // (keeps the conditional's B^T)
   return 0;

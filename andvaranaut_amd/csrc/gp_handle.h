@@ -140,6 +140,10 @@ struct mi_gp_handle {
   int outcov;              // option 52: the covariance BETWEEN the outputs of option 51 = q >= 2 -- 0 (default) none, the outputs
                            // independent under one variance; 1 a q x q Sigma under the Jeffreys prior, integrated out (api_multi.hip).
                            // Part of multi_blk's layout: a change drops the block
+  int sweep;               // option 53: what mi_gp_predict_grad is -- 0 (default) the conditional and its gradients, 1 the MEAN SWEEP,
+                           // the matrix-free posterior mean and its input gradient (mean_sweep(), api_sweep.hip)
+  CapBlock sweep_blk;      // its scratch: the training points staged for the kernel and the partial sums of one pass of query
+                           // points (sweep_f64.hip: sweep_scratch_len; allocated by the first sweep, holds nothing between calls)
   char err[256];
 };
 
@@ -335,6 +339,10 @@ inline bool refuse_outcov(mi_gp_handle* h, const char* entry) {
            entry, h->nout, h->n);
   return true;
 }
+
+// api_sweep.hip: mi_gp_predict_grad under option 53 = 1 (include/mi_gp.h has the contract).  Weak like loo_objective: without the
+// file option 53 = 1 is refused.  0 or a C-ABI error code; every refusal comes before any HIP call
+int mean_sweep(mi_gp_handle* h, const double* Xnew_dev, int m, double* mean_dev, double* dmean_dev) __attribute__((weak));
 
 // api_gp.hip
 hipError_t trsm_rec(mi_gp_handle* h, const Eval& E, double* Bw, long ldw, int mp, int c0, int w);  // X L^T = B in place

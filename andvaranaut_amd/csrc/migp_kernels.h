@@ -397,6 +397,19 @@ hipError_t launch_multi_cov_scal(const double* C, const int* info, int q, double
 // option 52 = 1: s[o] = sum_{i < n} BT[o * ldg + i]^2 / dof for o < q, zeros up to 127; every sum in a fixed order
 hipError_t launch_multi_rowsq(const double* BT, long ldg, int q, int n, double dof, double* s, hipStream_t stream);
 
+// ---------------------------------------------------------------- sweep_f64.hip (option 53: the mean sweep, api_sweep.hip)
+constexpr int SWEEP_MAX_D = 128;  // input dimensions the sweep's register windows cover
+constexpr int SWEEP_PARTS = 16;   // parts of the training range, [y q, min((y + 1) q, n)) with q = ceil(n / 16): a rule of n alone
+int sweep_stride(int d);                    // padded row length of the staged training points
+// doubles of scratch for up to cap training points: the staged points, 1 / l and 2 / l^2, the partial sums of one pass of query
+// points and (d > 32) the pass's query points
+size_t sweep_scratch_len(int cap, int d);
+// mean[p] = sum_j k(x*_p, x_j) alpha_j and dmean[p][.] = its gradient w.r.t. x*_p for p < m, each optional (not both null): one
+// thread per point and part, j in index order, the parts' sums added in part order; d <= SWEEP_MAX_D.  scratch is staged by the
+// same call; the query points are walked in passes of 16384 (d > 32: 4096)
+hipError_t launch_mean_sweep(const KernSpec& spec, const double* theta, const double* X, int n, const double* xstar, int m,
+                             const double* alpha, double* scratch, double* mean, double* dmean, hipStream_t stream);
+
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)
 void set_global_error(const char* text);

@@ -2,6 +2,7 @@
 // K and dK/dtheta are built from the SAME exp / sqrt sequences, so they are bit-consistent with each other.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "migp_kernels.h"
 
 namespace migp {
 
@@ -45,6 +46,54 @@ __device__ __forceinline__ double sqrt_pos(double t) {
   h = __builtin_fma(h, e, h);
   const double dd = __builtin_fma(-g, g, t);
   return __builtin_fma(dd, h, g);
+}
+
+// d k / d r2 of the base kernels (matches oracle base_kernel_dr2) and the value itself
+__device__ __forceinline__ void base_kernel_val_der(int kid, double r2, double alpha, double& k, double& dk,
+                                                    double& dalpha) {
+  dalpha = 0.0;
+  if (kid == KID_RATQUAD) {
+    const double u = 0.5 * r2 / alpha;
+    k = pow(1.0 + u, -alpha);
+    dk = -0.5 * k / (1.0 + u);
+    dalpha = k * (-log1p(u) + u / (1.0 + u));
+    return;
+  }
+  // the four exponential families share ONE exp evaluation: e = exp(-rate * s), s = r2 (RBF) or r = sqrt(r2 + 1e-12)
+  const bool rbf = kid == KID_RBF;
+  const double r = rbf ? 0.0 : sqrt_pos(r2 + 1e-12);
+  const double rate = rbf ? 0.5 : kid == KID_MATERN52 ? 2.23606797749979 : kid == KID_MATERN32 ? 1.7320508075688772 : 0.5;
+  const double e = exp_nonpos(-1.0 * rate * (rbf ? r2 : r));
+  if (rbf) {
+    k = e;
+    dk = -0.5 * e;
+  } else if (kid == KID_MATERN52) {
+    k = (1.0 + 2.23606797749979 * r + 5.0 / 3.0 * (r * r)) * e;
+    dk = -(5.0 / 6.0) * (1.0 + 2.23606797749979 * r) * e;
+  } else if (kid == KID_MATERN32) {
+    k = (1.0 + 1.7320508075688772 * r) * e;
+    dk = -1.5 * e;
+  } else {
+    k = e;
+    dk = -0.25 * e / r;
+  }
+}
+
+// NK = 8 is the one instantiation for 5..8 components: it reads the count at run time, `RUNTIME_NK<NK> ? spec.nkern : NK`
+template <int NK>
+constexpr bool RUNTIME_NK = NK > 4;
+
+// Component c at scaled squared distance r2: kval = kv_c k, dkv = kv_c dk/dr2 and, only under RQ (some component is a
+// rational quadratic), dal = kv_c dk/dalpha -- identically zero otherwise, and then not carried.  kvc is a reference so
+// that a caller's kv[c] is read where it is used.
+template <bool RQ>
+__device__ __forceinline__ void comp_val_der(int kid, double r2, double alpha, const double& kvc, double& kval, double& dkv,
+                                             double& dal) {
+  double k, dk, da;
+  base_kernel_val_der(kid, r2, alpha, k, dk, da);
+  kval = kvc * k;
+  dkv = kvc * dk;
+  if constexpr (RQ) dal = kvc * da;
 }
 
 }  // namespace migp

@@ -349,9 +349,10 @@ class GPMCMC(ConsumersMixin):
             print(f"Log predictive density is: {out['lpd']:0.5e}")
         return out
 
-    def y_dist(self, mode="hist_kde", nsamps=None, return_data=False, surrogate=True, seed=None):
+    def y_dist(self, mode="hist_kde", nsamps=None, return_data=False, surrogate=True, seed=None, mean_only=False):
         """Uncertainty propagation through the surrogate (gpmcmc.py:140-151; tutorial.ipynb cell 34): a Latin-hypercube sample of the
-        input priors is pushed through ``predict`` (one device sweep via U = L^-T for large ``nsamps``).  The density plots of
+        input priors is pushed through ``predict`` (one device sweep via U = L^-T for large ``nsamps``), or with ``mean_only=True``
+        through ``predict_mean``, the matrix-free sweep (samples large enough for a tail).  The density plots of
         LHC.__y_dist (lhc.py:100-110) are outside this backend's scope: ``mode`` is validated as there and otherwise ignored.
         ``surrogate=False``: the underlying data set.  ``return_data=True`` returns (x, y) as the reference does."""
         modes = ["hist", "kde", "ecdf", "hist_kde"]
@@ -362,7 +363,7 @@ class GPMCMC(ConsumersMixin):
         if not surrogate:
             return (self.x, self.y) if return_data else None
         xsamps = latin_sample(self.priors, nsamps, seed)
-        ypreds = self.predict(xsamps)
+        ypreds = self.predict_mean(xsamps) if mean_only else self.predict(xsamps)
         if return_data:
             return xsamps, ypreds
 
@@ -372,6 +373,75 @@ class GPMCMC(ConsumersMixin):
             raise Exception("Error: fit the GP before asking for relative importances")
         ri = 1.0 / np.asarray(self.hypers["l"], dtype=np.float64)
         return np.log(ri) if logscale else ri
+
+    # ------------------------------------------------------------------ mean-only sweeps and sensitivity analysis
+    def predict_mean(self, x, convert=True, revert=True, return_grad=False, jitter=1e-6):
+        """The posterior mean at x (M, nx) by the matrix-free sweep (MiGP.mean_sweep: O(n d) per point, no variance), an (M, 1)
+        array -- the route of sweeps of 1e5 .. 1e7 points.  ``revert=False``: the converted-space mean mu.  ``revert=True``: the
+        plug-in surrogate yconrevs[0].rev(mu) + mean function.  That is NOT the Gauss-Hermite mean of ``predict``, which averages
+        the reverted variable over the predictive normal: the two agree for an affine output conversion and differ by the
+        conversion's curvature times the predictive variance otherwise.  ``return_grad=True`` returns (mean, grad (M, nx)), the
+        gradient w.r.t. the inputs x as they are passed: rev'(mu) d mu / d xc_m con'_m(x_m), without rev' under ``revert=False``
+        and without con' under ``convert=False``; a non-zero mean function has no derivative here and raises ValueError."""
+        from .consumers import _con_and_der
+
+        self._no_trend("predict_mean")
+        self._no_all_outputs("predict_mean")
+        if return_grad and self.mean != self.zero_mean:
+            raise ValueError("predict_mean(return_grad=True) has no form under a non-zero mean function")
+        if self._ensure_gp() is None or self.hypers is None:
+            raise Exception("Error: fit the GP before predicting")
+        xarg, x = self._converted_x(np.asarray(x, dtype=np.float64), convert)
+        theta = self._theta_from_hypers(self.hypers, jitter)
+        if return_grad:
+            mu, g = self.gp.mean_sweep(theta, xarg, grad=True)
+        else:
+            mu = self.gp.mean_sweep(theta, xarg)
+        y = self.yconrevs[0].rev(mu) + self._mean_at(x) if revert else mu
+        if not return_grad:
+            return np.reshape(y, (-1, 1))
+        if revert:
+            g = g / np.reshape(self.yconrevs[0].der(self.yconrevs[0].rev(mu)), (-1, 1))
+        if convert:
+            for i in range(self.nx):
+                cr = self.xconrevs[i]
+                if hasattr(cr, "der"):  # (the whole column at once: the sweeps this serves hold 1e5 .. 1e7 points)
+                    g[:, i] *= np.asarray(cr.der(x[:, i]), dtype=np.float64).reshape(-1)
+                else:
+                    g[:, i] *= np.array([_con_and_der(cr, v)[1] for v in x[:, i]])
+        return np.reshape(y, (-1, 1)), g
+
+    def active_subspace(self, nsamps=10000, seed=None, x=None, space="converted", revert=False):
+        """The active subspace of the posterior mean (sensitivity.active_subspace_from_gradients) from its gradients at a
+        Latin-hypercube sample of the input priors, or at the rows of ``x`` (original inputs).  ``space="converted"`` (default):
+        gradients w.r.t. the converted inputs, which are comparable across dimensions; ``"original"``: w.r.t. x.  ``revert``: of the
+        plug-in surrogate in the original output space instead of the converted-space mean.  Returns a dict: eigenvalues,
+        eigenvectors (columns), C, dgsm (diag C), x, grads."""
+        from . import sensitivity
+
+        if space not in ("converted", "original"):
+            raise ValueError("space must be 'converted' or 'original'")
+        x = latin_sample(self.priors, nsamps, seed) if x is None else np.asarray(x, dtype=np.float64)
+        if space == "converted":
+            xc, _ = self._converted_x(x, True)
+            _, g = self.predict_mean(xc, convert=False, revert=revert, return_grad=True)
+        else:
+            _, g = self.predict_mean(x, convert=True, revert=revert, return_grad=True)
+        lam, V, C, dgsm = sensitivity.active_subspace_from_gradients(g)
+        return {"eigenvalues": lam, "eigenvectors": V, "C": C, "dgsm": dgsm, "x": x, "grads": g}
+
+    def sobol_indices(self, nsamps=10000, seed=None, revert=True):
+        """First-order (Saltelli 2010) and total (Jansen) Sobol indices of the posterior mean over the input priors: two
+        Latin-hypercube base samples of ``nsamps`` points from SeedSequence(seed).spawn(2), the (nx + 2) nsamps points of
+        sensitivity.saltelli_design through ``predict_mean``.  Returns a dict: first, total, mean, var."""
+        from . import sensitivity
+
+        sa, sb = np.random.SeedSequence(seed).spawn(2)
+        A = latin_sample(self.priors, nsamps, np.random.default_rng(sa))
+        B = latin_sample(self.priors, nsamps, np.random.default_rng(sb))
+        f = self.predict_mean(sensitivity.saltelli_design(A, B), revert=revert)[:, 0]
+        first, total, mean, var = sensitivity.sobol_from_evaluations(*sensitivity.split_saltelli(f, self.nx))
+        return {"first": first, "total": total, "mean": mean, "var": var}
 
     def test_plots(self, revert=True, yplots=True, xplots=True, logscale=False, iwgp=False, cwgp=False, method="none",
                    errorbars=True, saveyfig=None, xlab=None, ylab=None, returndat=False):

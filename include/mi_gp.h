@@ -571,6 +571,36 @@ MI_GP_API int mi_gp_set_option(mi_gp_handle* h, int what, int value);
 /* current value of a knob, the library's own defaults included; 40 (read-only): 1 once the handle has switched its cross-stream
  * edges to events by itself (option 26) */
 MI_GP_API int mi_gp_get_option(mi_gp_handle* h, int what, int* value);
+/* Option 53 (not a tuning knob) the MEAN SWEEP of mi_gp_predict_grad: 0 (default) today's call, bit for bit and launch for
+ *      launch; 1 the call becomes the matrix-free sweep of the posterior mean and its input gradient,
+ *          mu(x*) = sum_j k(x*, x_j) alpha_j,      d mu / d x*_m = sum_j alpha_j sum_c coef_c kv_c k_c'(r2_c) 2 (x*_m - x_jm) / l_cm^2
+ *      with alpha = K^-1 y: O(n d) per point, no work rows and no m x n matrix, where every other prediction route pays O(n^2) per
+ *      point for a variance -- the route of Saltelli designs, of E[grad mu grad mu^T] over the input priors and of mean-only
+ *      samples of 1e5 .. 1e7 points.  Under 1: Xnew_dev is m x d with m >= 1 and no other limit on m; mean_dev receives m doubles or
+ *      is NULL, dmean_dev receives m x d doubles or is NULL, at least one of them is given; work_dev, ldw, var_dev, dvar_dev and
+ *      pred_noise are ignored -- NULL is allowed for them, nothing is written there.  Xnew_dev and the outputs are device-visible
+ *      addresses as for mi_gp_predict (pinned host memory allowed).  Preconditions, those of today's call: a successful
+ *      mi_gp_factor or mi_gp_append, Z_dev / W_dev bound, option 50 = 0 and option 51 = 1 (their texts); further d <= 128 (the
+ *      (nkern + 1) * d LDS rule of the scalar kernel does not apply).  Every refusal returns -1 before any HIP call, with a text that
+ *      names option 53, and changes no state.  The call makes U = L^-T and alpha resident (make_u_resident, exactly as today's call)
+ *      and changes nothing else; the handle owns a scratch -- (capacity + 16) rows of the padded d doubles, the training points
+ *      staged for the kernel by every call, and the partial sums of one pass of 16384 query points (4096 for d > 32: 16 parts of
+ *      1 + d doubles per point, and for d > 32 the pass's points themselves) -- allocated by the first sweep, dropped by
+ *      mi_gp_reserve, freed by mi_gp_destroy; nothing in it is kept between calls and no buffer grows with m.  It
+ *      returns with the stream synchronised.
+ *      Arithmetic: per component r2_c = sum_m ((x*_m - x_jm) (1 / l_cm))^2, the direct form of the gradient kernels and not the
+ *      assembly's expansion -2 x.x' + |x|^2 + |x'|^2, whose residue of a few eps |x / l|^2 Exponential's dk/dr2 ~ 1 / r amplifies
+ *      near r = 0; value and derivative per component and the + / * fold as in mi_gp_predict_grad's kernel; the differences
+ *      (x*_m - x_jm) are accumulated, never x* sum C - sum C x_j, which cancels for short length scales; a coincident training
+ *      point contributes 0 to the gradient.  One thread owns one query point and walks training points in index order.
+ *      The training range is split over workgroups by a rule of n alone: 16 parts [y q, min((y + 1) q, n)), q = ceil(n / 16); a
+ *      workgroup sums one part for 64 points, and a kernel of the library adds a point's 16 partial sums in part order.  Every
+ *      sum runs in a fixed order, the same call in the same state returns the same bits, and a point's results do not depend
+ *      on m, on its position in Xnew_dev or on the other points.
+ *      Values outside 0..1 return -1, and so does 1 in a build without the sweep (the host-only schedule-trace program; the
+ *      text says "not part of this build").  Setting it changes no resident state; mi_gp_get_option(53) reads it back.
+ *      Out of scope: the sweep under a trend or several outputs; a batched (one theta per member) and a sharded form; variances;
+ *      d > 128; second derivatives. */
 
 /* profiling: level 0 none, 1 per-phase HIP events, 2 additionally per-GEMM-launch HIP events */
 MI_GP_API int mi_gp_set_profiling(mi_gp_handle* h, int level);
