@@ -619,6 +619,7 @@ class MiGP:
                 return r
             self.n += kc
             self.np_ = self._padded(self.n)
+            self.__dict__["_path_serial"] = self._path_serial + 1  # (draw_paths: the weights of a PathDraw belong to the old n)
             self._views()
             self._gx_t = None  # (sized for n)
             self._drop_batch()
@@ -927,6 +928,57 @@ class MiGP:
         finally:
             self.set_option(53, 0)
         return (mean, dmean) if grad else mean
+
+    # ---------------------------------------------------------------- posterior sample paths (options 54 / 55)
+    # The factorisation serial: every assignment of _factored_ok -- factor(), update_data(), set_diag() and every call that
+    # ends the factored state make one -- and every append() advance it.  A PathDraw remembers the serial it was conditioned on.
+    @property
+    def _factored_ok(self):
+        return self.__dict__.get("_factored_flag", False)
+
+    @_factored_ok.setter
+    def _factored_ok(self, value):
+        self.__dict__["_factored_flag"] = bool(value)
+        self.__dict__["_path_serial"] = self.__dict__.get("_path_serial", 0) + 1
+
+    @property
+    def _path_serial(self):
+        return self.__dict__.get("_path_serial", 0)
+
+    def draw_paths(self, theta, npaths, nfeatures=4096, seed=None):
+        """``npaths`` (1..128) posterior sample paths at theta by pathwise conditioning (paths.py; options 54 / 55 of
+        mi_gp_set_option): a prior draw from ``nfeatures`` random Fourier features (a multiple of 16 in 16..65536) plus the
+        update K(., X) K_y^-1 (y - prior(X) - eps), conditioned on the device against the resident factorisation.  Returns a
+        paths.PathDraw, whose ``evaluate`` sweeps the draws matrix-free over any number of points, with their input gradients.
+        The draws are of the latent f (add observation noise on the host).  Host draws come from
+        np.random.Generator(np.random.Philox(seed)) in the order of paths.draw_block_parts: the same seed gives the same block;
+        ``seed`` None takes one from the OS.  d <= 32.  Option 54 is 0 again afterwards."""
+        from . import paths
+
+        self._no_trend("draw_paths")
+        self._no_outputs("draw_paths")
+        if self.Z_t is None:
+            raise RuntimeError("this MiGP was created with need_grad=False")
+        if self.d > paths.MAX_D:
+            raise ValueError(f"draw_paths needs d <= {paths.MAX_D}, got {self.d}")
+        S, F = paths.check_counts(npaths, nfeatures)
+        self._ensure_factored(theta)
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(2, dtype=np.uint64)[0])
+        diag = self._diag_t.cpu().numpy() if getattr(self, "_diag_t", None) is not None else None
+        omega, b, W, E, _ = paths.draw_block_parts(self.kerns, self.ops, self._factored_theta, self.d, self.n, S, F, seed, diag)
+        ldw = paths.block_ldw(S)
+        with torch.cuda.device(self.dev):
+            block = torch.from_numpy(paths.pack_block(omega, b, W, E, ldw)).to(self.dev)
+            torch.cuda.synchronize(self.dev)
+            self.set_option(55, F)
+            self.set_option(54, S)
+            try:  # the conditioning call: m = 0, pred_noise read as `condition`
+                self._check(self.lib.mi_gp_predict_grad(self.h, None, 0, block.data_ptr(), ldw, None, None, 1, None, None),
+                            "mi_gp_predict_grad")
+            finally:
+                self.set_option(54, 0)
+        return paths.PathDraw(self, block, S, F, ldw, seed, self._path_serial)
 
     # ---------------------------------------------------------------- joint conditional and posterior draws
     # One call per request, nothing chunked: device memory bounds M.  predict_cov holds Sigma (mp^2 doubles, mp = M rounded up

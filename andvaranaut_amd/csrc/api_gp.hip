@@ -65,7 +65,7 @@ static void release_handle(mi_gp_handle* h) {
   free_scratch(h->one);
   free_scratch(h->batch);
   (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
-  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk, &h->multi_blk, &h->sweep_blk}) (void)hipFree(b->p);
+  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk, &h->multi_blk, &h->sweep_blk, &h->path_blk}) (void)hipFree(b->p);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -152,6 +152,7 @@ static void special_defaults(mi_gp_handle* h) {
   h->spin_us = 2000;
   h->cv_block = 1;
   h->nout = 1;
+  h->nfeat = 1024;
 }
 
 // The options with behaviour beyond a clamp; `set` (or nullptr) is the new value, `get` (or nullptr) receives the current one.
@@ -305,6 +306,32 @@ static int special_option(mi_gp_handle* h, int what, const int* set, int* get) {
         h->sweep = *set;
       } else {
         *get = h->sweep;
+      }
+      return 1;
+    case 54:  // the number of sample PATHS mi_gp_predict_grad sweeps (no resident state changes with it)
+      if (set) {
+        if (*set < 0 || *set > 128) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 54 is 0 (no paths) or a number of sample paths of 1 to 128, got %d", *set);
+          return -1;
+        }
+        if (*set >= 1 && !path_sweep) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the path sweep (option 54 >= 1) is not part of this build");
+          return -1;
+        }
+        h->npaths = *set;
+      } else {
+        *get = h->npaths;
+      }
+      return 1;
+    case 55:  // the number of random Fourier features of a path (no resident state changes with it)
+      if (set) {
+        if (*set < 16 || *set > 65536 || *set % 16 != 0) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 55 is a number of features, a multiple of 16 in 16..65536, got %d", *set);
+          return -1;
+        }
+        h->nfeat = *set;
+      } else {
+        *get = h->nfeat;
       }
       return 1;
   }
@@ -1029,6 +1056,14 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
                                   double* mean_dev, double* var_dev, int pred_noise, double* dmean_dev,
                                   double* dvar_dev) {
   if (!h) return -1;
+  if (h->npaths) {  // option 54 = S >= 1: the path sweep, work_dev the caller's path block and pred_noise `condition`
+    if (h->sweep) {
+      snprintf(h->err, sizeof(h->err), "mi_gp_predict_grad: option 53 = 1 (the mean sweep) and option 54 = %d (the path sweep) are both "
+               "set: set one of them to 0", h->npaths);
+      return -1;
+    }
+    return path_sweep(h, Xnew_dev, m, work_dev, ldw, mean_dev, pred_noise, dmean_dev);
+  }
   if (h->sweep) return mean_sweep(h, Xnew_dev, m, mean_dev, dmean_dev);  // option 53 = 1: another call behind the same entry point
   if (!dmean_dev || !dvar_dev) return -1;
   if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_grad");
@@ -1094,7 +1129,8 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   h->cap = capacity;
   // the capacity-sized blocks: the objectives' hold nothing between calls and are dropped (their next use re-sizes them), the
   // trend's keeps the conditional's G^T, beta^ and b~
-  for (CapBlock* b : {&h->loo, &h->cv, &h->sweep_blk}) (void)resize_block(*b, 0, 0);
+  for (CapBlock* b : {&h->loo, &h->cv, &h->sweep_blk, &h->path_blk}) (void)resize_block(*b, 0, 0);
+  h->path_len = 0;
   if (h->trend_blk.p && trend_reserve) HCK(trend_reserve(h, capacity), "mi_gp_reserve");
   if (h->multi_blk.p && multi_reserve) HCK(multi_reserve(h, capacity), "mi_gp_reserve");  // (keeps the conditional's B^T)
   return 0;

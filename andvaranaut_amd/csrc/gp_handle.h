@@ -144,6 +144,13 @@ struct mi_gp_handle {
                            // the matrix-free posterior mean and its input gradient (mean_sweep(), api_sweep.hip)
   CapBlock sweep_blk;      // its scratch: the training points staged for the kernel and the partial sums of one pass of query
                            // points (sweep_f64.hip: sweep_scratch_len; allocated by the first sweep, holds nothing between calls)
+  int npaths;              // option 54: 0 (default) mi_gp_predict_grad is what option 53 says; S = 1..128: it is the PATH SWEEP of S
+                           // posterior sample paths over the caller's path block (path_sweep(), api_paths.hip)
+  int nfeat;               // option 55: F, the random Fourier features of a path's prior draw (a multiple of 16 in 16..65536; read
+                           // only under option 54 >= 1)
+  CapBlock path_blk;       // the path sweep's scratch: the points, frequencies and weights staged for the kernel, the partial sums of
+  size_t path_len;         // one pass and the conditioning's two 128-row blocks (paths_f64.hip: path_scratch_len; path_len doubles,
+                           // grown by a call that needs more; holds nothing between calls)
   char err[256];
 };
 
@@ -343,6 +350,11 @@ inline bool refuse_outcov(mi_gp_handle* h, const char* entry) {
 // api_sweep.hip: mi_gp_predict_grad under option 53 = 1 (include/mi_gp.h has the contract).  Weak like loo_objective: without the
 // file option 53 = 1 is refused.  0 or a C-ABI error code; every refusal comes before any HIP call
 int mean_sweep(mi_gp_handle* h, const double* Xnew_dev, int m, double* mean_dev, double* dmean_dev) __attribute__((weak));
+
+// api_paths.hip: mi_gp_predict_grad under option 54 = S >= 1 (include/mi_gp.h has the contract).  Weak like mean_sweep: without
+// the file option 54 >= 1 is refused.  0 or a C-ABI error code; every refusal comes before any HIP call
+int path_sweep(mi_gp_handle* h, const double* Xnew_dev, int m, double* block_dev, long ldw, double* mean_dev, int condition,
+               double* dmean_dev) __attribute__((weak));
 
 // api_gp.hip
 hipError_t trsm_rec(mi_gp_handle* h, const Eval& E, double* Bw, long ldw, int mp, int c0, int w);  // X L^T = B in place

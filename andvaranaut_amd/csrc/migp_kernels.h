@@ -410,6 +410,40 @@ size_t sweep_scratch_len(int cap, int d);
 hipError_t launch_mean_sweep(const KernSpec& spec, const double* theta, const double* X, int n, const double* xstar, int m,
                              const double* alpha, double* scratch, double* mean, double* dmean, hipStream_t stream);
 
+// ---------------------------------------------------------------- paths_f64.hip (option 54: the path sweep, api_paths.hip)
+constexpr int PATH_MAX_D = 32;      // input dimensions the path sweep's register windows cover (4, 16, 32; no wide form)
+constexpr int PATH_MAX_S = 128;     // paths of one block; the row length of the staged weights
+constexpr int PATH_PARTS_N = 16;    // parts of the training range, [y q, min((y + 1) q, n)) with q = ceil(n / 16): a rule of n alone
+constexpr int PATH_PARTS_F = 16;    // parts of the feature range, [y F / 16, (y + 1) F / 16): a rule of F alone (F is a multiple of 16)
+constexpr int PATH_CHUNK = 4096;    // query points of one pass of 128 columns (a pass of fewer columns: up to 8 times as many)
+constexpr int PATH_TILE_VALUE = 16; // paths a thread carries without the gradient
+int path_window(int d);             // the register window that runs for d dimensions: 4, 16 or 32
+int path_tile(int d, bool grad);    // T, the paths a thread carries: PATH_TILE_VALUE, with the gradient 8 / 2 / 1 for the window 4 / 16 / 32
+// The handle-owned scratch for up to cap training points and F features (ldr = cap rounded up to 128, the row stride of R1 / R2)
+struct PathScratch {
+  double *Xp, *il, *il2;  // the training points, 1 / l and 2 / l^2 padded with zeros to the window (sweep_f64.hip's staging)
+  double* Om;             // [F][window] the frequencies, zeros from d on
+  double *Wp, *Vp;        // [F][128], [cap][128] the weights; columns S .. S rounded up to 16 hold zeros, the rest is never read
+  double* part;           // the partial sums of one pass of PATH_CHUNK points and one group of path tiles
+  double *R1, *R2;        // [128][ldr] the conditioning's staged blocks R^T and R^T U
+  long ldr;
+};
+size_t path_scratch_len(int cap, int d, int F);
+PathScratch path_scratch(double* base, int cap, int d, int F);
+// stages X, 1 / l, 2 / l^2, Omega and W (V: launch_path_stage_v, behind the conditioning); W and V rows are ldw apart, S columns used
+hipError_t launch_path_stage(const KernSpec& spec, const double* theta, const double* X, int n, const double* Om, const double* W, long ldw,
+                             int F, int S, const PathScratch& t, hipStream_t stream);
+hipError_t launch_path_stage_v(const double* V, long ldw, int n, int S, const PathScratch& t, hipStream_t stream);
+// mean[s * ldo + p] = sum_i W[i,s] cos(om_i . x*_p + b_i) (+ sum_j k(x*_p, x_j) V[j,s] unless features_only) for s < S, p < m, and
+// dmean[(s * ldo + p) * d + k] its derivative; each optional (not both null).  One thread per point, part and path tile; a
+// point's sums run in index order, the parts' sums are added in part order.  bph: the F phases.
+hipError_t launch_path_sweep(const KernSpec& spec, const double* theta, int n, int F, int S, const double* bph, const PathScratch& t,
+                             const double* xstar, int m, long ldo, double* mean, double* dmean, bool features_only, hipStream_t stream);
+// R1[s * ldr + j] = y[j] - R1[s * ldr + j] - V[j * ldw + s] for s < S, j < n; zeros in the rows from S on and the columns from n on
+hipError_t launch_path_residual(const double* y, const double* V, long ldw, int n, int S, const PathScratch& t, hipStream_t stream);
+// V[j * ldw + s] = R1[s * ldr + j] for s < S, j < n
+hipError_t launch_path_scatter(double* V, long ldw, int n, int S, const PathScratch& t, hipStream_t stream);
+
 // ---------------------------------------------------------------- api_blocks.hip
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)
 void set_global_error(const char* text);

@@ -45,6 +45,48 @@ def load_object(fname):
         return cloudpickle.load(f)
 
 
+class PosteriorPaths:
+    """What GPMCMC.sample_paths returns: npaths posterior function draws (a paths.PathDraw of the converted-space GP) behind
+    predict_mean's conversions."""
+
+    def __init__(self, model, draw):
+        self.model, self.draw = model, draw
+        self.npaths = draw.npaths
+
+    def __call__(self, x, convert=True, revert=True, return_grad=False):
+        """The draws at x (M, nx): values (npaths, M), and with ``return_grad`` (values, gradients (npaths, M, nx)) w.r.t. x as
+        passed.  The conversions are predict_mean's, applied per draw, point by point: ``revert=True`` yconrevs[0].rev(f) + mean
+        function, the chain rule through rev' and con' for the gradient; a non-zero mean function with ``return_grad`` raises."""
+        from .consumers import _con_and_der
+
+        g = self.model
+        if return_grad and g.mean != g.zero_mean:
+            raise ValueError("sample_paths(...)(return_grad=True) has no form under a non-zero mean function")
+        xarg, x = g._converted_x(np.asarray(x, dtype=np.float64), convert)
+        if return_grad:
+            f, df = self.draw.evaluate(xarg, grad=True)
+        else:
+            f = self.draw.evaluate(xarg)
+        cr0 = g.yconrevs[0]
+        y = np.stack([cr0.rev(fs) for fs in f]) + g._mean_at(x) if revert else f
+        if not return_grad:
+            return y
+        if revert:
+            for s in range(f.shape[0]):
+                df[s] /= np.reshape(cr0.der(cr0.rev(f[s])), (-1, 1))
+        if convert:
+            for i in range(g.nx):
+                cr = g.xconrevs[i]
+                if hasattr(cr, "der"):
+                    df[:, :, i] *= np.asarray(cr.der(x[:, i]), dtype=np.float64).reshape(1, -1)
+                else:
+                    df[:, :, i] *= np.array([_con_and_der(cr, v)[1] for v in x[:, i]])[None, :]
+        return y, df
+
+    def close(self):
+        self.draw.close()
+
+
 class GPMCMC(ConsumersMixin):
     def __init__(self, xconrevs=None, yconrevs=None, kernel="RBF", noise=True, mean=0, nx=None, ny=None,
                  priors=None, target=None, parallel=False, nproc=1, constraints=None, rundir=None, verbose=True,
@@ -349,12 +391,15 @@ class GPMCMC(ConsumersMixin):
             print(f"Log predictive density is: {out['lpd']:0.5e}")
         return out
 
-    def y_dist(self, mode="hist_kde", nsamps=None, return_data=False, surrogate=True, seed=None, mean_only=False):
+    def y_dist(self, mode="hist_kde", nsamps=None, return_data=False, surrogate=True, seed=None, mean_only=False, npaths=0,
+               nfeatures=4096, path_seed=None):
         """Uncertainty propagation through the surrogate (gpmcmc.py:140-151; tutorial.ipynb cell 34): a Latin-hypercube sample of the
         input priors is pushed through ``predict`` (one device sweep via U = L^-T for large ``nsamps``), or with ``mean_only=True``
         through ``predict_mean``, the matrix-free sweep (samples large enough for a tail).  The density plots of
         LHC.__y_dist (lhc.py:100-110) are outside this backend's scope: ``mode`` is validated as there and otherwise ignored.
-        ``surrogate=False``: the underlying data set.  ``return_data=True`` returns (x, y) as the reference does."""
+        ``surrogate=False``: the underlying data set.  ``return_data=True`` returns (x, y) as the reference does.
+        ``npaths > 0``: the same sample goes through one ``sample_paths`` draw instead, and y is (npaths, nsamps): one output
+        distribution per posterior function draw, whose spread is the surrogate's uncertainty about the distribution."""
         modes = ["hist", "kde", "ecdf", "hist_kde"]
         if mode not in modes:
             raise Exception(f"Error: selected mode must be one of {modes}")
@@ -363,7 +408,10 @@ class GPMCMC(ConsumersMixin):
         if not surrogate:
             return (self.x, self.y) if return_data else None
         xsamps = latin_sample(self.priors, nsamps, seed)
-        ypreds = self.predict_mean(xsamps) if mean_only else self.predict(xsamps)
+        if npaths > 0:
+            ypreds = self.sample_paths(npaths, nfeatures, path_seed)(xsamps)
+        else:
+            ypreds = self.predict_mean(xsamps) if mean_only else self.predict(xsamps)
         if return_data:
             return xsamps, ypreds
 
@@ -411,12 +459,29 @@ class GPMCMC(ConsumersMixin):
                     g[:, i] *= np.array([_con_and_der(cr, v)[1] for v in x[:, i]])
         return np.reshape(y, (-1, 1)), g
 
-    def active_subspace(self, nsamps=10000, seed=None, x=None, space="converted", revert=False):
+    def sample_paths(self, npaths=16, nfeatures=4096, seed=None, jitter=1e-6):
+        """``npaths`` (1..128) posterior function draws of the fitted GP by pathwise conditioning (MiGP.draw_paths: a prior draw
+        from ``nfeatures`` random Fourier features plus a kernel-weighted update; O((n + nfeatures) d) per point and draw, no
+        M x M matrix).  Returns a PosteriorPaths: call it like ``predict_mean`` -- ``paths(x, convert=True, revert=True,
+        return_grad=False)`` -- for values (npaths, M), and with ``return_grad`` the gradients (npaths, M, nx) w.r.t. x as passed.
+        Each draw is one consistent function over any number of calls; it is of the latent f (no observation noise).  The
+        object goes stale (RuntimeError) once the GP is factorised again at other hyper-parameters or given other data."""
+        self._no_trend("sample_paths")
+        self._no_all_outputs("sample_paths")
+        if self._ensure_gp() is None or self.hypers is None:
+            raise Exception("Error: fit the GP before sampling paths")
+        theta = self._theta_from_hypers(self.hypers, jitter)
+        return PosteriorPaths(self, self.gp.draw_paths(theta, npaths, nfeatures, seed))
+
+    def active_subspace(self, nsamps=10000, seed=None, x=None, space="converted", revert=False, npaths=0, nfeatures=4096,
+                        path_seed=None):
         """The active subspace of the posterior mean (sensitivity.active_subspace_from_gradients) from its gradients at a
         Latin-hypercube sample of the input priors, or at the rows of ``x`` (original inputs).  ``space="converted"`` (default):
         gradients w.r.t. the converted inputs, which are comparable across dimensions; ``"original"``: w.r.t. x.  ``revert``: of the
         plug-in surrogate in the original output space instead of the converted-space mean.  Returns a dict: eigenvalues,
-        eigenvectors (columns), C, dgsm (diag C), x, grads."""
+        eigenvectors (columns), C, dgsm (diag C), x, grads.  ``npaths > 0``: the same points also go through one
+        ``sample_paths`` draw, and the dict carries the per-draw estimates eigenvalues_paths (npaths, nx) and dgsm_paths
+        (npaths, nx) beside the mean-based ones."""
         from . import sensitivity
 
         if space not in ("converted", "original"):
@@ -428,20 +493,41 @@ class GPMCMC(ConsumersMixin):
         else:
             _, g = self.predict_mean(x, convert=True, revert=revert, return_grad=True)
         lam, V, C, dgsm = sensitivity.active_subspace_from_gradients(g)
-        return {"eigenvalues": lam, "eigenvectors": V, "C": C, "dgsm": dgsm, "x": x, "grads": g}
+        out = {"eigenvalues": lam, "eigenvectors": V, "C": C, "dgsm": dgsm, "x": x, "grads": g}
+        if npaths > 0:
+            draws = self.sample_paths(npaths, nfeatures, path_seed)
+            if space == "converted":
+                _, gp_ = draws(xc, convert=False, revert=revert, return_grad=True)
+            else:
+                _, gp_ = draws(x, convert=True, revert=revert, return_grad=True)
+            per = [sensitivity.active_subspace_from_gradients(gs) for gs in gp_]
+            out["eigenvalues_paths"] = np.array([r[0] for r in per])
+            out["dgsm_paths"] = np.array([r[3] for r in per])
+        return out
 
-    def sobol_indices(self, nsamps=10000, seed=None, revert=True):
+    def sobol_indices(self, nsamps=10000, seed=None, revert=True, npaths=0, nfeatures=4096, path_seed=None):
         """First-order (Saltelli 2010) and total (Jansen) Sobol indices of the posterior mean over the input priors: two
         Latin-hypercube base samples of ``nsamps`` points from SeedSequence(seed).spawn(2), the (nx + 2) nsamps points of
-        sensitivity.saltelli_design through ``predict_mean``.  Returns a dict: first, total, mean, var."""
+        sensitivity.saltelli_design through ``predict_mean``.  Returns a dict: first, total, mean, var.  ``npaths > 0``: the same
+        design also goes through one ``sample_paths`` draw, and the dict carries the per-draw estimates first_paths (npaths, nx),
+        total_paths, mean_paths and var_paths (npaths,) beside the mean-based ones: their spread is the surrogate's uncertainty."""
         from . import sensitivity
 
         sa, sb = np.random.SeedSequence(seed).spawn(2)
         A = latin_sample(self.priors, nsamps, np.random.default_rng(sa))
         B = latin_sample(self.priors, nsamps, np.random.default_rng(sb))
-        f = self.predict_mean(sensitivity.saltelli_design(A, B), revert=revert)[:, 0]
+        design = sensitivity.saltelli_design(A, B)
+        f = self.predict_mean(design, revert=revert)[:, 0]
         first, total, mean, var = sensitivity.sobol_from_evaluations(*sensitivity.split_saltelli(f, self.nx))
-        return {"first": first, "total": total, "mean": mean, "var": var}
+        out = {"first": first, "total": total, "mean": mean, "var": var}
+        if npaths > 0:
+            fp = self.sample_paths(npaths, nfeatures, path_seed)(design, revert=revert)
+            per = [sensitivity.sobol_from_evaluations(*sensitivity.split_saltelli(fs, self.nx)) for fs in fp]
+            out["first_paths"] = np.array([r[0] for r in per])
+            out["total_paths"] = np.array([r[1] for r in per])
+            out["mean_paths"] = np.array([r[2] for r in per])
+            out["var_paths"] = np.array([r[3] for r in per])
+        return out
 
     def test_plots(self, revert=True, yplots=True, xplots=True, logscale=False, iwgp=False, cwgp=False, method="none",
                    errorbars=True, saveyfig=None, xlab=None, ylab=None, returndat=False):

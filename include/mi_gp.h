@@ -601,6 +601,57 @@ MI_GP_API int mi_gp_get_option(mi_gp_handle* h, int what, int* value);
  *      text says "not part of this build").  Setting it changes no resident state; mi_gp_get_option(53) reads it back.
  *      Out of scope: the sweep under a trend or several outputs; a batched (one theta per member) and a sharded form; variances;
  *      d > 128; second derivatives. */
+/* Option 54 (not a tuning knob) the PATH SWEEP of mi_gp_predict_grad, S posterior sample paths by pathwise conditioning (Wilson
+ *      et al. 2020, "Efficiently sampling functions from Gaussian process posteriors"): 0 (default) the call is what option 53
+ *      says, bit for bit and launch for launch; S = 1..128 the call evaluates -- and on request first conditions -- S function
+ *      draws
+ *          f_s(x*) = sum_i W[i,s] cos(om_i . x* + b_i) + sum_j k(x*, x_j) V[j,s],     V[:,s] = K_y^-1 (y - Phi(X) W[:,s] - E[:,s])
+ *      -- a prior draw from F random Fourier features of the kernel's spectral measure (the only approximation: it vanishes at
+ *      the data) plus a kernel-weighted update, one weight per training point.  A draw is a consistent function: any number of
+ *      points, in any number of calls, with its input gradient, at O((n + F) d) per point and path, without an M x M matrix.
+ *      Option 55 is F, the number of features: a multiple of 16 in 16..65536, default 1024, read only while option 54 >= 1.
+ *      Under option 54 = S: work_dev is the caller's PATH BLOCK in device memory and ldw its row stride, even and >= S.  With
+ *      d the input dimension and n the current number of points, the block holds, in doubles from its start,
+ *          Omega at 0                      F x d, row-major: the frequencies om_i
+ *          b     at F * d                  F: the phases b_i
+ *          W     at F * d + F              F rows, ldw apart: the feature weights
+ *          V     at F * d + F + F * ldw    n rows, ldw apart: the update weights (on entry to a conditioning call: the noise draw E)
+ *      -- F * d + F + (F + n) * ldw doubles.  Columns s < S of W and V belong to path s; the padding columns are never read or
+ *      written.  pred_noise is read as `condition`; var_dev and dvar_dev are ignored (NULL allowed, nothing is written there).
+ *      condition = 1: the V rows hold E ~ N(0, K_y - K_f) on entry and the call replaces them by V = K_y^-1 (y - Phi(X) W - E) on
+ *      the handle's stream: Phi(X) W from the feature half of the sweep kernel at the training points, the residual as a 128-row
+ *      block R^T (rows from S on and columns from n on zero), R^T U and (R^T U) U^T on the GEMM against the resident U = L^-T
+ *      (mi_gp_predict_u's and mi_gp_append's launches), and the rows written back as columns.  m = 0 is allowed in this form --
+ *      conditioning only, Xnew_dev and the outputs NULL; m >= 1 goes on to the evaluation.  condition = 0: the block is used as
+ *      it is (any V and W), and m >= 1.  The evaluation writes, for mean_dev, dmean_dev or both (at least one given when m >= 1),
+ *          mean_dev[s * m + p]            = f_s(x*_p)                                    (S * m doubles, path-major as option 51's)
+ *          dmean_dev[(s * m + p) * d + k] = d f_s / d x*_pk                              (S * m * d doubles)
+ *      with no upper limit on m.  Preconditions, option 53's: a successful mi_gp_factor or mi_gp_append, Z_dev / W_dev bound,
+ *      option 50 = 0 and option 51 = 1 (their texts); further d <= 32 in this version (the text names option 54 and the limit).
+ *      ldw odd or < S, a NULL block, both outputs NULL with m >= 1, m = 0 with condition = 0 and m < 0 are refused, and so is the
+ *      call while options 53 = 1 and 54 >= 1 are both set.  Every refusal returns -1 before any HIP call and changes nothing,
+ *      the block included.  Apart from making U and alpha resident (make_u_resident, as today's call) no handle state changes:
+ *      mi_gp_alpha, the mean sweep and mi_gp_predict_grad return the bits they returned before.  The handle owns a scratch -- the
+ *      points, frequencies and weights staged per call in padded rows, the partial sums of one pass (32 parts of 4096 points and
+ *      128 columns) and the conditioning's two 128-row blocks -- allocated by the first call, re-sized when F grows, dropped by
+ *      mi_gp_reserve, freed by mi_gp_destroy; it holds nothing between calls and does not grow with m.  The call returns with the
+ *      stream synchronised.  THE LIBRARY CANNOT KNOW that a block was conditioned on another factorisation (other theta, data or
+ *      n): the caller keeps a block with the factorisation that made it.
+ *      Arithmetic: option 53's for the kernel sum -- r2 in the direct form, value and derivative per component and the + / * fold
+ *      as in the gradient kernels, the differences (x*_m - x_jm) accumulated, a coincident training point contributing 0 to the
+ *      gradient; per feature the phase b_i + sum_u om_iu x*_u in index order, one cos and with the gradient one sin, both with
+ *      an exact reduction of arguments of any size (Matern and Exponential frequencies are heavy-tailed).  One thread owns one
+ *      query point and T paths; the pair's kernel value is formed once and used T times.  The training range is cut into 16
+ *      parts [y q, min((y + 1) q, n)), q = ceil(n / 16), the feature range into 16 parts of F / 16: rules of n alone and of F
+ *      alone; a kernel of the library adds the 32 partial sums in part order, training parts first.  Every sum runs in a fixed
+ *      order of fused multiply-adds: the bits of path s at point p depend on the point, column s of V and W, Omega, b and the
+ *      resident state and on nothing else -- not on m, the position of p, S, the other columns, whether the gradient was asked
+ *      for, or a repetition.
+ *      Values outside 0..128 (option 54) and outside the multiples of 16 in 16..65536 (option 55) return -1 with a text that
+ *      names the option, and so does option 54 >= 1 in a build without the path sweep (the host-only schedule-trace program; the
+ *      text says "not part of this build").  Setting either changes no resident state; mi_gp_get_option reads them back.
+ *      Out of scope: d > 32; a trend or several outputs; batched and sharded forms; draws of noisy observations (add the noise
+ *      on the host); variances. */
 
 /* profiling: level 0 none, 1 per-phase HIP events, 2 additionally per-GEMM-launch HIP events */
 MI_GP_API int mi_gp_set_profiling(mi_gp_handle* h, int level);
