@@ -5,6 +5,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmi_gp.so")
+SPARSE_LIB_PATH = os.path.join(_HERE, "libmi_gp_sparse.so")  # the sparse inducing-point bound (include/mi_gp_sparse.h)
 
 MAX_KERN = 8
 KERNEL_IDS = {"RBF": 0, "Matern52": 1, "Matern32": 2, "Exponential": 3, "RatQuad": 4}
@@ -65,6 +66,19 @@ class MiGpShardConfig(ctypes.Structure):
         ("theta_dev", ctypes.c_void_p),
         ("info_dev", ctypes.c_void_p),
         ("out_dev", ctypes.c_void_p),
+    ]
+
+
+class MiGpSparseConfig(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_int),
+        ("m", ctypes.c_int),
+        ("d", ctypes.c_int),
+        ("nkern", ctypes.c_int),
+        ("kernel_ids", ctypes.c_int * MAX_KERN),
+        ("ops", ctypes.c_int * MAX_KERN),
+        ("device", ctypes.c_int),
+        ("chunk", ctypes.c_int),
     ]
 
 
@@ -216,4 +230,46 @@ EXPORTS = [
     "mi_gp_shard_piece_times",
     "mi_gp_shard_chain_stream",
     "mi_gp_shard_last_error",
+]
+
+
+_sparse = None
+
+
+def load_sparse():
+    """Load libmi_gp_sparse.so and declare every entry point of include/mi_gp_sparse.h."""
+    global _sparse
+    if _sparse is not None:
+        return _sparse
+    if not os.path.exists(SPARSE_LIB_PATH):
+        raise RuntimeError(f"{SPARSE_LIB_PATH} not found: build it with `make -C andvaranaut_amd/csrc` (there is no CPU fallback)")
+    lib = ctypes.CDLL(SPARSE_LIB_PATH)
+    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
+    dp = ctypes.POINTER(ctypes.c_double)
+    lib.mi_gp_sparse_create.argtypes = [ctypes.POINTER(MiGpSparseConfig), ctypes.POINTER(vp)]
+    lib.mi_gp_sparse_destroy.argtypes = [vp]
+    lib.mi_gp_sparse_last_error.argtypes = [vp]
+    lib.mi_gp_sparse_last_error.restype = ctypes.c_char_p
+    lib.mi_gp_sparse_work.argtypes = [ci, ci]
+    lib.mi_gp_sparse_work.restype = cl
+    lib.mi_gp_sparse_set_data.argtypes = [vp, vp, vp, ci, vp, vp, cl]
+    lib.mi_gp_sparse_bound_grad.argtypes = [vp, dp, dp, dp]
+    lib.mi_gp_sparse_factor.argtypes = [vp, dp]
+    lib.mi_gp_sparse_predict.argtypes = [vp, vp, ci, vp, vp, ci]
+    for name in SPARSE_EXPORTS:
+        getattr(lib, name)  # raises AttributeError if a declared symbol is missing
+    _sparse = lib
+    return lib
+
+
+# every symbol include/mi_gp_sparse.h declares (checked by tests/test_sparse_abi_host.py against the header text)
+SPARSE_EXPORTS = [
+    "mi_gp_sparse_create",
+    "mi_gp_sparse_destroy",
+    "mi_gp_sparse_last_error",
+    "mi_gp_sparse_work",
+    "mi_gp_sparse_set_data",
+    "mi_gp_sparse_bound_grad",
+    "mi_gp_sparse_factor",
+    "mi_gp_sparse_predict",
 ]

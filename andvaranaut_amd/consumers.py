@@ -188,6 +188,7 @@ class ConsumersMixin:
         refactorisation would also see, but the resident factor is already theirs)."""
         import torch
 
+        self._no_sparse("BO's single-point potential (opt_method other than 'predict' / 'DE', or refine=True)")
         theta = self._theta_from_hypers(self.hypers, jitter)
         xi_np, wi_np = np.polynomial.hermite.hermgauss(8)
         xi, wi = torch.from_numpy(xi_np), torch.from_numpy(wi_np)
@@ -256,6 +257,10 @@ class ConsumersMixin:
         refit_every = int(refit_every)
         if refit_every < 1:
             raise ValueError("refit_every must be >= 1")
+        if refit_every > 1:
+            self._no_sparse("BO(refit_every > 1)")
+        if method == "TS":
+            self._no_sparse("BO(method='TS')")
         if refit_every > 1 and (iwgp or cwgp):
             raise ValueError("refit_every > 1 is not supported with iwgp / cwgp (the warps are refitted with the hyper-parameters)")
         if self.ny > 1:
@@ -402,6 +407,8 @@ class ConsumersMixin:
             raise ValueError(f"inverse_opt has no form under trend={self.trend!r}: fit without a trend to use it")
         if getattr(self, "outputs", "first") == "all":
             raise ValueError("inverse_opt has no form under outputs='all': fit with outputs='first' to use it")
+        if resident:
+            self._no_sparse("inverse_opt(resident=True)")
         if self.m is None:
             raise Exception("Model must be fitted before running Bayesian optimisation")
         if self.verbose:

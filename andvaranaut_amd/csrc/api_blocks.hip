@@ -203,6 +203,11 @@ static hipError_t trsm_block_rec(const double* L, long ldl, const double* dinv, 
   return trsm_block_rec(L, ldl, dinv, B, ldb, m, cbase, c0 + w1, w2, st);
 }
 
+hipError_t migp::trsm_blocks(const double* L, long ldl, const double* dinv, double* B, long ldb, int m, int c0, int w,
+                             hipStream_t st) {
+  return trsm_block_rec(L, ldl, dinv, B, ldb, m, c0, c0, w, st);
+}
+
 extern "C" int mi_gp_trsm_block(const double* L_dev, long ldl, const double* dinv_dev, int c0_tiles, int w_tiles,
                                 double* B_dev, long ldb, int m, void* stream) {
   if (!L_dev || !dinv_dev || !B_dev || c0_tiles < 0 || w_tiles <= 0 || m <= 0 || m % 128 || (ldl & 1) || (ldb & 1)) {

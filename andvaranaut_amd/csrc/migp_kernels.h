@@ -444,7 +444,33 @@ hipError_t launch_path_residual(const double* y, const double* V, long ldw, int 
 // V[j * ldw + s] = R1[s * ldr + j] for s < S, j < n
 hipError_t launch_path_scatter(double* V, long ldw, int n, int S, const PathScratch& t, hipStream_t stream);
 
+// ---------------------------------------------------------------- sparse_f64.hip (the sparse inducing-point bound, api_sparse.hip)
+int sparse_contract_blocks(int cnt, int m);  // 64 x 64 tiles of the cnt x m cross-covariance
+// acc[ntheta] (first: =, else +=) sum_{i < cnt, u < m} (T[i][u] + y[i] tv[u]) dK(x_i, z_u)/dtheta (natural parameters, C-ABI
+// order; the gv and jitter slots receive 0).  part: [sparse_contract_blocks(cnt, m)][ntheta] scratch
+hipError_t launch_sparse_contract(const KernSpec& spec, const double* theta, const double* X, int cnt, const double* Z, int m,
+                                  const double* T, long ldt, const double* y, const double* tv, double* part, double* acc, int first,
+                                  hipStream_t stream);
+// v[u] (first: =, else +=) sum_{i < cnt} At[i][u] y[i] for u < mp (a multiple of 64), yy[0] likewise sum y_i^2
+hipError_t launch_sparse_accum_vy(const double* At, long ld, int mp, const double* y, int cnt, double* v, double* yy, int first,
+                                  hipStream_t stream);
+// B = I + Psi / s over mp x mp (leading dimension mp)
+hipError_t launch_sparse_make_b(const double* Psi, double* B, int mp, double s, hipStream_t stream);
+// out[i] = in[i] / s, i < n
+hipError_t launch_sparse_scale(const double* in, double* out, int n, double s, hipStream_t stream);
+// out[0..4] = sum log LB_ii, tr Psi, |c|^2, |a^|^2, tr B^-1 over the leading m entries (ahat / Binv optional: 0 without)
+hipError_t launch_sparse_scalars(const double* LB, const double* Psi, long ld, const double* cvec, const double* ahat,
+                                 const double* Binv, int m, double* out, hipStream_t stream);
+// H = I - B^-1 - a^ a^^T, G0 = Psi / s - H over mp x mp (Psi: lower triangle; ahat: mp entries, zeros from m on)
+hipError_t launch_sparse_hg(const double* Psi, const double* Binv, const double* ahat, int mp, double s, double* H, double* G0,
+                            hipStream_t stream);
+// mean[i] = Bq_i . c, var[i] = kdiag - |A_i|^2 + |Bq_i|^2 + noise for i < mq (rows ld apart, m entries each)
+hipError_t launch_sparse_predict_reduce(const double* A, const double* Bq, long ld, const double* cvec, int m, int mq, double kdiag,
+                                        double noise, double* mean, double* var, hipStream_t stream);
+
 // ---------------------------------------------------------------- api_blocks.hip
+// X L^T = B in place for the tile columns [c0, c0 + w) of a lower factor L (the body of mi_gp_trsm_block)
+hipError_t trsm_blocks(const double* L, long ldl, const double* dinv, double* B, long ldb, int m, int c0, int w, hipStream_t st);
 // text behind mi_gp_last_global_error() (calls that have no handle to carry it: mi_gp_create, the block-level entries)
 void set_global_error(const char* text);
 // leaf + strip + in-panel updates of the w_tiles leading tile columns of a (row_tiles x w_tiles)-tile lower trapezoid

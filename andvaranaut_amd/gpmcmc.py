@@ -18,6 +18,7 @@ from time import time as stopwatch
 import numpy as np
 
 from .backend import MiGP, parse_kernel
+from .sparse import MAX_INDUCING, MiSparseGP, select_inducing
 from .consumers import ConsumersMixin
 from .lhc import latin_sample
 from .nuts import Trace, sample_chain
@@ -343,6 +344,7 @@ class GPMCMC(ConsumersMixin):
         ``log_predictive``), ``lpd_folds`` (per fold, its Jacobian included), ``folds`` and ``info`` (0 per fold, or the
         pivot at which the fold's block of K^-1 was not positive definite)."""
         self._no_trend("cv_stats")
+        self._no_sparse("cv_stats")
         self._no_all_outputs("cv_stats")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before cross-validating")
@@ -434,6 +436,7 @@ class GPMCMC(ConsumersMixin):
         from .consumers import _con_and_der
 
         self._no_trend("predict_mean")
+        self._no_sparse("predict_mean")
         self._no_all_outputs("predict_mean")
         if return_grad and self.mean != self.zero_mean:
             raise ValueError("predict_mean(return_grad=True) has no form under a non-zero mean function")
@@ -467,6 +470,7 @@ class GPMCMC(ConsumersMixin):
         Each draw is one consistent function over any number of calls; it is of the latent f (no observation noise).  The
         object goes stale (RuntimeError) once the GP is factorised again at other hyper-parameters or given other data."""
         self._no_trend("sample_paths")
+        self._no_sparse("sample_paths")
         self._no_all_outputs("sample_paths")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before sampling paths")
@@ -557,6 +561,7 @@ class GPMCMC(ConsumersMixin):
         self.trend = None
         self.outputs = "first"
         self.output_cov = "shared"
+        self.inducing = None
 
     def __release(self):
         gp = getattr(self, "gp", None)
@@ -575,6 +580,9 @@ class GPMCMC(ConsumersMixin):
     def _ensure_gp(self):
         if self.gp is None and self.hypers is not None and self.m is not None:
             xin, yin = self._converted(self.x, self.y - self.ym)
+            if getattr(self, "inducing", None) is not None:  # a sparse fit: the bound's object on the stored inducing points
+                self.gp = MiSparseGP(xin, yin, self.inducing, self.kernel, device=self.device)
+                return self.gp
             self.gp = MiGP(xin, yin, self.kernel, device=self.device)
             if getattr(self, "trend", None) is not None:
                 self.gp.set_trend(self.trend)
@@ -588,6 +596,32 @@ class GPMCMC(ConsumersMixin):
         if getattr(self, "trend", None) is not None:
             raise ValueError(f"{what} has no form under trend={self.trend!r}: fit without a trend to use it")
 
+    def _no_sparse(self, what):
+        """Raised, before any device call, by what needs the dense factorisation after a fit on inducing points."""
+        if getattr(self, "inducing", None) is not None:
+            raise ValueError(f"{what} has no form under a sparse fit (inducing={len(self.inducing)} points): it needs the dense "
+                             "factorisation; fit with inducing=None to use it")
+
+    def _inducing_points(self, inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs):
+        """The converted inducing points Z of fit(inducing=...), or None.  Every refusal is raised here, before any device call."""
+        if inducing is None:
+            return None
+        if method not in ("map", "none") or iwgp or cwgp or objective != "lml" or trend is not None or outputs != "first":
+            raise ValueError("inducing needs method='map' or 'none', objective='lml', trend=None, outputs='first' and neither iwgp "
+                             "nor cwgp: the sparse bound has no sampler, no cross-validation objective, no trend, no warps and one output")
+        xin, _ = self._converted(self.x, self.y - self.ym)
+        if isinstance(inducing, (int, np.integer)) and not isinstance(inducing, bool):
+            if not 1 <= inducing <= min(len(xin), MAX_INDUCING):
+                raise ValueError(f"inducing = {inducing} points: 1 <= inducing <= min(n, {MAX_INDUCING}) is required (n = {len(xin)})")
+            return select_inducing(xin, int(inducing), seed=inducing_seed)
+        Z = np.array(inducing, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[1] != self.nx or not 1 <= Z.shape[0] <= min(len(xin), MAX_INDUCING) or not np.isfinite(Z).all():
+            raise ValueError(f"inducing must be an int or a finite (m, nx = {self.nx}) array of raw inputs with 1 <= m <= "
+                             f"min(n, {MAX_INDUCING})")
+        for i in range(self.nx):
+            Z[:, i] = self.xconrevs[i].con(Z[:, i])
+        return np.ascontiguousarray(Z)
+
     def _no_all_outputs(self, what):
         """Raised, before any device call, by what has no form once every output is modelled (fit(outputs="all"))."""
         if getattr(self, "outputs", "first") == "all":
@@ -600,7 +634,7 @@ class GPMCMC(ConsumersMixin):
     # ------------------------------------------------------------------ fit
     def fit(self, method="map", return_data=False, iwgp=False, cwgp=False, jitter=1e-6, truncate=False,
             restarts=1, objective="lml", nfolds=10, fold_seed=None, trend=None, outputs="first", output_cov="shared",
-            **kwargs):
+            inducing=None, inducing_seed=None, **kwargs):
         """gpmcmc.py:175-182.  ``objective="loo"`` (with ``method="map"``) maximises the leave-one-out log predictive density
         sum_i log p(y_i | y_-i) plus the priors instead of the log marginal likelihood (Rasmussen & Williams section 5.4.2: the
         criterion for a misspecified kernel family); the hyper-parameters are stored as a MAP fit stores them.  It has no
@@ -626,7 +660,17 @@ class GPMCMC(ConsumersMixin):
         separable emulator of Conti & O'Hagan 2010): the fit no longer depends on how the columns are scaled or mixed, and
         ``predict(return_var=True)`` returns a variance per output, column i reverted through ``yconrevs[i]``.  That marginal
         likelihood does not change under K_y -> c K_y, so only their priors identify the overall scale of kv, gv and the
-        jitter.  The choice is part of the object's state (``self.output_cov``)."""
+        jitter.  The choice is part of the object's state (``self.output_cov``).
+        ``inducing=m`` (an int) or an (m, nx) array of raw inputs (with ``method="map"`` or ``"none"``, ``objective="lml"``, no
+        trend, no warps, ``outputs="first"``) fits on m << n inducing points instead of the n x n covariance, for data sets one
+        card cannot factorise: the fit maximises Titsias' collapsed variational bound (a lower bound of the log marginal
+        likelihood, exact theta gradient, the data streamed in chunks) plus the priors, and ``predict`` returns the sparse
+        predictive.  An int chooses the points by k-means++ seeding among the converted inputs (``select_inducing``,
+        ``inducing_seed``); an array goes through ``xconrevs``.  At most 2048 points.  The inducing locations are not
+        optimised.  The choice is part of the object's state (``self.inducing``, the converted points) and survives pickling;
+        what needs the dense factorisation (predict_joint, sample_posterior, log_predictive, cv_stats, predict_mean,
+        sample_paths, predict_posterior, the resident paths of BO and inverse_opt) then raises ValueError."""
+        Z = self._inducing_points(inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs)
         if outputs not in ("first", "all"):
             raise ValueError(f"outputs must be 'first' or 'all' (got {outputs!r})")
         if output_cov not in MiGP.OUTPUT_COVS:
@@ -654,7 +698,8 @@ class GPMCMC(ConsumersMixin):
             raise ValueError("objective='loo' needs method='map' and neither iwgp nor cwgp")
         self.m, self.gp, self.hypers, data = self.__fit(self.x, self.y - self.ym, method, iwgp, cwgp, jitter,
                                                         truncate, restarts, objective=objective, cv=cv, trend=trend, outputs=outputs,
-                                                        output_cov=output_cov, **kwargs)
+                                                        output_cov=output_cov, inducing=Z, **kwargs)
+        self.inducing = Z
         self.trend = trend
         self.outputs = outputs
         self.output_cov = output_cov
@@ -785,13 +830,15 @@ class GPMCMC(ConsumersMixin):
         return likelihood
 
     def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", cv=None, trend=None,
-              outputs="first", output_cov="shared", **kwargs):
+              outputs="first", output_cov="shared", inducing=None, **kwargs):
         n_i, n_pos, n_free = self._warp_sizes(iwgp, cwgp)
         model = HyperModel(self.nx, self.kerns, noise=self.noise, truncate=truncate, jitter=jitter, n_iwgp=n_i,
                            n_cwgp_pos=n_pos, n_cwgp=n_free)
         xin, yin = self._converted(x, y)
         self.__release()
-        gp = MiGP(xin, yin, self.kernel, device=self.device)
+        # (inducing points: gp.lml_grad is then the sparse bound and its gradient, gp.predict the sparse predictive)
+        gp = MiGP(xin, yin, self.kernel, device=self.device) if inducing is None else MiSparseGP(xin, yin, inducing, self.kernel,
+                                                                                                  device=self.device)
         if trend is not None:
             gp.set_trend(trend)  # (gp.lml_grad then returns the trend's marginal likelihood; the stored handle keeps the trend)
         if outputs == "all":
@@ -1106,6 +1153,7 @@ class GPMCMC(ConsumersMixin):
         A covariance has no image under a nonlinear output reversion, so there is no ``revert`` here (sample_posterior
         reverts draws instead)."""
         self._no_trend("predict_joint")
+        self._no_sparse("predict_joint")
         self._no_all_outputs("predict_joint")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
@@ -1118,6 +1166,7 @@ class GPMCMC(ConsumersMixin):
         units, at ``self.hypers``: log N(y_con | conditional of the fitted GP at x_con, with observation noise) plus the
         Jacobian sum log|d y_con / d y| when the output conversion has ``der`` (MiGP.logpdf; nothing is appended)."""
         self._no_trend("log_predictive")
+        self._no_sparse("log_predictive")
         self._no_all_outputs("log_predictive")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
@@ -1140,6 +1189,7 @@ class GPMCMC(ConsumersMixin):
         output reversion point by point and adds the mean function -- exact for sample paths, no quadrature.  ``seed``: see
         MiGP.sample_posterior (None: fresh draws on every call)."""
         self._no_trend("sample_posterior")
+        self._no_sparse("sample_posterior")
         self._no_all_outputs("sample_posterior")
         if self._ensure_gp() is None or self.hypers is None:
             raise Exception("Error: fit the GP before predicting")
@@ -1189,6 +1239,7 @@ class GPMCMC(ConsumersMixin):
         unreverted moments bit for bit where predict() takes the triangular solve (not U = L^-T, MiGP.predict), the reverted
         ones to rounding."""
         self._no_trend("predict_posterior")
+        self._no_sparse("predict_posterior")
         self._no_all_outputs("predict_posterior")
         if self._ensure_gp() is None or self.m is None:
             raise Exception("Error: fit the GP before predicting")
