@@ -79,6 +79,7 @@ class MiGpSparseConfig(ctypes.Structure):
         ("ops", ctypes.c_int * MAX_KERN),
         ("device", ctypes.c_int),
         ("chunk", ctypes.c_int),
+        ("zgrad_slabs", ctypes.c_int),  # 0: no dF/dZ; s >= 1: dF/dZ behind dF/dtheta, at most s slabs per chunk
     ]
 
 

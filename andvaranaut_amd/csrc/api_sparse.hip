@@ -1,7 +1,7 @@
 // The sparse inducing-point bound, the C-ABI of libmi_gp_sparse.so (include/mi_gp_sparse.h has the algebra and the contract): an
 // object of its own in the manner of mi_gp_shard, built from the launchers the dense paths use -- the cross-assembly and blocked solve of
 // mi_gp_predict, the panel factorisation of mi_gp_chol_panel, the GEMM, the symmetric contraction of mi_gp_lml_grad -- and the
-// kernels of sparse_f64.hip.
+// kernels of sparse_f64.hip and, for the gradient by the inducing locations, sparse_zgrad_f64.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -51,23 +51,35 @@ struct mi_gp_sparse {
   int n, m, mp, ntm, d, P, chunk;
   hipStream_t stream = nullptr;
   // the object's own scratch (first mi_gp_sparse_set_data): theta [P], the chunks' gradient [P], Kuu's gradient [P], two scalar
-  // records [8] each, yy [2], the two bad-pivot words [2 doubles], then the partial sums of the two contractions
+  // records [8] each, yy [2], the two bad-pivot words [2 doubles], dF/dZ [m d, with zgrad_slabs >= 1 only], then the partial sums
+  // of the two contractions and, with zgrad_slabs >= 1, Kuu's part of dF/dZ [m d] and the slab scratch the two passes over Z share
   double* own_dev = nullptr;
-  double* host = nullptr;  // pinned mirror of the first 3 P + 20 doubles
+  double* host = nullptr;  // pinned mirror of the first 3 P + 20 (+ m d) doubles
   const double *X = nullptr, *y = nullptr, *Z = nullptr;
   double* work = nullptr;
   bool have_data = false, factored = false;
   double fac_s = 0.0, fac_kdiag = 0.0;  // noise variance and prior variance at the factored theta
   char err[256] = "";
-  long small_len() const { return 3L * P + 20; }
+  int zcap() const { return cfg.zgrad_slabs; }  // 0: no dF/dZ, every call as it was before the field existed
+  long zlen() const { return zcap() > 0 ? (long)m * d : 0; }
+  long small_len() const { return 3L * P + 20 + zlen(); }
   double* theta_dev() const { return own_dev; }
   double* gacc_dev() const { return own_dev + P; }
   double* gsym_dev() const { return own_dev + 2 * P; }
   double* scal_dev() const { return own_dev + 3 * P; }        // [0..8) pass 1's record, [8..16) the gradient's
   double* yy_dev() const { return own_dev + 3 * P + 16; }
   int* info_dev() const { return reinterpret_cast<int*>(own_dev + 3 * P + 18); }  // [0] Kuu, [1] B
+  double* gz_dev() const { return own_dev + 3 * P + 20; }    // dF/dZ: the chunks' sums, then Kuu's part added
   double* part_rect_dev() const { return own_dev + small_len(); }
   double* part_sym_dev() const { return part_rect_dev() + (long)sparse_contract_blocks(chunk, m) * P; }
+  double* gzsym_dev() const { return part_sym_dev() + (long)grad_contract_blocks(m) * P; }
+  double* zscratch_dev() const { return gzsym_dev() + zlen(); }
+  // the slab scratch: the largest chunk's slabs of sparse_zgrad, or the column splits of grad_x over Z (one after the other)
+  long zscratch_len() const {
+    if (zcap() <= 0) return 0;
+    const int splits = grad_x_splits(m, d);
+    return std::max(sparse_zgrad_scratch(std::min(chunk, n), m, d, zcap()), splits > 1 ? (long)splits * m * d : 0L);
+  }
 };
 
 static thread_local char g_sparse_err[256] = "";
@@ -119,6 +131,10 @@ extern "C" int mi_gp_sparse_create(const mi_gp_sparse_config* cfg, mi_gp_sparse*
     snprintf(g_sparse_err, sizeof(g_sparse_err), "mi_gp_sparse_create: chunk must be a multiple of 128 (0: the default), got %d", cfg->chunk);
     return -1;
   }
+  if (cfg->zgrad_slabs < 0) {
+    snprintf(g_sparse_err, sizeof(g_sparse_err), "mi_gp_sparse_create: zgrad_slabs must be >= 0 (0: no dF/dZ), got %d", cfg->zgrad_slabs);
+    return -1;
+  }
   if (const char* why = kern_spec_error(cfg->nkern, cfg->kernel_ids, cfg->ops)) {
     snprintf(g_sparse_err, sizeof(g_sparse_err), "mi_gp_sparse_create: %s", why);
     return -1;
@@ -152,7 +168,8 @@ extern "C" int mi_gp_sparse_set_data(mi_gp_sparse* s, const double* X_dev, const
   SCK(hipSetDevice(s->cfg.device), "hipSetDevice");
   if (!s->stream) SCK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "hipStreamCreate");
   if (!s->own_dev) {
-    const long own = s->small_len() + ((long)sparse_contract_blocks(s->chunk, s->m) + grad_contract_blocks(s->m)) * s->P;
+    const long own = s->small_len() + ((long)sparse_contract_blocks(s->chunk, s->m) + grad_contract_blocks(s->m)) * s->P + s->zlen() +
+                     s->zscratch_len();
     SCK(hipMalloc(&s->own_dev, sizeof(double) * own), "hipMalloc");
   }
   if (!s->host) SCK(hipHostMalloc(&s->host, sizeof(double) * s->small_len()), "hipHostMalloc");
@@ -294,11 +311,23 @@ static int gradient(mi_gp_sparse* s, const double* theta, double* grad_out) {
     SCK(launch_gemm_f64(p, 0, 1, 1, s->stream), "T rows");
     SCK(launch_sparse_contract(s->spec, s->theta_dev(), s->X + i0 * d, cnt, s->Z, m, w.Tc, mp, s->y + i0, w.tv, s->part_rect_dev(),
                                s->gacc_dev(), first, s->stream), "contraction");
+    if (s->zcap() > 0)  // Kuf's term of dF/dZ on the same weights: the chunks in chunk order onto gz
+      SCK(launch_sparse_zgrad(s->spec, s->theta_dev(), s->X + i0 * d, cnt, s->Z, m, w.Tc, mp, s->y + i0, w.tv, s->zcap(),
+                              s->zscratch_dev(), s->gz_dev(), first, s->stream), "dF/dZ contraction");
   }
   // Kuu's term through the symmetric contraction: W = -2 Guu and a zero alpha give sum_uv Guu_uv dK(Z,Z)_uv/dtheta (its gv and
   // jitter slots, 1/2 tr(-W), are not used)
   SCK(launch_grad_contract(s->spec, s->theta_dev(), s->Z, m, w.H, mp, w.zero, s->part_sym_dev(), s->gsym_dev(), s->stream), "Kuu's contraction");
-  SCK(hipMemcpyAsync(s->host + P, s->gacc_dev(), sizeof(double) * (2 * P + 16), hipMemcpyDeviceToHost, s->stream), "gradient download");
+  if (s->zcap() > 0) {
+    // Kuu's term of dF/dZ through dLML/dX's kernel over Z: with a zero alpha its weight is -W_uv = 2 Guu_uv, read from the lower
+    // triangle, and row and column of the symmetric sum contribute equally -- 2 sum_v Guu_uv dK(Z,Z)_uv/dz_u.  Then gz += that.
+    SCK(launch_grad_x(s->spec, s->theta_dev(), s->Z, m, w.H, mp, w.zero, s->gzsym_dev(), grad_x_splits(m, d) > 1 ? s->zscratch_dev() : nullptr,
+                      s->stream), "Kuu's dF/dZ");
+    SCK(launch_sparse_zgrad_add(s->gzsym_dev(), 1, 0, s->zlen(), s->gz_dev(), 0, s->stream), "dF/dZ sum");
+  }
+  // (with dF/dZ the copy runs on over yy and the pivot words, which pass 1 has downloaded already, to the end of gz)
+  SCK(hipMemcpyAsync(s->host + P, s->gacc_dev(), sizeof(double) * (s->zcap() > 0 ? 2 * P + 20 + s->zlen() : 2 * P + 16), hipMemcpyDeviceToHost,
+                     s->stream), "gradient download");
   SCK(hipStreamSynchronize(s->stream), "stream sync");
   const double* ga = s->host + P;
   const double* gs = s->host + 2 * P;
@@ -311,6 +340,7 @@ static int gradient(mi_gp_sparse* s, const double* theta, double* grad_out) {
   grad_out[P - 2] = -(double)n / (2.0 * sv) + yy / (2.0 * sv * sv) + (kappa - sc[1]) / (2.0 * sv * sv) + ((double)m - sc[12]) / (2.0 * sv) -
                     (sc[2] + sc[11]) / (2.0 * sv);
   grad_out[P - 1] = 0.0;  // jitter is a constant of the fit
+  if (s->zcap() > 0) memcpy(grad_out + P, s->host + 3 * P + 20, sizeof(double) * s->zlen());
   return 0;
 }
 
@@ -327,7 +357,7 @@ extern "C" int mi_gp_sparse_bound_grad(mi_gp_sparse* s, const double* theta_host
   if (!bound) { snprintf(s->err, sizeof(s->err), "mi_gp_sparse_bound_grad: null bound"); return -1; }
   s->factored = false;
   if (grad_out)
-    for (int k = 0; k < s->P; ++k) grad_out[k] = 0.0;
+    for (long k = 0; k < s->P + s->zlen(); ++k) grad_out[k] = 0.0;
   int r = pass_one(s, theta_host, bound);
   if (r == 0 && grad_out) {
     r = gradient(s, theta_host, grad_out);

@@ -451,6 +451,18 @@ int sparse_contract_blocks(int cnt, int m);  // 64 x 64 tiles of the cnt x m cro
 hipError_t launch_sparse_contract(const KernSpec& spec, const double* theta, const double* X, int cnt, const double* Z, int m,
                                   const double* T, long ldt, const double* y, const double* tv, double* part, double* acc, int first,
                                   hipStream_t stream);
+// (sparse_zgrad_f64.hip) Slabs of one chunk's dF/dZ pass: min(64-row blocks of the chunk, cap, ceil(1024 / 64-column blocks of m)), lowered until the
+// slab scratch is at most 64 MB -- a function of (cnt, m, d, cap) alone -- and the doubles of scratch they take
+int sparse_zgrad_slabs(int cnt, int m, int d, int cap);
+long sparse_zgrad_scratch(int cnt, int m, int d, int cap);
+// gz[m x d] (first: =, else +=) sum_{i < cnt} (T[i][u] + y[i] tv[u]) dK(x_i, z_u)/dz_u: workgroup (ub, sl) of the grid
+// (ceil(m / 64), slabs) walks the data blocks sl, sl + slabs, ..., and the slabs are added in slab order.  scratch:
+// sparse_zgrad_scratch(cnt, m, d, cap) doubles
+hipError_t launch_sparse_zgrad(const KernSpec& spec, const double* theta, const double* X, int cnt, const double* Z, int m,
+                               const double* T, long ldt, const double* y, const double* tv, int cap, double* scratch, double* gz,
+                               int first, hipStream_t stream);
+// gz[e] (first: =, else +=) sum_{k < nslab} part[k * slab + e] for e < len, in slab order
+hipError_t launch_sparse_zgrad_add(const double* part, int nslab, long slab, long len, double* gz, int first, hipStream_t stream);
 // v[u] (first: =, else +=) sum_{i < cnt} At[i][u] y[i] for u < mp (a multiple of 64), yy[0] likewise sum y_i^2
 hipError_t launch_sparse_accum_vy(const double* At, long ld, int mp, const double* y, int cnt, double* v, double* yy, int first,
                                   hipStream_t stream);

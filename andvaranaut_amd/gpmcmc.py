@@ -602,8 +602,11 @@ class GPMCMC(ConsumersMixin):
             raise ValueError(f"{what} has no form under a sparse fit (inducing={len(self.inducing)} points): it needs the dense "
                              "factorisation; fit with inducing=None to use it")
 
-    def _inducing_points(self, inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs):
+    def _inducing_points(self, inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs, optimize_inducing=False):
         """The converted inducing points Z of fit(inducing=...), or None.  Every refusal is raised here, before any device call."""
+        if optimize_inducing and (inducing is None or method != "map"):
+            raise ValueError("optimize_inducing=True needs inducing points to move and method='map': give inducing=m or an array, "
+                             "and fit with method='map'")
         if inducing is None:
             return None
         if method not in ("map", "none") or iwgp or cwgp or objective != "lml" or trend is not None or outputs != "first":
@@ -634,7 +637,7 @@ class GPMCMC(ConsumersMixin):
     # ------------------------------------------------------------------ fit
     def fit(self, method="map", return_data=False, iwgp=False, cwgp=False, jitter=1e-6, truncate=False,
             restarts=1, objective="lml", nfolds=10, fold_seed=None, trend=None, outputs="first", output_cov="shared",
-            inducing=None, inducing_seed=None, **kwargs):
+            inducing=None, inducing_seed=None, optimize_inducing=False, **kwargs):
         """gpmcmc.py:175-182.  ``objective="loo"`` (with ``method="map"``) maximises the leave-one-out log predictive density
         sum_i log p(y_i | y_-i) plus the priors instead of the log marginal likelihood (Rasmussen & Williams section 5.4.2: the
         criterion for a misspecified kernel family); the hyper-parameters are stored as a MAP fit stores them.  It has no
@@ -666,11 +669,15 @@ class GPMCMC(ConsumersMixin):
         card cannot factorise: the fit maximises Titsias' collapsed variational bound (a lower bound of the log marginal
         likelihood, exact theta gradient, the data streamed in chunks) plus the priors, and ``predict`` returns the sparse
         predictive.  An int chooses the points by k-means++ seeding among the converted inputs (``select_inducing``,
-        ``inducing_seed``); an array goes through ``xconrevs``.  At most 2048 points.  The inducing locations are not
-        optimised.  The choice is part of the object's state (``self.inducing``, the converted points) and survives pickling;
+        ``inducing_seed``); an array goes through ``xconrevs``.  At most 2048 points.  With ``optimize_inducing=False``
+        (default) the locations stay where they are.  ``optimize_inducing=True`` (``method="map"``) trains them jointly with the
+        hyper-parameters, as the bound -- variational in Z -- allows: L-BFGS-B runs over [q | vec(Z)] with the exact dF/dZ of the
+        device, Z in converted input space without prior or bounds, started at the points ``inducing`` gives;
+        ``data["inducing_start"]`` keeps those.  The choice is part of the object's state (``self.inducing``, the converted --
+        with ``optimize_inducing`` the optimised -- points) and survives pickling;
         what needs the dense factorisation (predict_joint, sample_posterior, log_predictive, cv_stats, predict_mean,
         sample_paths, predict_posterior, the resident paths of BO and inverse_opt) then raises ValueError."""
-        Z = self._inducing_points(inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs)
+        Z = self._inducing_points(inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs, optimize_inducing)
         if outputs not in ("first", "all"):
             raise ValueError(f"outputs must be 'first' or 'all' (got {outputs!r})")
         if output_cov not in MiGP.OUTPUT_COVS:
@@ -698,8 +705,9 @@ class GPMCMC(ConsumersMixin):
             raise ValueError("objective='loo' needs method='map' and neither iwgp nor cwgp")
         self.m, self.gp, self.hypers, data = self.__fit(self.x, self.y - self.ym, method, iwgp, cwgp, jitter,
                                                         truncate, restarts, objective=objective, cv=cv, trend=trend, outputs=outputs,
-                                                        output_cov=output_cov, inducing=Z, **kwargs)
-        self.inducing = Z
+                                                        output_cov=output_cov, inducing=Z, optimize_inducing=optimize_inducing,
+                                                        **kwargs)
+        self.inducing = data["inducing"] if optimize_inducing else Z
         self.trend = trend
         self.outputs = outputs
         self.output_cov = output_cov
@@ -830,7 +838,7 @@ class GPMCMC(ConsumersMixin):
         return likelihood
 
     def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", cv=None, trend=None,
-              outputs="first", output_cov="shared", inducing=None, **kwargs):
+              outputs="first", output_cov="shared", inducing=None, optimize_inducing=False, **kwargs):
         n_i, n_pos, n_free = self._warp_sizes(iwgp, cwgp)
         model = HyperModel(self.nx, self.kerns, noise=self.noise, truncate=truncate, jitter=jitter, n_iwgp=n_i,
                            n_cwgp_pos=n_pos, n_cwgp=n_free)
@@ -838,7 +846,8 @@ class GPMCMC(ConsumersMixin):
         self.__release()
         # (inducing points: gp.lml_grad is then the sparse bound and its gradient, gp.predict the sparse predictive)
         gp = MiGP(xin, yin, self.kernel, device=self.device) if inducing is None else MiSparseGP(xin, yin, inducing, self.kernel,
-                                                                                                  device=self.device)
+                                                                                                  device=self.device,
+                                                                                                  z_grad=bool(optimize_inducing))
         if trend is not None:
             gp.set_trend(trend)  # (gp.lml_grad then returns the trend's marginal likelihood; the stored handle keeps the trend)
         if outputs == "all":
@@ -848,6 +857,26 @@ class GPMCMC(ConsumersMixin):
         # pm.find_MAP maximises without the transform Jacobian, pm.sample with it (priors.py header)
         fun_map = lambda q: model.logp_dlogp(q, gp.lml_grad, jacobian=False, likelihood=lik)  # noqa: E731
         data = None
+        nq, zbest = model.nq, None
+        if optimize_inducing:
+            # the inducing locations join the optimiser's vector, [q | vec(Z)]: every evaluation moves Z on the device, takes the
+            # bound with both gradients in one call, hands the theta part to the model and appends dF/dZ (Z has no prior)
+            def fun_map(qz):  # noqa: F811
+                Zq = qz[nq:].reshape(inducing.shape)
+                if not np.isfinite(Zq).all():
+                    return -np.inf, np.zeros(len(qz))
+                gp.set_inducing(Zq)
+                cell = {}
+
+                def bound_grad(theta):
+                    F, g, cell["gz"] = gp.lml_grad_z(theta)
+                    return F, g
+
+                v, g = model.logp_dlogp(qz[:nq], bound_grad, jacobian=False)
+                if not np.isfinite(v) or "gz" not in cell:
+                    return -np.inf, np.zeros(len(qz))
+                return v, np.concatenate([g, cell["gz"].ravel()])
+
         if method == "map":
             fit_gp = None
             if cv is not None:
@@ -870,6 +899,8 @@ class GPMCMC(ConsumersMixin):
                     q0 = model.initial_point()
                     if kwargs.get("start") is not None:  # pm.find_MAP(start=...), e.g. BO's warm refits (gpmcmc.py:899)
                         q0 = model.q_from_point(kwargs["start"])
+                    if optimize_inducing:
+                        q0 = np.concatenate([q0, inducing.ravel()])
                     q, info = find_MAP(fun_map, q0, progressbar=kwargs.get("progressbar", False),
                                        maxeval=kwargs.get("maxeval", 5000))
                 except RuntimeError:
@@ -881,7 +912,7 @@ class GPMCMC(ConsumersMixin):
                     last_error = e
                     continue
                 if info["logp"] > best:
-                    best, mp, data = info["logp"], model.point_dict(q), info
+                    best, mp, data, zbest = info["logp"], model.point_dict(q[:nq]), info, q[nq:]
             if fit_gp is not None:
                 fit_gp.close()
                 if data is not None:
@@ -890,6 +921,10 @@ class GPMCMC(ConsumersMixin):
                 gp.set_objective("lml")
             if mp is None:
                 raise RuntimeError("find_MAP failed in every restart") from last_error
+            if optimize_inducing:
+                data["inducing_start"] = inducing.copy()
+                data["inducing"] = np.ascontiguousarray(zbest.reshape(inducing.shape))
+                gp.set_inducing(data["inducing"])  # the stored object predicts on the optimised points
             if self.verbose:
                 print(f"MAP: {data['nfev']} evaluations, logp = {data['logp']:,.5g}")
         elif method == "none":

@@ -13,6 +13,7 @@ from .backend import parse_kernel
 
 MAX_INDUCING = 2048
 DEFAULT_CHUNK = 8192
+DEFAULT_ZGRAD_SLABS = 1024  # no cap of its own: the library's rule (row blocks of the chunk, 1024 workgroups, 64 MB) decides
 
 
 def select_inducing(X, m, seed=None):
@@ -42,9 +43,12 @@ def select_inducing(X, m, seed=None):
 
 class MiSparseGP:
     """One data set, one set of inducing points and one kernel structure bound to one MI355X: the bound F(theta) <= LML, its
-    gradient and the sparse predictive.  lml_grad has MiGP.lml_grad's signature, so HyperModel.logp_dlogp takes it unchanged."""
+    gradient and the sparse predictive.  lml_grad has MiGP.lml_grad's signature, so HyperModel.logp_dlogp takes it unchanged.
+    ``z_grad=True`` adds the exact gradient of the bound by the inducing locations: lml_grad_z returns (F, dF/dtheta, dF/dZ),
+    set_inducing moves Z (lml_grad still returns (F, dF/dtheta) alone).  ``zgrad_slabs`` caps the slabs per chunk of its kernel
+    (None: the library's rule); another count regroups sums, the same count returns the same bits."""
 
-    def __init__(self, X, y, Z, kernel="RBF", device=0, chunk=None):
+    def __init__(self, X, y, Z, kernel="RBF", device=0, chunk=None, z_grad=False, zgrad_slabs=None):
         if not torch.cuda.is_available():
             raise RuntimeError("MiSparseGP needs a ROCm GPU: the GP hot path has no CPU implementation")
         self.lib = _lib.load_sparse()
@@ -77,6 +81,10 @@ class MiSparseGP:
         for i, o in enumerate(self.ops):
             cfg.ops[i] = _lib.OP_IDS[o]
         cfg.device, cfg.chunk = self.device, self.chunk
+        self.z_grad = bool(z_grad)
+        if zgrad_slabs is not None and (not self.z_grad or int(zgrad_slabs) < 1):
+            raise ValueError(f"zgrad_slabs needs z_grad=True and a count >= 1, got {zgrad_slabs}")
+        cfg.zgrad_slabs = (DEFAULT_ZGRAD_SLABS if zgrad_slabs is None else int(zgrad_slabs)) if self.z_grad else 0
         h = ctypes.c_void_p()
         r = self.lib.mi_gp_sparse_create(ctypes.byref(cfg), ctypes.byref(h))
         if r != 0:
@@ -91,8 +99,23 @@ class MiSparseGP:
             self.Z_t = torch.from_numpy(Z).to(self.dev)
             self.work_t = torch.empty(self.work_len, dtype=torch.float64, device=self.dev)
             torch.cuda.synchronize(self.dev)
+        self._bind()
+
+    def _bind(self):
+        self._factored_theta = None
         self._check(self.lib.mi_gp_sparse_set_data(self.h, self.X_t.data_ptr(), self.y_t.data_ptr(), self.n, self.Z_t.data_ptr(),
                                                    self.work_t.data_ptr(), self.work_len), "mi_gp_sparse_set_data")
+
+    def set_inducing(self, Z):
+        """Moves the inducing points: Z (m, d), converted inputs, is copied into the device buffer the library reads, the buffers
+        are bound again (which resets the library's factored state and allocates nothing) and the predictive's state is dropped."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        if Z.shape != (self.m, self.d) or not np.isfinite(Z).all():
+            raise ValueError(f"Z must be a finite ({self.m}, {self.d}) array")
+        with torch.cuda.device(self.dev):
+            self.Z_t.copy_(torch.from_numpy(Z))
+            torch.cuda.synchronize(self.dev)
+        self._bind()
 
     def _check(self, r, what):
         if r < 0:
@@ -115,9 +138,21 @@ class MiSparseGP:
 
     def lml_grad(self, theta):
         """(F, dF/dtheta) at natural-scale theta, the jitter slot 0; (-inf, zeros) on a bad pivot."""
+        F, grad = self._bound_grad(theta)
+        return F, grad[: self.ntheta].copy() if self.z_grad else grad
+
+    def lml_grad_z(self, theta):
+        """(F, dF/dtheta, dF/dZ as an (m, d) array) at natural-scale theta and the current inducing points (z_grad=True);
+        (-inf, zeros, zeros) on a bad pivot."""
+        if not self.z_grad:
+            raise ValueError("lml_grad_z needs MiSparseGP(..., z_grad=True)")
+        F, grad = self._bound_grad(theta)
+        return F, grad[: self.ntheta].copy(), grad[self.ntheta:].reshape(self.m, self.d).copy()
+
+    def _bound_grad(self, theta):
         theta, tp = self._theta(theta)
         out = ctypes.c_double()
-        grad = np.zeros(self.ntheta)
+        grad = np.zeros(self.ntheta + (self.m * self.d if self.z_grad else 0))
         self._factored_theta = None
         self.info = self._check(self.lib.mi_gp_sparse_bound_grad(self.h, tp, ctypes.byref(out),
                                                                  grad.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),

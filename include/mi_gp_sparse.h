@@ -29,6 +29,22 @@ extern "C" {
  * the m x m products on the GEMM).  Pass 2 (gradient only) rebuilds A_c^T chunk by chunk -- it is never stored --, forms T_c^T with
  * one GEMM and contracts it with dKuf/dtheta in one kernel; Kuu's term goes through the symmetric contraction of mi_gp_lml_grad
  * (include/mi_gp.h).
+ * The gradient by the inducing locations (zgrad_slabs >= 1).  Every base kernel is stationary ARD, so kdiag and the jitter on Kuu's
+ * diagonal do not depend on Z, and with k_c' = dk_c/dr2 and coef_c the fold's dK/dK_c
+ *   dF/dz_ud =   sum_i T_ui sum_c coef_c(i,u) kv_c k_c'(r2_c(i,u)) 2 (z_ud - x_id) / l_cd^2      (Kuf's term)
+ *            + 2 sum_v Guu_uv sum_c coef_c(u,v) kv_c k_c'(r2_c(u,v)) 2 (z_ud - z_vd) / l_cd^2    (Kuu's term)
+ * with r2 in the direct form: z_u = x_i gives a zero term exactly, despite the 1e-12 under Matern-3/2's and Exponential's root.
+ * Kuf's term is one more kernel per chunk of pass 2 on the weights the theta contraction reads (T_c^T and the rank-one part
+ * formed in the kernel): workgroup (ub, sl) of a grid (ceil(m / 64), slabs) owns 64 inducing points and walks the chunk's 64-row
+ * data blocks sl, sl + slabs, ...; each slab's m x d partial goes to scratch and a reduction adds the slabs in slab order, the
+ * first chunk overwriting dF/dZ and later chunks adding to it in chunk order.  slabs = min(row blocks of the chunk, zgrad_slabs,
+ * ceil(1024 / column blocks)), lowered until the slab scratch is at most 64 MB: a function of (chunk's points, m, d, zgrad_slabs)
+ * alone.  Kuu's term is the kernel of mi_gp_grad_x (include/mi_gp.h) over Z with the weight 2 Guu and a zero alpha.  No atomics;
+ * dF/dZ's bits depend on (Z, X, y, theta, chunk, slabs) and nothing else; another slab count regroups sums.  dF/dZ, Kuu's part and
+ * the slab scratch live in the object's own allocation (sized by the first mi_gp_sparse_set_data), not in the caller's work block.
+ * Z stays a borrowed buffer that every call reads afresh: a caller that overwrites it (an optimiser's step) may evaluate the bound
+ * at once, but must call mi_gp_sparse_set_data again before mi_gp_sparse_predict -- that resets the factored state and, after the
+ * first time, allocates nothing.
  * Every sum runs in a fixed order and nothing uses atomics: the same call in the same state returns the same bits.  Every element
  * a launch reads is written earlier in the same call: what the work block held before does not matter.  Another chunk size
  * regroups sums: agreement to rounding, not bit for bit.
@@ -44,6 +60,8 @@ typedef struct {
   int ops[MI_GP_MAX_KERN];
   int device;
   int chunk;               /* data points per pass step, a multiple of 128; 0: the default, 8192 */
+  int zgrad_slabs;         /* 0: no dF/dZ, every call bit for bit what it is without the field; s >= 1: mi_gp_sparse_bound_grad also
+                              writes dF/dZ, its kernel with at most s slabs per chunk (1: one slab walks every row block); < 0 refused */
 } mi_gp_sparse_config;
 /* validates and records the configuration; makes no HIP call (the stream and the object's small scratch come with the first
  * mi_gp_sparse_set_data).  With a null object the text of a refusal is behind mi_gp_sparse_last_error(NULL). */
@@ -59,7 +77,9 @@ MI_GP_API long mi_gp_sparse_work(int m, int chunk);
 MI_GP_API int mi_gp_sparse_set_data(mi_gp_sparse* s, const double* X_dev, const double* y_dev, int n, const double* Z_dev,
                                     double* work_dev, long work_len);
 /* *bound = F(theta) and grad_out[ntheta] = dF/dtheta (theta_host: nkern * d + 2 * nkern + 2 host doubles).  A null grad_out
- * means the value only: pass 1 and the algebra of F alone, and the same bits for F as with the gradient. */
+ * means the value only: pass 1 and the algebra of F alone, and the same bits for F as with the gradient.  With zgrad_slabs >= 1
+ * grad_out takes ntheta + m * d doubles: dF/dtheta as without it (the same bits), then dF/dZ row-major (m x d); a bad pivot
+ * zeroes both. */
 MI_GP_API int mi_gp_sparse_bound_grad(mi_gp_sparse* s, const double* theta_host, double* bound, double* grad_out);
 /* the state of the predictive at theta: L, LB, c and both sets of leaf inverses stay in the work block until the next
  * mi_gp_sparse_bound_grad, _factor or _set_data */
