@@ -1031,6 +1031,59 @@ class MiGP:
         low = np.tril(cov_t[:m, :m].cpu().numpy())
         return mu_t.cpu().numpy(), low + np.tril(low, -1).T
 
+    DESIGN_MAX_BATCH = 128  # points one design call selects (option 56)
+
+    def design(self, theta, Xcand, Xref=None, batch=1, noise=True):
+        """Greedy variance-reduction design at theta (options 56 / 57 of mi_gp_set_option): up to ``batch`` (1..128) of the
+        candidates ``Xcand`` (converted inputs, (Mc, d)), each the one whose observation lowers the latent posterior variance
+        averaged over the reference sample ``Xref`` (Mr, d) the most, given the ones chosen before it (integrated variance
+        reduction, ALC: Cohn 1996).  The gain of c is mean_r cov(c, r)^2 / v(c) with v(c) = var_latent(c) + jitter, plus gv with
+        ``noise`` -- exactly the drop of that average after ``append`` of one observation at c, whatever its value.
+        ``Xref=None``: the plain maximum-variance criterion, gain = var_latent.  Returns (indices, gains, gains0): the chosen
+        candidates in order (fewer than ``batch`` when no candidate is left or no gain is positive), their gains at the moment
+        of choice and the round-0 gains of all candidates (NaN where v is not a finite positive number).  No resident state
+        changes; both options are what they were afterwards."""
+        self._no_trend("design")
+        self._no_outputs("design")
+        if getattr(self, "_diag_t", None) is not None:
+            raise ValueError("design has no form under a per-point diagonal (set_diag is in force): set_diag(None) first")
+        batch = int(batch)
+        if not 1 <= batch <= self.DESIGN_MAX_BATCH:
+            raise ValueError(f"batch must lie in 1..{self.DESIGN_MAX_BATCH}")
+        Xcand = np.ascontiguousarray(Xcand, dtype=np.float64)
+        if Xcand.ndim != 2 or Xcand.shape[1] != self.d or Xcand.shape[0] < 1:
+            raise ValueError("Xcand must be (Mc, d) with Mc >= 1")
+        if Xref is None:
+            Xref = np.empty((0, self.d))
+        Xref = np.ascontiguousarray(Xref, dtype=np.float64)
+        if Xref.ndim != 2 or Xref.shape[1] != self.d:
+            raise ValueError("Xref must be (Mr, d)")
+        if not (np.isfinite(Xcand).all() and np.isfinite(Xref).all()):
+            raise ValueError("Xcand and Xref must be finite")
+        self._ensure_factored(theta)
+        mc, mr = Xcand.shape[0], Xref.shape[0]
+        mcp, mrp = self._padded(mc), self._padded(mr)
+        before = self.get_option(56), self.get_option(57)
+        with torch.cuda.device(self.dev):
+            if getattr(self, "_work", None) is None or self._work.shape[0] < mcp + mrp:
+                self._work = None
+                self._work = torch.empty((mcp + mrp, self.lda), dtype=torch.float64, device=self.dev)
+            xn = torch.from_numpy(np.concatenate([Xcand, Xref])).to(self.dev)
+            out_t = torch.empty(mc + 2 * batch + 1, dtype=torch.float64, device=self.dev)
+            g_t = torch.empty((mcp, mrp), dtype=torch.float64, device=self.dev) if mr else None
+            torch.cuda.synchronize(self.dev)
+            self.set_option(57, mr)
+            self.set_option(56, batch)
+            try:
+                self._check(self.lib.mi_gp_predict_cov(self.h, xn.data_ptr(), mc + mr, self._work.data_ptr(), self.lda, out_t.data_ptr(),
+                                                       g_t.data_ptr() if mr else None, mrp, 1 if noise else 0), "mi_gp_predict_cov")
+            finally:
+                self.set_option(56, before[0])
+                self.set_option(57, before[1])
+            o = out_t.cpu().numpy()
+        count = int(o[-1])
+        return o[mc : mc + count].astype(np.int64), o[mc + batch : mc + batch + count].copy(), o[:mc].copy()
+
     SAMPLE_JITTER_STEPS = (1e-12, 1e-10, 1e-8, 1e-6, 1e-4)  # extra diagonal (x kd) of sample_posterior's retries
 
     def sample_posterior(self, theta, Xnew, nsamples, seed=None, pred_noise=False, offset=None):

@@ -65,7 +65,7 @@ static void release_handle(mi_gp_handle* h) {
   free_scratch(h->one);
   free_scratch(h->batch);
   (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
-  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk, &h->multi_blk, &h->sweep_blk, &h->path_blk}) (void)hipFree(b->p);
+  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk, &h->multi_blk, &h->sweep_blk, &h->path_blk, &h->design_blk}) (void)hipFree(b->p);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -332,6 +332,33 @@ static int special_option(mi_gp_handle* h, int what, const int* set, int* get) {
         h->nfeat = *set;
       } else {
         *get = h->nfeat;
+      }
+      return 1;
+    case 56:  // the batch size of the DESIGN CALL mi_gp_predict_cov becomes (no resident state changes with it)
+      if (set) {
+        if (*set < 0 || *set > DESIGN_MAX_B) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 56 is 0 (the joint conditional) or a batch of 1 to %d points to select, "
+                   "got %d", DESIGN_MAX_B, *set);
+          return -1;
+        }
+        if (*set >= 1 && !design_select) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the design call (option 56 >= 1) is not part of this build");
+          return -1;
+        }
+        h->design_b = *set;
+      } else {
+        *get = h->design_b;
+      }
+      return 1;
+    case 57:  // the number of reference points of the design call (no resident state changes with it)
+      if (set) {
+        if (*set < 0) {
+          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 57 is a number of reference points >= 0, got %d", *set);
+          return -1;
+        }
+        h->design_nref = *set;
+      } else {
+        *get = h->design_nref;
       }
       return 1;
   }
@@ -841,6 +868,7 @@ extern "C" int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, dou
 // (the rest of that row is strict upper triangle: unspecified).
 extern "C" int mi_gp_predict_cov(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw, double* mean_dev,
                                  double* cov_dev, long ldc, int pred_noise) {
+  if (h && h->design_b) return design_select(h, Xnew_dev, m, work_dev, ldw, mean_dev, cov_dev, ldc, pred_noise);  // option 56 >= 1
   const long mp = m > 0 ? (m + 127) / 128 * 128 : 0;
   const char* why = (!Xnew_dev || !work_dev || !mean_dev || !cov_dev) ? "null buffer"
                   : m <= 0 ? "m must be >= 1"

@@ -151,6 +151,12 @@ struct mi_gp_handle {
   CapBlock path_blk;       // the path sweep's scratch: the points, frequencies and weights staged for the kernel, the partial sums of
   size_t path_len;         // one pass and the conditioning's two 128-row blocks (paths_f64.hip: path_scratch_len; path_len doubles,
                            // grown by a call that needs more; holds nothing between calls)
+  int design_b;            // option 56: 0 (default) mi_gp_predict_cov is the joint conditional; b = 1..128: it is the DESIGN CALL that
+                           // selects up to b of the candidates in Xnew_dev (design_select(), api_design.hip)
+  int design_nref;         // option 57: Mr, the reference points behind the candidates in Xnew_dev (0: the maximum-variance criterion;
+                           // read only under option 56 >= 1)
+  CapBlock design_blk;     // the design call's scratch (design_f64.hip: design_scratch_len; design_len doubles, grown by a call that
+  size_t design_len;       // needs more; holds nothing between calls)
   char err[256];
 };
 
@@ -355,6 +361,11 @@ int mean_sweep(mi_gp_handle* h, const double* Xnew_dev, int m, double* mean_dev,
 // the file option 54 >= 1 is refused.  0 or a C-ABI error code; every refusal comes before any HIP call
 int path_sweep(mi_gp_handle* h, const double* Xnew_dev, int m, double* block_dev, long ldw, double* mean_dev, int condition,
                double* dmean_dev) __attribute__((weak));
+
+// api_design.hip: mi_gp_predict_cov under option 56 = b >= 1 (include/mi_gp.h has the contract).  Weak like mean_sweep: without the
+// file option 56 >= 1 is refused.  0 or a C-ABI error code; every refusal comes before any HIP call
+int design_select(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw, double* out_dev, double* G_dev, long ldc,
+                  int pred_noise) __attribute__((weak));
 
 // api_gp.hip
 hipError_t trsm_rec(mi_gp_handle* h, const Eval& E, double* Bw, long ldw, int mp, int c0, int w);  // X L^T = B in place

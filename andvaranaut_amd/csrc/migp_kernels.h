@@ -444,6 +444,30 @@ hipError_t launch_path_residual(const double* y, const double* V, long ldw, int 
 // V[j * ldw + s] = R1[s * ldr + j] for s < S, j < n
 hipError_t launch_path_scatter(double* V, long ldw, int n, int S, const PathScratch& t, hipStream_t stream);
 
+// ---------------------------------------------------------------- design_f64.hip (option 56: the design call, api_design.hip)
+constexpr int DESIGN_MAX_B = 128;  // points one call selects at most
+// The handle-owned scratch for Mc candidates and b steps (mcp = Mc rounded up to 128, the row stride of hist)
+struct DesignScratch {
+  double *v, *rowsq;      // [mcp] v(c) = var_latent(c) + noise, the rows' sums of squares of G
+  double* mean;           // [mcp] the row reduction's means (written, never read)
+  double* hist;           // [b][mcp] the candidate columns g_s = cov_s(C, c*_s) of the steps so far, the current one included
+  double* vs;             // [128] v* of the steps so far
+  int* alive;             // [mcp] 1 until a candidate is chosen
+  int* piv;               // the step's pivot, -1 once the selection has stopped
+  long mcp;
+};
+size_t design_scratch_len(int Mc, int b);
+DesignScratch design_scratch(double* base, int Mc, int b);
+// rowsq[c] = sum_{r < Mr} G[c][r]^2 for c < Mc, each sum in a fixed order
+hipError_t launch_design_rowsq(const double* G, long ldc, int Mc, int Mr, double* rowsq, hipStream_t stream);
+// Step `step` of the greedy loop, three launches: the pick (score, arg-max with ties to the lowest index, the records in out), the
+// candidate column g = cov_t(C, c*) from the rows A (ldw apart, n entries each) and the fused pass over G (Mc x Mr, ldc apart;
+// Mr = 0: the plain maximum-variance criterion, G is not touched).  noise = v - var_latent.  out: [Mc] round-0 gains, [b] chosen
+// indices as doubles (-1 beyond the count), [b] their gains, the count; step 0 initialises it
+hipError_t launch_design_step(const KernSpec& spec, const double* theta, const double* Xc, int Mc, int Mr, int b, int step,
+                              const double* A, long ldw, int n, double* G, long ldc, double noise, const DesignScratch& t, double* out,
+                              hipStream_t stream);
+
 // ---------------------------------------------------------------- sparse_f64.hip (the sparse inducing-point bound, api_sparse.hip)
 int sparse_contract_blocks(int cnt, int m);  // 64 x 64 tiles of the cnt x m cross-covariance
 // acc[ntheta] (first: =, else +=) sum_{i < cnt, u < m} (T[i][u] + y[i] tv[u]) dK(x_i, z_u)/dtheta (natural parameters, C-ABI

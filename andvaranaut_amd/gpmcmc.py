@@ -225,6 +225,98 @@ class GPMCMC(ConsumersMixin):
         self.__reconvert()
         self.train = self.test = None
 
+    def _design_ready(self, what):
+        """Raised, before any device call, by the adaptive sampler where it has no form or no fit to work from."""
+        self._no_sparse(what)
+        self._no_trend(what)
+        self._no_all_outputs(what)
+        if getattr(self, "hypers", None) is None or self.m is None:
+            raise Exception(f"Error: fit the GP before {what}")
+
+    def propose_samples(self, nsamps, criterion="alc", ncand=None, nref=None, seed=None, jitter=1e-6):
+        """Where to run the target next: ``nsamps`` points chosen greedily among ``ncand`` Latin-hypercube candidates of the
+        priors (default max(1024, 16 nsamps)) at the fitted hyper-parameters.  ``criterion="alc"``: each point is the candidate
+        whose observation lowers the latent posterior variance, averaged over ``nref`` (default 512) further Latin-hypercube
+        points, the most, given the points chosen before it (integrated variance reduction: Cohn 1996, Gramacy & Lee 2009).
+        ``criterion="var"``: the candidate of the largest posterior variance.  Neither reads an output, so the whole set is
+        chosen before the target runs once.  Candidates and reference points come from ``latin_sample`` under ``seed`` and
+        ``seed + 1``, pass the constraints as ``sample``'s points do and are converted with the current ``xconrevs``.  Points are
+        chosen in batches of at most 128 (MiGP.design); between batches the chosen ones are appended to the resident
+        factorisation with placeholder outputs, and afterwards the handle is rebuilt from the data, so the object is left as it
+        was found.  Returns (x, gains): the raw-space points (k, nx), k <= nsamps, and their gains in converted output units."""
+        what = "propose_samples"
+        self._design_ready(what)
+        if not isinstance(nsamps, (int, np.integer)) or isinstance(nsamps, bool) or nsamps < 1:
+            raise Exception("Error: nsamps argument must be an integer > 0")
+        if criterion not in ("alc", "var"):
+            raise ValueError(f"criterion must be 'alc' or 'var' (got {criterion!r})")
+        ncand = max(1024, 16 * int(nsamps)) if ncand is None else int(ncand)
+        nref = 512 if nref is None else int(nref)
+        if ncand < 1 or (criterion == "alc" and nref < 1):
+            raise ValueError("ncand and nref must be >= 1")
+        xcand = latin_sample(self.priors, ncand, seed)
+        xref = latin_sample(self.priors, nref, None if seed is None else seed + 1) if criterion == "alc" else None
+        if self.constraints is not None:
+            xcand = self.__check_constraints(xcand)
+            xref = self.__check_constraints(xref) if xref is not None else None
+        if len(xcand) < 1 or (xref is not None and len(xref) < 1):
+            raise ValueError("the constraints leave no candidate or no reference point")
+        ccand, _ = self._converted_x(xcand, True)
+        cref = self._converted_x(xref, True)[0] if xref is not None else None
+        gp = self._ensure_gp()
+        theta = self._theta_from_hypers(self.hypers, jitter)
+        left = np.arange(len(xcand))
+        chosen, gains, appended = [], [], False
+        try:
+            while len(chosen) < nsamps and len(left) > 0:
+                k = min(MiGP.DESIGN_MAX_BATCH, int(nsamps) - len(chosen))
+                idx, gn, _ = gp.design(theta, ccand[left], cref, batch=k)
+                chosen.extend(left[idx])
+                gains.extend(gn)
+                if len(idx) < k or len(chosen) >= nsamps:
+                    break
+                gp.append(ccand[left[idx]], np.zeros(len(idx)))  # (placeholders: the criterion never reads an output)
+                appended = True
+                left = np.delete(left, idx)
+        finally:
+            if appended:  # the handle holds the placeholders: the next use builds it again from the data
+                self.__release()
+        return xcand[np.array(chosen, dtype=np.int64)], np.array(gains)
+
+    def adaptive_sample(self, nsamps, batch=None, refit=True, **propose_kwargs):
+        """Sequential design: propose ``batch`` points (default: all ``nsamps`` at once) with ``propose_samples(**propose_kwargs)``,
+        run the target there, extend the data exactly as ``sample`` does, fit again with the last fit's arguments
+        (``refit=False``: keep the hyper-parameters and only rebuild the factorisation on the extended data), and repeat until
+        ``nsamps`` points have been proposed.  A ``seed`` among the keyword arguments advances by 2 per round."""
+        self._design_ready("adaptive_sample")
+        if not isinstance(nsamps, (int, np.integer)) or isinstance(nsamps, bool) or nsamps < 1:
+            raise Exception("Error: nsamps argument must be an integer > 0")
+        batch = int(nsamps) if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        seed = propose_kwargs.pop("seed", None)
+        done, rnd = 0, 0
+        while done < nsamps:
+            k = min(batch, int(nsamps) - done)
+            xs, _ = self.propose_samples(k, seed=None if seed is None else seed + 2 * rnd, **propose_kwargs)
+            if len(xs) == 0:
+                break
+            done += len(xs)
+            rnd += 1
+            if self.verbose:
+                print(f"Evaluating {len(xs)} adaptively chosen samples...")
+            xs, ys = self.__evaluate(xs, self.target)
+            self.x = np.r_[self.x, xs]
+            self.y = np.r_[self.y, ys]
+            self.nsamp = len(self.x)
+            self.__mean_eval()
+            self.__reconvert()
+            self.train = self.test = None
+            if refit and getattr(self, "_fit_args", None) is not None:
+                self.fit(**self._fit_args)
+            else:
+                self.__release()  # (same hyper-parameters: _ensure_gp builds the handle on the extended data)
+
     def set_data(self, x, y):
         """gpmcmc.py:122-137 + lhc.py:113-131."""
         if not isinstance(x, np.ndarray) or len(x.shape) != 2 or x.dtype != "float64" or x.shape[1] != self.nx:
@@ -708,6 +800,10 @@ class GPMCMC(ConsumersMixin):
                                                         output_cov=output_cov, inducing=Z, optimize_inducing=optimize_inducing,
                                                         **kwargs)
         self.inducing = data["inducing"] if optimize_inducing else Z
+        # what adaptive_sample(refit=True) fits again with
+        self._fit_args = dict(method=method, iwgp=iwgp, cwgp=cwgp, jitter=jitter, truncate=truncate, restarts=restarts, objective=objective,
+                              nfolds=nfolds, fold_seed=fold_seed, trend=trend, outputs=outputs, output_cov=output_cov, inducing=inducing,
+                              inducing_seed=inducing_seed, optimize_inducing=optimize_inducing, **kwargs)
         self.trend = trend
         self.outputs = outputs
         self.output_cov = output_cov

@@ -652,6 +652,45 @@ MI_GP_API int mi_gp_get_option(mi_gp_handle* h, int what, int* value);
  *      text says "not part of this build").  Setting either changes no resident state; mi_gp_get_option reads them back.
  *      Out of scope: d > 32; a trend or several outputs; batched and sharded forms; draws of noisy observations (add the noise
  *      on the host); variances. */
+/* Option 56 (not a tuning knob) the DESIGN CALL of mi_gp_predict_cov, a greedy variance-reduction design (integrated variance
+ *      reduction, ALC / IMSE: Cohn 1996, Gramacy & Lee 2009): 0 (default) the call is the joint conditional, bit for bit and launch
+ *      for launch; b = 1..128 the call selects up to b of the candidate points it is given, each the one whose observation lowers
+ *      the latent posterior variance averaged over a reference sample R the most, given the ones chosen before it:
+ *          gain(c) = (1 / Mr) sum_r cov(c, r)^2 / v(c),      v(c) = var_latent(c) + jitter (+ sqrt(gv)^2 with pred_noise = 1)
+ *      with cov and var_latent the posterior's at the factored theta.  gain(c) is exactly the drop of mean_r var_latent(r) when
+ *      one observation at c is appended (mi_gp_append, pred_noise = 1), whatever its value: a batch is chosen before the target
+ *      runs once.  Option 57 is Mr, the number of reference points, >= 0, read only while option 56 >= 1; Mr = 0 is the plain
+ *      maximum-variance criterion, gain(c) = var_latent(c), with no reference set.
+ *      Under option 56 = b: Xnew_dev is (Mc + Mr) x d, the Mc >= 1 candidates and then the Mr reference points, m = Mc + Mr.
+ *      work_dev receives the rows A = L^-1 K(X, .) of the candidates and, from row ceil(Mc/128)*128 on, those of the reference
+ *      points: ceil(Mc/128)*128 + ceil(Mr/128)*128 rows, ldw as for mi_gp_predict.  cov_dev receives G, the running cov(C, R):
+ *      ceil(Mc/128)*128 rows ldc apart, ldc even and >= ceil(Mr/128)*128; with Mr = 0 it is not touched and may be NULL.
+ *      mean_dev receives Mc + 2 b + 1 doubles:
+ *          [0, Mc)              the round-0 gains of all candidates (NaN where v is not a finite positive number)
+ *          [Mc, Mc + b)         the chosen candidates' indices as doubles, in order, -1 beyond the count
+ *          [Mc + b, Mc + 2 b)   their gains at the moment of choice, 0 beyond the count
+ *          [Mc + 2 b]           the count: fewer than b when no candidate is left or the best score is not > 0
+ *      Setup, from the launchers of mi_gp_predict and mi_gp_predict_cov: the cross-assembly of both point sets and one blocked
+ *      solve over their rows, the assembly of K(C, R) into cov_dev, ONE GEMM G -= A_C A_R^T (k = padded n), v from mi_gp_predict's
+ *      row reduction and the rows' sums of squares of G.  Then b steps on the handle's stream without a host synchronisation, the
+ *      pivot index in device memory: (1) score(c) = sum_r G[c][r]^2 / (Mr v[c]) and its arg-max over the alive candidates with a
+ *      finite v > 0, ties to the lowest index; (2) the candidate column g = cov_t(C, c*) = k(C, c*) - A_C a_c* less the earlier
+ *      pivots' contributions g_s g_s[c*] / v*_s, one pass over the candidates' rows of A; (3) one fused pass over the alive rows,
+ *      G[c][:] -= (g[c] / v*) G[c*][:] with the row's new sum of squares, and v[c] -= g[c]^2 / v*.  The chosen candidate is dead
+ *      from step (1) on and the pass skips dead rows, so the pivot row every workgroup reads is written by none.
+ *      No atomics; every row sum is lane-strided partial sums (a lane takes pairs of elements) and mi_gp_predict's wave tree, so a
+ *      row's bits do not depend on the grid; the same call in the same state returns the same bits; every element a launch reads is written earlier in the call
+ *      (NaN in work_dev, cov_dev or the handle's scratch changes nothing).  The handle owns a scratch of (4 + b) ceil(Mc/128)*128
+ *      + 130 doubles -- v, the row sums, the candidate columns of the steps so far, v* per step, the alive mask and the pivot --
+ *      allocated by the first call, grown by a call that needs more, freed by mi_gp_destroy; it holds nothing between calls.
+ *      The call changes no handle state, returns with the stream synchronised and works after mi_gp_append.
+ *      Every refusal returns -1 before any HIP call with a text that names option 56: no factorisation, a per-point diagonal
+ *      (mi_gp_set_diag), option 50 != 0 or option 51 >= 2, m < Mr + 1, ldw odd or < padded n, ldc odd or too small, a NULL buffer.
+ *      Values outside 0..128 (option 56) and below 0 (option 57) return -1 with a text that names the option, and so does option
+ *      56 >= 1 in a build without the design call (the text says "not part of this build").  Setting either changes no resident
+ *      state; mi_gp_get_option reads them back.
+ *      Out of scope: continuous refinement of a chosen point; a trend, several outputs, a per-point diagonal or a sparse fit;
+ *      batched and sharded handles; criteria that read y. */
 
 /* profiling: level 0 none, 1 per-phase HIP events, 2 additionally per-GEMM-launch HIP events */
 MI_GP_API int mi_gp_set_profiling(mi_gp_handle* h, int level);
