@@ -2,6 +2,7 @@
 
 Mirrors what the reference keeps inside its PyMC model object ``m``/``gp`` (gpmcmc.py:178,401):
 the training inputs, the kernel structure, and a way to evaluate logp / dlogp / the conditional."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -285,12 +286,8 @@ class MiGP:
     def loo_grad(self, theta):
         """(L_LOO, dL_LOO/dtheta) at natural-scale theta, whatever objective is set (it is the same afterwards); (-inf, zeros)
         if K is not positive definite or a diagonal entry of K^-1 is not positive (``info``)."""
-        before = self.get_option(48)
-        self.set_option(48, 1)
-        try:
+        with self._options({48: 1}):
             return self.lml_grad(theta)
-        finally:
-            self.set_option(48, before)
 
     def set_cv_block(self, b):
         """The fold size of the objective "loo" (option 49 of mi_gp_set_option): 1, leave-one-out, or 2..128, the leave-block-out
@@ -302,14 +299,8 @@ class MiGP:
         """(L_CV, dL_CV/dtheta) at natural-scale theta over contiguous folds of ``block`` points, whatever objective and fold size
         are set (they are the same afterwards); (-inf, zeros) if K or a fold's block of K^-1 is not positive definite (``info``:
         the 1-based index of the point at the bad pivot)."""
-        before = self.get_option(48), self.get_option(49)
-        self.set_option(49, int(block))
-        try:
-            self.set_option(48, 1)
+        with self._options({49: int(block), 48: 1}):
             return self.lml_grad(theta)
-        finally:
-            self.set_option(48, before[0])
-            self.set_option(49, before[1])
 
     # ------------------------------------------------------------------ batched evaluation
     def _ensure_batch(self, k, need_grad):
@@ -971,13 +962,9 @@ class MiGP:
         with torch.cuda.device(self.dev):
             block = torch.from_numpy(paths.pack_block(omega, b, W, E, ldw)).to(self.dev)
             torch.cuda.synchronize(self.dev)
-            self.set_option(55, F)
-            self.set_option(54, S)
-            try:  # the conditioning call: m = 0, pred_noise read as `condition`
+            with self._options({55: F, 54: S}, leave={55: F, 54: 0}):  # the conditioning call: m = 0, pred_noise read as `condition`
                 self._check(self.lib.mi_gp_predict_grad(self.h, None, 0, block.data_ptr(), ldw, None, None, 1, None, None),
                             "mi_gp_predict_grad")
-            finally:
-                self.set_option(54, 0)
         return paths.PathDraw(self, block, S, F, ldw, seed, self._path_serial)
 
     # ---------------------------------------------------------------- joint conditional and posterior draws
@@ -1063,7 +1050,6 @@ class MiGP:
         self._ensure_factored(theta)
         mc, mr = Xcand.shape[0], Xref.shape[0]
         mcp, mrp = self._padded(mc), self._padded(mr)
-        before = self.get_option(56), self.get_option(57)
         with torch.cuda.device(self.dev):
             if getattr(self, "_work", None) is None or self._work.shape[0] < mcp + mrp:
                 self._work = None
@@ -1072,14 +1058,9 @@ class MiGP:
             out_t = torch.empty(mc + 2 * batch + 1, dtype=torch.float64, device=self.dev)
             g_t = torch.empty((mcp, mrp), dtype=torch.float64, device=self.dev) if mr else None
             torch.cuda.synchronize(self.dev)
-            self.set_option(57, mr)
-            self.set_option(56, batch)
-            try:
+            with self._options({57: mr, 56: batch}):
                 self._check(self.lib.mi_gp_predict_cov(self.h, xn.data_ptr(), mc + mr, self._work.data_ptr(), self.lda, out_t.data_ptr(),
                                                        g_t.data_ptr() if mr else None, mrp, 1 if noise else 0), "mi_gp_predict_cov")
-            finally:
-                self.set_option(56, before[0])
-                self.set_option(57, before[1])
             o = out_t.cpu().numpy()
         count = int(o[-1])
         return o[mc : mc + count].astype(np.int64), o[mc + batch : mc + batch + count].copy(), o[:mc].copy()
@@ -1152,6 +1133,22 @@ class MiGP:
             self._outcov = int(value)
             self._factored_ok = False
             self._u_theta_ok = False
+
+    @contextlib.contextmanager
+    def _options(self, values, leave=None):
+        """Options set for the length of a ``with`` block: ``values`` {id: value} are set in their order; on the way out, in
+        reverse order, every id that was set gets back the value it had on entry, or the one ``leave`` {id: value} names for it.
+        About 1 us of Python per use: mean_sweep and PathDraw.evaluate, whose calls take tens of us, set their option inline."""
+        restore = []
+        try:
+            for what, value in values.items():
+                old = leave[what] if leave and what in leave else self.get_option(what)
+                self.set_option(what, value)
+                restore.append((what, old))  # (a refused value changed nothing: nothing to put back)
+            yield
+        finally:
+            for what, old in reversed(restore):
+                self.set_option(what, old)
 
     def get_option(self, what, default=None):
         """Current value of a knob on this handle, the library's own defaults included (mi_gp_get_option; 40: 1 once the handle

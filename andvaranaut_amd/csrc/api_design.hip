@@ -22,14 +22,8 @@ int design_select(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_d
   if (Mr > 0 && !G_dev) return design_refuse(h, "null buffer (cov_dev is required with option 57 >= 1)");
   if (Mr > 0 && (ldc < Mrp || (ldc & 1))) return design_refuse(h, "ldc must be even and >= ceil(Mr/128)*128");
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  const size_t need = design_scratch_len(Mc, b);
-  if (!h->design_blk.p || h->design_len < need) {
-    HCK(hipStreamSynchronize(h->stream), "stream sync");
-    h->design_len = 0;
-    HCK(resize_block(h->design_blk, h->cap, need), "design scratch");
-    h->design_len = need;
-  }
-  const DesignScratch t = design_scratch(h->design_blk.p, Mc, b);
+  if (int r = ensure_block(h, BLK_DESIGN, design_scratch_len(Mc, b), "design scratch")) return r;
+  const DesignScratch t = design_scratch(h->blocks[BLK_DESIGN].p, Mc, b);
   const hipStream_t st = h->stream;
   const Eval E = one_eval(h);
   const double* theta = h->one.theta_dev;

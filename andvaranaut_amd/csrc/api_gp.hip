@@ -65,7 +65,7 @@ static void release_handle(mi_gp_handle* h) {
   free_scratch(h->one);
   free_scratch(h->batch);
   (void)hipFree(h->sig_dev); (void)hipFree(h->gxs_dev); (void)hipFree(h->app_stats_dev);
-  for (CapBlock* b : {&h->loo, &h->cv, &h->trend_blk, &h->multi_blk, &h->sweep_blk, &h->path_blk, &h->design_blk}) (void)hipFree(b->p);
+  for (CapBlock& b : h->blocks) (void)hipFree(b.p);
   for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (auto& ev : h->gemm_ev) (void)hipEventDestroy(ev);
   for (auto& ev : h->ev_pool) (void)hipEventDestroy(ev);
@@ -103,7 +103,8 @@ static hipError_t probe_dispatch(mi_gp_handle* h) {
 
 // ---------------------------------------------------------------- tuning options (include/mi_gp.h lists them)
 // The plain options: a member, its default and its clamp (flag: normalised to 0 / 1).  mi_gp_create takes the defaults from
-// here, mi_gp_set_option and mi_gp_get_option look the id up; the options that do more than that follow in special_option().
+// here, mi_gp_set_option and mi_gp_get_option look the id up; the modes follow in mode_options, the few options that do more
+// than either in special_option().
 constexpr int ANY_LO = -2147483647 - 1, ANY_HI = 2147483647;
 struct PlainOption {
   int id;
@@ -139,10 +140,86 @@ static const PlainOption plain_options[] = {
     {46, &mi_gp_handle::rl_whole, 0, ANY_HI, false, 31},
 };
 
-static const PlainOption* find_option(int what) {
-  for (const PlainOption& o : plain_options)
+// The mode options (48-57): what an entry point computes.  Where a knob clamps, a mode refuses: a value outside lo..hi (or no
+// multiple of step), a value other than the default whose code is not linked (the weak functions of gp_handle.h: the host-only
+// schedule-trace program links api_gp.hip without them), and whatever `refuse` adds.  A new mode is a row here, a BlockId for its
+// scratch (gp_handle.h) and its dispatch in the entry point it changes.  The texts are the C-ABI's: callers and tests read them.
+enum ModeEffect {
+  MODE_KEEPS,          // no resident state changes with the option
+  MODE_ENDS_RESIDENT,  // a change ends the resident state as mi_gp_set_data does: the factor belongs to the model it was computed under
+  MODE_ENDS_RESIDENT_DROPS_MULTI,  // ... and the outputs' scratch is laid out for the option's value: its next use allocates it again
+};
+struct ModeOption {
+  int id;
+  int mi_gp_handle::*member;
+  int def;                // the default, and the value that needs nothing linked: the mode is off
+  int lo, hi, step;
+  const char* legal;      // "mi_gp_set_option: option <id> is <legal>, got <value>"
+  bool (*built)();        // are the mode's functions linked (nullptr: it has none)
+  const char* not_built;  // the refusal when they are not: snprintf's format with the value as its one argument, so at most one
+                          // conversion, a %d
+  bool (*refuse)(mi_gp_handle*, int);  // nullptr, or a further check of the value: true with the text set
+  ModeEffect effect;
+};
+static bool linear_trend_too_wide(mi_gp_handle* h, int value) {
+  if (value != 2 || h->cfg.d <= 127) return false;
+  snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the linear trend (option 50 = 2) needs d <= 127, got %d", h->cfg.d);
+  return true;
+}
+static bool loo_built() { return loo_objective; }
+static bool trend_built() { return trend_objective && trend_factor && trend_predict_reduce; }
+static bool multi_built() { return multi_objective && multi_factor && multi_predict_reduce; }
+static bool sweep_built() { return mean_sweep; }
+static bool paths_built() { return path_sweep; }
+static bool design_built() { return design_select; }
+static_assert(DESIGN_MAX_B == 128, "the text of option 56 names the largest batch");
+static const ModeOption mode_options[] = {
+    {48, &mi_gp_handle::objective, 0, 0, 1, 1, "0 (log marginal likelihood) or 1 (leave-one-out)", loo_built,
+     "mi_gp_set_option: the leave-one-out objective (option 48 = 1) is not part of this build", nullptr, MODE_KEEPS},
+    {49, &mi_gp_handle::cv_block, 1, 1, 128, 1, "a fold size of 1 (leave-one-out) to 128 points", loo_built,
+     "mi_gp_set_option: the k-fold objective (option 49 > 1) is not part of this build", nullptr, MODE_KEEPS},
+    {50, &mi_gp_handle::trend, 0, 0, 2, 1, "0 (no trend), 1 (constant) or 2 (linear)", trend_built,
+     "mi_gp_set_option: the trend (option 50 = %d) is not part of this build", linear_trend_too_wide, MODE_ENDS_RESIDENT},
+    {51, &mi_gp_handle::nout, 1, 1, 128, 1, "a number of outputs of 1 (the single y) to 128", multi_built,
+     "mi_gp_set_option: several outputs (option 51 = %d) are not part of this build", nullptr, MODE_ENDS_RESIDENT},
+    {52, &mi_gp_handle::outcov, 0, 0, 1, 1, "0 (independent outputs) or 1 (the between-output covariance integrated out)", multi_built,
+     "mi_gp_set_option: the between-output covariance (option 52 = %d) is not part of this build", nullptr, MODE_ENDS_RESIDENT_DROPS_MULTI},
+    {53, &mi_gp_handle::sweep, 0, 0, 1, 1, "0 (the conditional and its gradients) or 1 (the mean sweep)", sweep_built,
+     "mi_gp_set_option: the mean sweep (option 53 = 1) is not part of this build", nullptr, MODE_KEEPS},
+    {54, &mi_gp_handle::npaths, 0, 0, 128, 1, "0 (no paths) or a number of sample paths of 1 to 128", paths_built,
+     "mi_gp_set_option: the path sweep (option 54 >= 1) is not part of this build", nullptr, MODE_KEEPS},
+    {55, &mi_gp_handle::nfeat, 1024, 16, 65536, 16, "a number of features, a multiple of 16 in 16..65536", nullptr, nullptr, nullptr, MODE_KEEPS},
+    {56, &mi_gp_handle::design_b, 0, 0, DESIGN_MAX_B, 1, "0 (the joint conditional) or a batch of 1 to 128 points to select",
+     design_built, "mi_gp_set_option: the design call (option 56 >= 1) is not part of this build", nullptr, MODE_KEEPS},
+    {57, &mi_gp_handle::design_nref, 0, 0, ANY_HI, 1, "a number of reference points >= 0", nullptr, nullptr, nullptr, MODE_KEEPS},
+};
+
+template <class Row, size_t N>
+static const Row* find_option(const Row (&rows)[N], int what) {
+  for (const Row& o : rows)
     if (o.id == what) return &o;
   return nullptr;
+}
+
+// 0, or -1 with the refusal's text
+static int set_mode_option(mi_gp_handle* h, const ModeOption& o, int value) {
+  if (value < o.lo || value > o.hi || value % o.step != 0) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option %d is %s, got %d", o.id, o.legal, value);
+    return -1;
+  }
+  if (o.refuse && o.refuse(h, value)) return -1;
+  if (value != o.def && o.built && !o.built()) {
+    snprintf(h->err, sizeof(h->err), o.not_built, value);
+    return -1;
+  }
+  if (value == h->*o.member) return 0;
+  h->*o.member = value;
+  if (o.effect != MODE_KEEPS) drop_resident(h);
+  if (o.effect == MODE_ENDS_RESIDENT_DROPS_MULTI && h->blocks[BLK_MULTI].p) {  // (every entry point returns with the stream synchronised)
+    (void)hipSetDevice(h->device);
+    drop_block(h->blocks[BLK_MULTI]);
+  }
+  return 0;
 }
 
 // defaults of the options below (2: mi_gp_config's panel_tiles)
@@ -150,9 +227,6 @@ static void special_defaults(mi_gp_handle* h) {
   h->w_thr[0] = 1 << 20; h->w_thr[1] = 0; h->w_thr[2] = 0;
   h->use_smo = 2;  // (0 where the driver lacks stream memory operations: mi_gp_create)
   h->spin_us = 2000;
-  h->cv_block = 1;
-  h->nout = 1;
-  h->nfeat = 1024;
 }
 
 // The options with behaviour beyond a clamp; `set` (or nullptr) is the new value, `get` (or nullptr) receives the current one.
@@ -195,172 +269,6 @@ static int special_option(mi_gp_handle* h, int what, const int* set, int* get) {
       if (set) { h->spin_us = *set < 0 ? 0 : *set; h->spin_backoff = 0; }
       else *get = h->spin_us;
       return 1;
-    case 48:  // what mi_gp_lml_grad returns (no resident state changes with it)
-      if (set) {
-        if (*set != 0 && *set != 1) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 48 is 0 (log marginal likelihood) or 1 (leave-one-out), got %d", *set);
-          return -1;
-        }
-        if (*set == 1 && !loo_objective) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the leave-one-out objective (option 48 = 1) is not part of this build");
-          return -1;
-        }
-        h->objective = *set;
-      } else {
-        *get = h->objective;
-      }
-      return 1;
-    case 49:  // the fold size of the objective under option 48 = 1 (no resident state changes with it)
-      if (set) {
-        if (*set < 1 || *set > 128) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 49 is a fold size of 1 (leave-one-out) to 128 points, got %d", *set);
-          return -1;
-        }
-        if (*set != 1 && !loo_objective) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the k-fold objective (option 49 > 1) is not part of this build");
-          return -1;
-        }
-        h->cv_block = *set;
-      } else {
-        *get = h->cv_block;
-      }
-      return 1;
-    case 50:  // the TREND (a change ends the resident state as mi_gp_set_data does)
-      if (set) {
-        if (*set < 0 || *set > 2) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 50 is 0 (no trend), 1 (constant) or 2 (linear), got %d", *set);
-          return -1;
-        }
-        if (*set == 2 && h->cfg.d > 127) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the linear trend (option 50 = 2) needs d <= 127, got %d", h->cfg.d);
-          return -1;
-        }
-        if (*set != 0 && !(trend_objective && trend_factor && trend_predict_reduce)) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the trend (option 50 = %d) is not part of this build", *set);
-          return -1;
-        }
-        if (*set != h->trend) {
-          h->trend = *set;
-          h->factored = h->have_kinv = h->have_u = false;
-          h->b_cond_k = 0;
-        }
-      } else {
-        *get = h->trend;
-      }
-      return 1;
-    case 51:  // the number of OUTPUTS (a change ends the resident state as mi_gp_set_data does)
-      if (set) {
-        if (*set < 1 || *set > 128) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 51 is a number of outputs of 1 (the single y) to 128, got %d", *set);
-          return -1;
-        }
-        if (*set != 1 && !(multi_objective && multi_factor && multi_predict_reduce)) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: several outputs (option 51 = %d) are not part of this build", *set);
-          return -1;
-        }
-        if (*set != h->nout) {
-          h->nout = *set;
-          h->factored = h->have_kinv = h->have_u = false;
-          h->b_cond_k = 0;
-        }
-      } else {
-        *get = h->nout;
-      }
-      return 1;
-    case 52:  // the covariance BETWEEN the outputs (a change ends the resident state as mi_gp_set_data does)
-      if (set) {
-        if (*set != 0 && *set != 1) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 52 is 0 (independent outputs) or 1 (the between-output covariance "
-                   "integrated out), got %d", *set);
-          return -1;
-        }
-        if (*set != 0 && !(multi_objective && multi_factor && multi_predict_reduce)) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the between-output covariance (option 52 = %d) is not part of this build", *set);
-          return -1;
-        }
-        if (*set != h->outcov) {
-          h->outcov = *set;
-          h->factored = h->have_kinv = h->have_u = false;
-          h->b_cond_k = 0;
-          // the outputs' scratch is laid out for the option's value: its next use allocates it again (every entry point returns
-          // with the stream synchronised)
-          if (h->multi_blk.p) {
-            (void)hipSetDevice(h->device);
-            (void)resize_block(h->multi_blk, 0, 0);
-          }
-        }
-      } else {
-        *get = h->outcov;
-      }
-      return 1;
-    case 53:  // what mi_gp_predict_grad is (no resident state changes with it)
-      if (set) {
-        if (*set != 0 && *set != 1) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 53 is 0 (the conditional and its gradients) or 1 (the mean sweep), got %d", *set);
-          return -1;
-        }
-        if (*set == 1 && !mean_sweep) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the mean sweep (option 53 = 1) is not part of this build");
-          return -1;
-        }
-        h->sweep = *set;
-      } else {
-        *get = h->sweep;
-      }
-      return 1;
-    case 54:  // the number of sample PATHS mi_gp_predict_grad sweeps (no resident state changes with it)
-      if (set) {
-        if (*set < 0 || *set > 128) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 54 is 0 (no paths) or a number of sample paths of 1 to 128, got %d", *set);
-          return -1;
-        }
-        if (*set >= 1 && !path_sweep) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the path sweep (option 54 >= 1) is not part of this build");
-          return -1;
-        }
-        h->npaths = *set;
-      } else {
-        *get = h->npaths;
-      }
-      return 1;
-    case 55:  // the number of random Fourier features of a path (no resident state changes with it)
-      if (set) {
-        if (*set < 16 || *set > 65536 || *set % 16 != 0) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 55 is a number of features, a multiple of 16 in 16..65536, got %d", *set);
-          return -1;
-        }
-        h->nfeat = *set;
-      } else {
-        *get = h->nfeat;
-      }
-      return 1;
-    case 56:  // the batch size of the DESIGN CALL mi_gp_predict_cov becomes (no resident state changes with it)
-      if (set) {
-        if (*set < 0 || *set > DESIGN_MAX_B) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 56 is 0 (the joint conditional) or a batch of 1 to %d points to select, "
-                   "got %d", DESIGN_MAX_B, *set);
-          return -1;
-        }
-        if (*set >= 1 && !design_select) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: the design call (option 56 >= 1) is not part of this build");
-          return -1;
-        }
-        h->design_b = *set;
-      } else {
-        *get = h->design_b;
-      }
-      return 1;
-    case 57:  // the number of reference points of the design call (no resident state changes with it)
-      if (set) {
-        if (*set < 0) {
-          snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option 57 is a number of reference points >= 0, got %d", *set);
-          return -1;
-        }
-        h->design_nref = *set;
-      } else {
-        *get = h->design_nref;
-      }
-      return 1;
   }
   return 0;
 }
@@ -396,6 +304,7 @@ extern "C" int mi_gp_create(const mi_gp_config* cfg, mi_gp_handle** out) {
     e = hipStreamCreateWithPriority(&h->pstream, hipStreamNonBlocking, hi);
   }
   for (const PlainOption& o : plain_options) h->*o.member = o.def;
+  for (const ModeOption& o : mode_options) h->*o.member = o.def;
   special_defaults(h);
   // hipStreamWriteValue32 / hipStreamWaitValue32 need driver support: without it every two-stream evaluation would fail,
   // so the edges fall back to events (option 26 = 0; mi_gp_set_option refuses 1 and 2 then)
@@ -442,17 +351,17 @@ extern "C" int mi_gp_set_data(mi_gp_handle* h, const mi_gp_buffers* b) {
   h->have_data = true;
   // (the resident factor, U and K^-1 belong to the buffers they were computed in: mi_gp_predict* behind a rebind would read an
   // unfactored K, mi_gp_alpha / mi_gp_grad_x another W)
-  h->factored = h->have_kinv = h->have_u = false;
-  h->b_cond_k = 0;
+  drop_resident(h);
   return 0;
 }
 
 extern "C" int mi_gp_set_option(mi_gp_handle* h, int what, int value) {
   if (!h) return -1;
-  if (const PlainOption* o = find_option(what)) {
+  if (const PlainOption* o = find_option(plain_options, what)) {
     h->*o->member = o->flag ? (value ? 1 : 0) : value < o->lo ? o->lo : value > o->hi ? o->hi : value;
     return 0;
   }
+  if (const ModeOption* o = find_option(mode_options, what)) return set_mode_option(h, *o, value);
   const int r = special_option(h, what, &value, nullptr);
   if (r == 0) snprintf(h->err, sizeof(h->err), "mi_gp_set_option: unknown option %d", what);
   return r > 0 ? 0 : -1;
@@ -461,7 +370,11 @@ extern "C" int mi_gp_set_option(mi_gp_handle* h, int what, int value) {
 // current value of a knob (the library's own defaults included)
 extern "C" int mi_gp_get_option(mi_gp_handle* h, int what, int* value) {
   if (!h || !value) return -1;
-  if (const PlainOption* o = find_option(what)) {
+  if (const PlainOption* o = find_option(plain_options, what)) {
+    *value = h->*o->member;
+    return 0;
+  }
+  if (const ModeOption* o = find_option(mode_options, what)) {
     *value = h->*o->member;
     return 0;
   }
@@ -586,8 +499,7 @@ static int factor_internal(mi_gp_handle* h, const double* theta, int what) {
 
 extern "C" int mi_gp_lml(mi_gp_handle* h, const double* theta, double* lml_out) {
   if (!h || !theta || !lml_out) return -1;
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_lml");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_lml");
+  if (int r = refuse_plain_model(h, "mi_gp_lml")) return r;
   const int r = factor_internal(h, theta, 0);
   if (r < 0) return r;
   if (r > 0) { *lml_out = -INFINITY; return r; }
@@ -662,8 +574,7 @@ extern "C" int mi_gp_lml_grad(mi_gp_handle* h, const double* theta, double* lml_
 // (gpmcmc.py:1096-1101), which PyMC differentiates by autodiff through the same Cholesky.
 extern "C" int mi_gp_alpha(mi_gp_handle* h, double* alpha_host) {
   if (!h || !alpha_host) return -1;
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_alpha");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_alpha");
+  if (int r = refuse_plain_model(h, "mi_gp_alpha")) return r;
   if (!h->have_kinv) { snprintf(h->err, sizeof(h->err), "mi_gp_alpha: call mi_gp_lml_grad first"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
   HCK(hipMemcpyAsync(alpha_host, h->one.alpha_dev, sizeof(double) * h->n, hipMemcpyDeviceToHost, h->stream), "alpha download");
@@ -673,8 +584,7 @@ extern "C" int mi_gp_alpha(mi_gp_handle* h, double* alpha_host) {
 
 extern "C" int mi_gp_grad_x(mi_gp_handle* h, double* gx_dev) {
   if (!h || !gx_dev) return -1;
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_grad_x");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_grad_x");
+  if (int r = refuse_plain_model(h, "mi_gp_grad_x")) return r;
   if (!h->have_kinv) { snprintf(h->err, sizeof(h->err), "mi_gp_grad_x: call mi_gp_lml_grad first"); return -1; }
   HCK(hipSetDevice(h->device), "hipSetDevice");
   const int nsplit = grad_x_splits(h->n, h->cfg.d);
@@ -697,8 +607,7 @@ extern "C" int mi_gp_grad_x(mi_gp_handle* h, double* gx_dev) {
 extern "C" int mi_gp_set_diag(mi_gp_handle* h, const double* diag_dev) {
   if (!h) return -1;
   h->diag_dev = diag_dev;
-  h->factored = h->have_kinv = h->have_u = false;  // (as mi_gp_set_data: K, U and K^-1 belong to the diagonal they were built with)
-  h->b_cond_k = 0;
+  drop_resident(h);  // (as mi_gp_set_data: K, U and K^-1 belong to the diagonal they were built with)
   return 0;
 }
 
@@ -743,8 +652,7 @@ static int batch_internal(mi_gp_handle* h, int k, const double* thetas, int what
     if (!std::isfinite(thetas[i])) { snprintf(h->err, sizeof(h->err), "theta[%d] of problem %d is not finite", i % h->ntheta, i / h->ntheta); return -1; }
     s.theta_host[i] = thetas[i];
   }
-  h->factored = h->have_kinv = h->have_u = false;  // the single-evaluation state of the handle is not touched, but K_dev may alias
-  h->b_cond_k = 0;
+  drop_resident(h);  // the single-evaluation state of the handle is not touched, but K_dev may alias
   const Eval E = batch_eval(h, k);
   for (int attempt = 0;; ++attempt) {
     if (int r = run_evaluation(h, E, what)) return r;
@@ -770,15 +678,13 @@ static int batch_internal(mi_gp_handle* h, int k, const double* thetas, int what
 
 extern "C" int mi_gp_lml_batch(mi_gp_handle* h, int k, const double* thetas, double* lml_out, int* info_out) {
   if (!h || !thetas || !lml_out) return -1;
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_lml_batch");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_lml_batch");
+  if (int r = refuse_plain_model(h, "mi_gp_lml_batch")) return r;
   return batch_internal(h, k, thetas, 0, lml_out, nullptr, info_out);
 }
 
 extern "C" int mi_gp_lml_grad_batch(mi_gp_handle* h, int k, const double* thetas, double* lml_out, double* grad_out, int* info_out) {
   if (!h || !thetas || !lml_out || !grad_out) return -1;
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_lml_grad_batch");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_lml_grad_batch");
+  if (int r = refuse_plain_model(h, "mi_gp_lml_grad_batch")) return r;
   if (h->objective == 1) {
     snprintf(h->err, sizeof(h->err), "mi_gp_lml_grad_batch: the leave-one-out objective (option 48 = 1) has no batched form");
     return -1;
@@ -974,8 +880,7 @@ extern "C" int mi_gp_sample_cov(mi_gp_handle* h, double* cov_dev, long ldc, int 
 // mi_gp_predict's bits: same kernels, same per-element arithmetic, and the solve's GEMMs take the single problem's tile form.
 extern "C" int mi_gp_factor_batch(mi_gp_handle* h, int k, const double* thetas, int* info_out) {
   if (!h) return -1;
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_factor_batch");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_factor_batch");
+  if (int r = refuse_plain_model(h, "mi_gp_factor_batch")) return r;
   if (k < 1 || !thetas) { snprintf(h->err, sizeof(h->err), "mi_gp_factor_batch: k >= 1 and thetas are required"); return -1; }
   return batch_internal(h, k, thetas, 1, nullptr, nullptr, info_out);
 }
@@ -984,8 +889,7 @@ extern "C" int mi_gp_predict_batch(mi_gp_handle* h, int k, const double* Xnew_de
                                    long stride_work, double* mean_dev, double* var_dev, int pred_noise, double* mix_mean_dev,
                                    double* mix_var_dev) {
   if (!h) return -1;
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_batch");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_predict_batch");
+  if (int r = refuse_plain_model(h, "mi_gp_predict_batch")) return r;
   if (k < 1 || !Xnew_dev || !work_dev || !mean_dev || !var_dev || m <= 0) {
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_batch: k >= 1, m >= 1 and the point / work / output buffers are required");
     return -1;
@@ -1061,8 +965,7 @@ static int predict_via_u(mi_gp_handle* h, const double* Xnew_dev, int m, double*
 extern "C" int mi_gp_predict_u(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw,
                                double* mean_dev, double* var_dev, int pred_noise) {
   if (!h || !Xnew_dev || !work_dev || !mean_dev || !var_dev || m <= 0) return -1;
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_u");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_predict_u");
+  if (int r = refuse_plain_model(h, "mi_gp_predict_u")) return r;
   if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_predict_u: call mi_gp_factor first"); return -1; }
   if (!h->buf.Z_dev || !h->buf.W_dev) {
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_u needs Z_dev and W_dev in mi_gp_set_data");
@@ -1094,8 +997,7 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
   }
   if (h->sweep) return mean_sweep(h, Xnew_dev, m, mean_dev, dmean_dev);  // option 53 = 1: another call behind the same entry point
   if (!dmean_dev || !dvar_dev) return -1;
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_predict_grad");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_predict_grad");
+  if (int r = refuse_plain_model(h, "mi_gp_predict_grad")) return r;
   if (!h->buf.Z_dev || !h->buf.W_dev) {
     snprintf(h->err, sizeof(h->err), "mi_gp_predict_grad needs Z_dev and W_dev in mi_gp_set_data");
     return -1;
@@ -1155,12 +1057,17 @@ extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   (void)hipFree(s.dinv_dev); (void)hipFree(s.alpha_dev); (void)hipFree(s.part_dev);
   s.dinv_dev = dinv; s.alpha_dev = alpha; s.part_dev = part;
   h->cap = capacity;
-  // the capacity-sized blocks: the objectives' hold nothing between calls and are dropped (their next use re-sizes them), the
-  // trend's keeps the conditional's G^T, beta^ and b~
-  for (CapBlock* b : {&h->loo, &h->cv, &h->sweep_blk, &h->path_blk}) (void)resize_block(*b, 0, 0);
-  h->path_len = 0;
-  if (h->trend_blk.p && trend_reserve) HCK(trend_reserve(h, capacity), "mi_gp_reserve");
-  if (h->multi_blk.p && multi_reserve) HCK(multi_reserve(h, capacity), "mi_gp_reserve");  // (keeps the conditional's B^T)
+  // the modes' blocks: those that hold nothing between calls are dropped (their next use allocates them again), the trend's
+  // keeps the conditional's G^T, beta^ and b~, the outputs' its B^T
+  for (int id = 0; id < BLK_COUNT; ++id)
+    if (!block_keeps_state(id)) drop_block(h->blocks[id]);
+  static_assert(block_keeps_state(BLK_TREND) && block_keeps_state(BLK_MULTI) && [] {
+    int kept = 0;
+    for (int id = 0; id < BLK_COUNT; ++id) kept += block_keeps_state(id);
+    return kept;
+  }() == 2, "every block that block_keeps_state() names needs its reserve function called here");
+  if (h->blocks[BLK_TREND].p && trend_reserve) HCK(trend_reserve(h, capacity), "mi_gp_reserve");
+  if (h->blocks[BLK_MULTI].p && multi_reserve) HCK(multi_reserve(h, capacity), "mi_gp_reserve");
   return 0;
 }
 
@@ -1224,8 +1131,7 @@ int conditional_block(mi_gp_handle* h, const double* Xnew_dev, const double* yne
 extern "C" int mi_gp_append(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
                             double* work_dev, long ldw) {
   if (!h) { set_global_error("mi_gp_append: null handle"); return -1; }
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_append");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_append");
+  if (int r = refuse_plain_model(h, "mi_gp_append")) return r;
   if (!Xnew_dev || !ynew_dev || !work_dev) { snprintf(h->err, sizeof(h->err), "mi_gp_append: null point, value or work buffer"); return -1; }
   if (k < 1 || k > 128) { snprintf(h->err, sizeof(h->err), "mi_gp_append: 1 <= k <= 128 (got %d)", k); return -1; }
   if (!h->factored) { snprintf(h->err, sizeof(h->err), "mi_gp_append: call mi_gp_factor first"); return -1; }

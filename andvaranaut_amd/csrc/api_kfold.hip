@@ -45,8 +45,7 @@ struct DevInts {  // the singleton path's index list and info words
 extern "C" int mi_gp_kfold(mi_gp_handle* h, int nfolds, const int* fold_ptr_host, const int* fold_idx_host, double* work_dev,
                            long work_len, double* logp_dev, double* mean_dev, double* var_dev, int* info_out) {
   if (!h) { set_global_error("mi_gp_kfold: null handle"); return -1; }
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_kfold");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_kfold");
+  if (int r = refuse_plain_model(h, "mi_gp_kfold")) return r;
   char why[160] = "";
   bool singletons = true;
   long total = 0;

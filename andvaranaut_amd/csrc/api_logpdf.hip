@@ -20,8 +20,7 @@ extern "C" long mi_gp_logpdf_work(long ldw) { return (ldw < 128 || (ldw & 1)) ? 
 extern "C" int mi_gp_logpdf(mi_gp_handle* h, const double* Xnew_dev, const double* ynew_dev, const double* diag_new_dev, int k,
                             double* work_dev, long ldw, double* logp_out, double* dx_dev, double* dy_dev) {
   if (!h) { set_global_error("mi_gp_logpdf: null handle"); return -1; }
-  if (h->trend != 0) return refuse_trend(h, "mi_gp_logpdf");
-  if (h->nout > 1) return refuse_multi(h, "mi_gp_logpdf");
+  if (int r = refuse_plain_model(h, "mi_gp_logpdf")) return r;
   const bool grad = dx_dev || dy_dev;
   char why[160] = "";
   if (!Xnew_dev || !ynew_dev || !work_dev || !logp_out) snprintf(why, sizeof(why), "null point, value, work or result buffer");

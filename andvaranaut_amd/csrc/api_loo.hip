@@ -26,7 +26,7 @@
 constexpr int CV_PASS_MAX = 128;
 static int cv_pass(int cap) { return cap / 2 + 1 < CV_PASS_MAX ? cap / 2 + 1 : CV_PASS_MAX; }  // (folds of two points or more)
 static long cv_padded(int cap) { return (cap + 127) / 128 * 128; }
-static double* cv_R(const mi_gp_handle* h) { return h->cv.p + fold_work_len(cv_pass(h->cv.cap), cv_padded(h->cv.cap)); }
+static double* cv_R(const CapBlock& cv) { return cv.p + fold_work_len(cv_pass(cv.cap), cv_padded(cv.cap)); }
 
 // The fold pass of option 49: mi_gp_kfold's gather and batched leaf over passes of the handle's scratch, then per fold t, e_I,
 // q_I, R_f and the logp (cv_fold_kernel); the folds' sum and the first bad index in one launch behind the last pass.  idx / ptr:
@@ -34,13 +34,12 @@ static double* cv_R(const mi_gp_handle* h) { return h->cv.p + fold_work_len(cv_p
 static int cv_fold_pass(mi_gp_handle* h, int b, std::vector<int>& idx, std::vector<int>& ptr, double* e, double* q, double* scal) {
   const int n = h->n;
   const hipStream_t st = h->stream;
-  if (stale_block(h, h->cv)) {
-    const long vl = cv_padded(h->cap);
-    HCK(resize_block(h->cv, h->cap, fold_work_len(cv_pass(h->cap), vl) + vl * 128 + vl), "k-fold scratch");
-  }
+  const long vl = cv_padded(h->cap);
+  if (int r = ensure_block(h, BLK_CV, fold_work_len(cv_pass(h->cap), vl) + vl * 128 + vl, "k-fold scratch")) return r;
+  const CapBlock& cv = h->blocks[BLK_CV];
   const int nfolds = (n + b - 1) / b;
-  const FoldWork w = fold_layout(h->cv.p, cv_pass(h->cv.cap), n, nfolds);
-  double *R = cv_R(h), *flogp = R + cv_padded(h->cv.cap) * 128;
+  const FoldWork w = fold_layout(cv.p, cv_pass(cv.cap), n, nfolds);
+  double *R = cv_R(cv), *flogp = R + cv_padded(cv.cap) * 128;
   idx.resize(n);
   ptr.resize(nfolds + 1);
   for (int i = 0; i < n; ++i) idx[i] = i;
@@ -62,13 +61,13 @@ int loo_objective(mi_gp_handle* h, double* value, double* grad) {
   // returns before the fill has run, and the handle's streams are non-blocking, so a fill on the null stream can land behind the
   // first tail's kernels and wipe what they wrote (e, s, q and the scalars: a first evaluation with L_LOO = 0 and a zero
   // gradient, and a MAP fit that ends elsewhere).
-  if (stale_block(h, h->loo)) {
-    const size_t len = (size_t)6 * ((h->cap + 127) / 128 * 128) + 8;
-    HCK(resize_block(h->loo, h->cap, len), "leave-one-out vectors");
-    HCK(hipMemsetAsync(h->loo.p, 0, sizeof(double) * len, h->stream), "leave-one-out vectors");
-  }
-  const long vl = (h->loo.cap + 127) / 128 * 128;
-  double *e = h->loo.p, *s = e + vl, *q = s + vl, *w = q + vl, *logp = w + 2 * vl, *scal = logp + vl;
+  const CapBlock& loo = h->blocks[BLK_LOO];
+  const size_t len = (size_t)6 * ((h->cap + 127) / 128 * 128) + 8;
+  bool fresh = false;
+  if (int r = ensure_block(h, BLK_LOO, len, "leave-one-out vectors", &fresh)) return r;
+  if (fresh) HCK(hipMemsetAsync(loo.p, 0, sizeof(double) * len, h->stream), "leave-one-out vectors");
+  const long vl = (loo.cap + 127) / 128 * 128;
+  double *e = loo.p, *s = e + vl, *q = s + vl, *w = q + vl, *logp = w + 2 * vl, *scal = logp + vl;
   const double* zero = w + vl;  // (zeroed with the block, never written)
   const hipStream_t st = h->stream;
   const Eval E = one_eval(h);
@@ -79,7 +78,7 @@ int loo_objective(mi_gp_handle* h, double* value, double* grad) {
   if (h->cv_block > 1) {
     const int r = cv_fold_pass(h, h->cv_block, fold_idx, fold_ptr, e, q, scal);
     if (r != 0) return r;
-    HCK(launch_cv_mirror_multiply(P, ld, cv_R(h), h->cv_block, n, np, B, ld, st), "cv_mirror_multiply");
+    HCK(launch_cv_mirror_multiply(P, ld, cv_R(h->blocks[BLK_CV]), h->cv_block, n, np, B, ld, st), "cv_mirror_multiply");
   } else {
     HCK(launch_loo_weights(P, ld, alpha, n, e, s, q, logp, scal, st), "loo_weights");
     HCK(launch_loo_scale_mirror(P, ld, s, n, np, B, ld, st), "loo_scale_mirror");

@@ -76,7 +76,9 @@ MultiScratch multi_layout(double* base, int cap, bool cov) {
           base + o.minv, base + o.Cinv, base + o.svar, base + o.scal, reinterpret_cast<int*>(base + o.info)};
 }
 size_t multi_scratch_len(int cap, bool cov) { return multi_offsets(cap, cov).len; }
-MultiScratch multi_scratch(const mi_gp_handle* h) { return multi_layout(h->multi_blk.p, h->multi_blk.cap, h->outcov != 0); }
+MultiScratch multi_scratch(const mi_gp_handle* h) {
+  return multi_layout(h->blocks[BLK_MULTI].p, h->blocks[BLK_MULTI].cap, h->outcov != 0);
+}
 
 // log Gamma_q(a) = q (q - 1) / 4 log pi + sum_{j = 1 .. q} lgamma(a + (1 - j) / 2)
 double log_multigamma(double a, int q) {
@@ -111,7 +113,7 @@ int multi_objective(mi_gp_handle* h, double* value, double* grad) {
   const long ld = h->buf.lda;
   const bool cov = h->outcov != 0;
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  if (stale_block(h, h->multi_blk)) HCK(resize_block(h->multi_blk, h->cap, multi_scratch_len(h->cap, cov)), "outputs scratch");
+  if (int r = ensure_block(h, BLK_MULTI, multi_scratch_len(h->cap, cov), "outputs scratch")) return r;
   const MultiScratch t = multi_scratch(h);
   const hipStream_t st = h->stream;
   const Eval E = one_eval(h);
@@ -149,9 +151,7 @@ int multi_objective(mi_gp_handle* h, double* value, double* grad) {
 
 int multi_factor(mi_gp_handle* h) {
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  if (stale_block(h, h->multi_blk)) {
-    HCK(resize_block(h->multi_blk, h->cap, multi_scratch_len(h->cap, h->outcov != 0)), "outputs scratch");
-  }
+  if (int r = ensure_block(h, BLK_MULTI, multi_scratch_len(h->cap, h->outcov != 0), "outputs scratch")) return r;
   const MultiScratch t = multi_scratch(h);
   const Eval E = one_eval(h);
   HCK(launch_multi_stage(h->buf.y_dev, h->buf.lda, h->nout, h->n, h->np, t.YT, t.ldg, h->stream), "multi_stage");
@@ -164,7 +164,7 @@ int multi_factor(mi_gp_handle* h) {
 
 hipError_t multi_predict_reduce(mi_gp_handle* h, const double* work_dev, long ldw, int m, double* mean_dev, double* var_dev,
                                 int pred_noise) {
-  if (!h->multi_blk.p) return hipErrorInvalidValue;  // (mi_gp_factor under option 51 allocates it)
+  if (!h->blocks[BLK_MULTI].p) return hipErrorInvalidValue;  // (mi_gp_factor under option 51 allocates it)
   const MultiScratch t = multi_scratch(h);
   double kd, noise;
   predict_scalars(h, pred_noise, &kd, &noise);
@@ -178,8 +178,12 @@ hipError_t multi_predict_reduce(mi_gp_handle* h, const double* work_dev, long ld
 // stays; without a factored state under q >= 2 there is no B^T to keep, and the block is dropped like the objectives' (its next
 // use re-sizes it).
 hipError_t multi_reserve(mi_gp_handle* h, int capacity) {
-  if (!h->multi_blk.p || h->multi_blk.cap >= capacity) return hipSuccess;
-  if (!(h->factored && h->nout > 1)) return resize_block(h->multi_blk, 0, 0);
+  CapBlock& blk = h->blocks[BLK_MULTI];
+  if (!blk.p || blk.cap >= capacity) return hipSuccess;
+  if (!(h->factored && h->nout > 1)) {
+    drop_block(blk);
+    return hipSuccess;
+  }
   const bool cov = h->outcov != 0;
   double* fresh = nullptr;
   hipError_t e = hipMalloc(&fresh, sizeof(double) * multi_scratch_len(capacity, cov));
@@ -193,7 +197,7 @@ hipError_t multi_reserve(mi_gp_handle* h, int capacity) {
     (void)hipFree(fresh);
     return e;
   }
-  (void)hipFree(h->multi_blk.p);
-  h->multi_blk = {fresh, capacity};
+  (void)hipFree(blk.p);
+  blk = {fresh, capacity, multi_scratch_len(capacity, cov)};
   return hipSuccess;
 }

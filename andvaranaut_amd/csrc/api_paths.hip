@@ -26,8 +26,7 @@ int path_sweep(mi_gp_handle* h, const double* Xnew_dev, int m, double* block_dev
                double* dmean_dev) {
   static const char* entry = "mi_gp_predict_grad under option 54 >= 1 (the path sweep)";
   const int S = h->npaths, F = h->nfeat, d = h->cfg.d;
-  if (h->trend != 0) return refuse_trend(h, entry);
-  if (h->nout > 1) return refuse_multi(h, entry);
+  if (int r = refuse_plain_model(h, entry)) return r;
   if (!h->have_data || !h->buf.Z_dev || !h->buf.W_dev) return path_refuse(h, "needs Z_dev and W_dev in mi_gp_set_data");
   if (d > PATH_MAX_D) {
     snprintf(h->err, sizeof(h->err), "%s: d <= %d, got %d", entry, PATH_MAX_D, d);
@@ -41,14 +40,8 @@ int path_sweep(mi_gp_handle* h, const double* Xnew_dev, int m, double* block_dev
   if (m > 0 && !mean_dev && !dmean_dev) return path_refuse(h, "at least one of mean_dev and dmean_dev is required");
   HCK(hipSetDevice(h->device), "hipSetDevice");
   if (int r = make_u_resident(h)) return r;
-  const size_t need = path_scratch_len(h->cap, d, F);
-  if (stale_block(h, h->path_blk) || h->path_len < need) {
-    HCK(hipStreamSynchronize(h->stream), "stream sync");
-    h->path_len = 0;
-    HCK(resize_block(h->path_blk, h->cap, need), "path sweep scratch");
-    h->path_len = need;
-  }
-  const PathScratch t = path_scratch(h->path_blk.p, h->path_blk.cap, d, F);
+  if (int r = ensure_block(h, BLK_PATH, path_scratch_len(h->cap, d, F), "path sweep scratch")) return r;
+  const PathScratch t = path_scratch(h->blocks[BLK_PATH].p, h->blocks[BLK_PATH].cap, d, F);
   // the path block: Omega [F][d], b [F], W [F][ldw], V [n][ldw]
   const double* Om = block_dev;
   const double* bph = Om + (size_t)F * d;

@@ -9,8 +9,7 @@ static int sweep_refuse(mi_gp_handle* h, const char* why) {
 
 int mean_sweep(mi_gp_handle* h, const double* Xnew_dev, int m, double* mean_dev, double* dmean_dev) {
   static const char* entry = "mi_gp_predict_grad under option 53 = 1 (the mean sweep)";
-  if (h->trend != 0) return refuse_trend(h, entry);
-  if (h->nout > 1) return refuse_multi(h, entry);
+  if (int r = refuse_plain_model(h, entry)) return r;
   if (!h->have_data || !h->buf.Z_dev || !h->buf.W_dev) return sweep_refuse(h, "needs Z_dev and W_dev in mi_gp_set_data");
   if (h->cfg.d > SWEEP_MAX_D) {
     snprintf(h->err, sizeof(h->err), "%s: d <= %d, got %d", entry, SWEEP_MAX_D, h->cfg.d);
@@ -21,11 +20,8 @@ int mean_sweep(mi_gp_handle* h, const double* Xnew_dev, int m, double* mean_dev,
   if (!mean_dev && !dmean_dev) return sweep_refuse(h, "at least one of mean_dev and dmean_dev is required");
   HCK(hipSetDevice(h->device), "hipSetDevice");
   if (int r = make_u_resident(h)) return r;
-  if (stale_block(h, h->sweep_blk)) {
-    HCK(hipStreamSynchronize(h->stream), "stream sync");
-    HCK(resize_block(h->sweep_blk, h->cap, sweep_scratch_len(h->cap, h->cfg.d)), "mean sweep scratch");
-  }
-  HCK(launch_mean_sweep(h->spec, h->one.theta_dev, h->buf.X_dev, h->n, Xnew_dev, m, h->one.alpha_dev, h->sweep_blk.p, mean_dev,
+  if (int r = ensure_block(h, BLK_SWEEP, sweep_scratch_len(h->cap, h->cfg.d), "mean sweep scratch")) return r;
+  HCK(launch_mean_sweep(h->spec, h->one.theta_dev, h->buf.X_dev, h->n, Xnew_dev, m, h->one.alpha_dev, h->blocks[BLK_SWEEP].p, mean_dev,
                         dmean_dev, h->stream), "mean_sweep");
   HCK(hipStreamSynchronize(h->stream), "stream sync");
   return 0;

@@ -52,7 +52,7 @@ TrendScratch trend_layout(double* base, int cap) {
   t.info = reinterpret_cast<int*>(t.scal + 8);
   return t;
 }
-TrendScratch trend_scratch(const mi_gp_handle* h) { return trend_layout(h->trend_blk.p, h->trend_blk.cap); }
+TrendScratch trend_scratch(const mi_gp_handle* h) { return trend_layout(h->blocks[BLK_TREND].p, h->blocks[BLK_TREND].cap); }
 
 // A = sum over k segments of GT[:, seg] B[seg]^T (B = V stored [k][x] for the fit, G^T itself for the conditional), C_A = chol(A)
 // in place, its row-major inverse, then u = GT x, c, beta^ and the scalars
@@ -77,7 +77,7 @@ int trend_objective(mi_gp_handle* h, double* value, double* grad) {
   const int n = h->n, np = h->np, ntc = h->ntc, p = trend_columns(h);
   const long ld = h->buf.lda;
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  if (stale_block(h, h->trend_blk)) HCK(resize_block(h->trend_blk, h->cap, trend_scratch_len(h->cap)), "trend scratch");
+  if (int r = ensure_block(h, BLK_TREND, trend_scratch_len(h->cap), "trend scratch")) return r;
   const TrendScratch t = trend_scratch(h);
   const hipStream_t st = h->stream;
   const Eval E = one_eval(h);
@@ -105,7 +105,7 @@ int trend_factor(mi_gp_handle* h) {
   const int n = h->n, np = h->np, p = trend_columns(h);
   const long ld = h->buf.lda;
   HCK(hipSetDevice(h->device), "hipSetDevice");
-  if (stale_block(h, h->trend_blk)) HCK(resize_block(h->trend_blk, h->cap, trend_scratch_len(h->cap)), "trend scratch");
+  if (int r = ensure_block(h, BLK_TREND, trend_scratch_len(h->cap), "trend scratch")) return r;
   const TrendScratch t = trend_scratch(h);
   const hipStream_t st = h->stream;
   const Eval E = one_eval(h);
@@ -127,7 +127,7 @@ int trend_factor(mi_gp_handle* h) {
 
 hipError_t trend_predict_reduce(mi_gp_handle* h, const double* Xnew_dev, const double* work_dev, long ldw, int m, double* mean_dev,
                                 double* var_dev, int pred_noise) {
-  if (!h->trend_blk.p) return hipErrorInvalidValue;  // (mi_gp_factor under a trend allocates it; mi_gp_reserve ends `factored`)
+  if (!h->blocks[BLK_TREND].p) return hipErrorInvalidValue;  // (mi_gp_factor under a trend allocates it; mi_gp_reserve ends `factored`)
   const TrendScratch t = trend_scratch(h);
   double kd, noise;
   predict_scalars(h, pred_noise, &kd, &noise);
@@ -139,7 +139,7 @@ hipError_t trend_predict_reduce(mi_gp_handle* h, const double* Xnew_dev, const d
 // mi_gp_factor -- moves into the new block (the layout depends on the capacity), as mi_gp_reserve moves the leaf inverses and
 // alpha; everything else is written by the next call before it is read.  The handle's stream is idle (mi_gp_reserve).
 hipError_t trend_reserve(mi_gp_handle* h, int capacity) {
-  if (!h->trend_blk.p) return hipSuccess;
+  if (!h->blocks[BLK_TREND].p) return hipSuccess;
   double* fresh = nullptr;
   hipError_t e = hipMalloc(&fresh, sizeof(double) * trend_scratch_len(capacity));
   if (e != hipSuccess) return e;
@@ -154,7 +154,7 @@ hipError_t trend_reserve(mi_gp_handle* h, int capacity) {
     (void)hipFree(fresh);
     return e;
   }
-  (void)hipFree(h->trend_blk.p);
-  h->trend_blk = {fresh, capacity};
+  (void)hipFree(h->blocks[BLK_TREND].p);
+  h->blocks[BLK_TREND] = {fresh, capacity, trend_scratch_len(capacity)};
   return hipSuccess;
 }

@@ -31,12 +31,29 @@ struct Scratch {
   double* theta_host = nullptr; // pinned [k][ntheta]
 };
 
-// A device block sized by point capacity.  Its owner re-sizes it before use once the handle's capacity has outgrown it
-// (stale_block / resize_block); mi_gp_reserve drops it, or moves what must outlive the call (trend_reserve).
+// A device block of a mode's scratch, sized by point capacity and by what the mode's call needs.  Its owner asks for it before
+// use (ensure_block); mi_gp_reserve drops it, or moves what must outlive the call (block_keeps_state).
 struct CapBlock {
   double* p = nullptr;
-  int cap = 0;  // points p is sized for
+  int cap = 0;     // points p is sized for
+  size_t len = 0;  // doubles p holds
 };
+// The handle's mode blocks (mi_gp_handle::blocks).  A new mode adds its id here, asks for its block with ensure_block and
+// declares its option in mode_options (api_gp.hip); release_handle and mi_gp_reserve go over all of them.
+enum BlockId {
+  BLK_LOO,     // [6][padded cap] e, s, q, w, the zero vector and the per-point logp, then [8] scalars (api_loo.hip)
+  BLK_CV,      // the fold pass of the objective under option 49 > 1 (cv_fold_pass(), api_loo.hip)
+  BLK_TREND,   // TrendScratch (api_trend.hip)
+  BLK_MULTI,   // MultiScratch (api_multi.hip); laid out for option 52's value: a change of it drops the block
+  BLK_SWEEP,   // the training points staged for the kernel and the partial sums of one pass (sweep_f64.hip: sweep_scratch_len)
+  BLK_PATH,    // the points, frequencies and weights staged for the kernel, the partial sums of one pass and the conditioning's
+               // two 128-row blocks (paths_f64.hip: path_scratch_len)
+  BLK_DESIGN,  // design_f64.hip: design_scratch_len
+  BLK_COUNT
+};
+// true: the block holds the conditional's part of a mode behind mi_gp_factor, and mi_gp_reserve moves it (trend_reserve /
+// multi_reserve).  Every other block holds nothing between calls: mi_gp_reserve drops it and its next use allocates it again
+constexpr bool block_keeps_state(int id) { return id == BLK_TREND || id == BLK_MULTI; }
 
 struct mi_gp_handle {
   mi_gp_config cfg;
@@ -126,37 +143,26 @@ struct mi_gp_handle {
   double* app_stats_dev;   // [4] mi_gp_append's scalar increments and bad-pivot word
   int objective;           // option 48: what mi_gp_lml_grad returns -- 0 the log marginal likelihood, 1 the leave-one-out log
                            // predictive density (loo_objective() behind the ordinary evaluation)
-  CapBlock loo;            // [6][padded loo.cap] e, s, q, w, the zero vector and the per-point logp, then [8] scalars
-                           // (api_loo.hip; allocated by the first evaluation under option 48 = 1)
   int cv_block;            // option 49: the fold size b of the objective under option 48 = 1 -- 1 (default) leave-one-out, 2..128 the
                            // leave-block-out density over the contiguous folds [f b, min((f + 1) b, n))
-  CapBlock cv;             // the fold pass of that objective (cv_fold_pass(), api_loo.hip; allocated by the first evaluation with b > 1)
   int trend;               // option 50: the TREND whose coefficients are integrated out -- 0 none, 1 constant h = [1], 2 linear
                            // h = [1, x_1 .. x_d] (mi_gp_lml_grad, mi_gp_factor and mi_gp_predict; api_trend.hip)
-  CapBlock trend_blk;      // its scratch (TrendScratch, api_trend.hip; allocated by the first use)
   int nout;                // option 51: the number of OUTPUTS q under one shared kernel -- 1 (default) the single y, 2..128 the vectors
                            // y_dev[o * lda ..) (mi_gp_lml_grad, mi_gp_factor and mi_gp_predict; api_multi.hip)
-  CapBlock multi_blk;      // its scratch (MultiScratch, api_multi.hip; allocated by the first use)
   int outcov;              // option 52: the covariance BETWEEN the outputs of option 51 = q >= 2 -- 0 (default) none, the outputs
                            // independent under one variance; 1 a q x q Sigma under the Jeffreys prior, integrated out (api_multi.hip).
-                           // Part of multi_blk's layout: a change drops the block
+                           // Part of the outputs' block's layout: a change drops the block
   int sweep;               // option 53: what mi_gp_predict_grad is -- 0 (default) the conditional and its gradients, 1 the MEAN SWEEP,
                            // the matrix-free posterior mean and its input gradient (mean_sweep(), api_sweep.hip)
-  CapBlock sweep_blk;      // its scratch: the training points staged for the kernel and the partial sums of one pass of query
-                           // points (sweep_f64.hip: sweep_scratch_len; allocated by the first sweep, holds nothing between calls)
   int npaths;              // option 54: 0 (default) mi_gp_predict_grad is what option 53 says; S = 1..128: it is the PATH SWEEP of S
                            // posterior sample paths over the caller's path block (path_sweep(), api_paths.hip)
   int nfeat;               // option 55: F, the random Fourier features of a path's prior draw (a multiple of 16 in 16..65536; read
                            // only under option 54 >= 1)
-  CapBlock path_blk;       // the path sweep's scratch: the points, frequencies and weights staged for the kernel, the partial sums of
-  size_t path_len;         // one pass and the conditioning's two 128-row blocks (paths_f64.hip: path_scratch_len; path_len doubles,
-                           // grown by a call that needs more; holds nothing between calls)
   int design_b;            // option 56: 0 (default) mi_gp_predict_cov is the joint conditional; b = 1..128: it is the DESIGN CALL that
                            // selects up to b of the candidates in Xnew_dev (design_select(), api_design.hip)
   int design_nref;         // option 57: Mr, the reference points behind the candidates in Xnew_dev (0: the maximum-variance criterion;
                            // read only under option 56 >= 1)
-  CapBlock design_blk;     // the design call's scratch (design_f64.hip: design_scratch_len; design_len doubles, grown by a call that
-  size_t design_len;       // needs more; holds nothing between calls)
+  CapBlock blocks[BLK_COUNT];  // the modes' scratch, by BlockId (each allocated by its mode's first use)
   char err[256];
 };
 
@@ -165,21 +171,40 @@ inline int hfail(mi_gp_handle* h, hipError_t e, const char* where) {
   return -2;
 }
 
-// frees b, then allocates len doubles for cap points (len = 0: none); what it held is not kept
-inline hipError_t resize_block(CapBlock& b, int cap, size_t len) {
-  (void)hipFree(b.p);
-  b = CapBlock();
-  const hipError_t e = len ? hipMalloc(&b.p, sizeof(double) * len) : hipSuccess;
-  if (e == hipSuccess && len) b.cap = cap;
-  return e;
-}
-inline bool stale_block(const mi_gp_handle* h, const CapBlock& b) { return !b.p || b.cap < h->cap; }
-
 #define HCK(call, where)                          \
   do {                                            \
     hipError_t e__ = (call);                      \
     if (e__ != hipSuccess) return hfail(h, e__, where); \
   } while (0)
+
+// Ends the resident state: the factor, U and K^-1 of the single problem and the batch's conditional factors belong to the data,
+// diagonal and model they were computed with.  (Each call site says why its change ends them.)
+inline void drop_resident(mi_gp_handle* h) {
+  h->factored = h->have_kinv = h->have_u = false;
+  h->b_cond_k = 0;
+}
+
+// frees b; what it held is not kept.  The stream that used it must be idle
+inline void drop_block(CapBlock& b) {
+  (void)hipFree(b.p);
+  b = CapBlock();
+}
+// The mode block `id` with at least len doubles, sized for the handle's capacity: 0, or the C-ABI error code with the text set
+// (`what` names the block).  A block that is missing, was sized for fewer points than h->cap or holds fewer doubles is
+// allocated anew behind a synchronisation of the handle's stream (which may still read the old one); what it held is not kept
+// (*fresh, where given, says so: the new block's contents are unspecified).
+inline int ensure_block(mi_gp_handle* h, BlockId id, size_t len, const char* what, bool* fresh = nullptr) {
+  CapBlock& b = h->blocks[id];
+  if (fresh) *fresh = false;
+  if (b.p && b.cap >= h->cap && b.len >= len) return 0;
+  HCK(hipStreamSynchronize(h->stream), "stream sync");
+  drop_block(b);
+  HCK(hipMalloc(&b.p, sizeof(double) * len), what);
+  b.cap = h->cap;
+  b.len = len;
+  if (fresh) *fresh = true;
+  return 0;
+}
 
 // What the enqueue code evaluates: the single problem (one_eval) or a batch of problems (batch_eval) -- its K / Z / W, its
 // scratch and its per-problem strides.  X, y and lda are the handle's (h->buf) either way.  Built by each call, never stored:
@@ -343,6 +368,10 @@ hipError_t multi_reserve(mi_gp_handle* h, int capacity) __attribute__((weak));
 inline int refuse_multi(mi_gp_handle* h, const char* entry) {
   snprintf(h->err, sizeof(h->err), "%s has no form under several outputs (option 51 = %d): set option 51 to 1 first", entry, h->nout);
   return -1;
+}
+// an entry point of the plain model alone (no trend, one output): 0, or the -1 of the trend's refusal, else of the outputs'
+inline int refuse_plain_model(mi_gp_handle* h, const char* entry) {
+  return h->trend != 0 ? refuse_trend(h, entry) : h->nout > 1 ? refuse_multi(h, entry) : 0;
 }
 // option 52 = 1 under q >= 2 outputs integrates a q x q covariance out: n >= q + 2 (the predictive t has n - q + 1 degrees of
 // freedom, its variance needs more than two).  True -- and the text is set -- when the entry point must return -1

@@ -17,8 +17,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "andvaranaut_amd", "csrc")
 HERE = os.path.join(ROOT, "tests", "sched_trace")
-SOURCES = [os.path.join(HERE, f) for f in ("hip_standin.hip", "kernel_standin.hip", "trace_main.hip")] + [
-    os.path.join(CSRC, f) for f in ("gp_sched.hip", "api_gp.hip")]
+STANDINS = ("hip_standin.hip", "kernel_standin.hip")
+LIBRARY = ("gp_sched.hip", "api_gp.hip")
 SANITIZE = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-Xarch_host", "-fno-omit-frame-pointer"]
 
 
@@ -29,33 +29,41 @@ def _hipcc():
     return None
 
 
-_built = {}  # variant -> path of the program, this session
+_built = {}  # variant -> path of the program or of one of its objects, this session
 
 
-def build_trace_program(sanitize=False):
-    """path of the trace program (built on first use in this session); skips the calling test if there is no hipcc"""
-    if sanitize in _built:
-        return _built[sanitize]
+def build_trace_program(sanitize=False, main="trace_main.hip", extra=(), root=ROOT, defines=()):
+    """path of the trace program (built on first use in this session); skips the calling test if there is no hipcc.  main: the
+    file of tests/sched_trace with the program's main (modes_main.hip: the mode-option program); extra: further files of that
+    directory; root / defines: another tree with the same layout and -D flags (the recording of tests/test_mode_options_host.py)"""
+    variant = (sanitize, main, tuple(extra), root, tuple(defines))
+    if variant in _built:
+        return _built[variant]
     hipcc = _hipcc()
     if hipcc is None:
         pytest.skip("hipcc not found: the schedule-trace program cannot be built")
     work = tempfile.mkdtemp(prefix="migp_sched_trace_")  # (mode 0700, ours alone)
     atexit.register(shutil.rmtree, work, ignore_errors=True)
     flags = ["--offload-host-only", "-std=c++17", "-O1", "-g", "-Wall", "-Wno-unused-result"] + (SANITIZE if sanitize else [])
+    flags += ["-D" + d for d in defines]
+    here, csrc = os.path.join(root, os.path.relpath(HERE, ROOT)), os.path.join(root, os.path.relpath(CSRC, ROOT))
     objs = []
-    for src in SOURCES:
-        obj = os.path.join(work, os.path.basename(src) + ".o")
-        r = subprocess.run([hipcc] + flags + ["-c", src, "-o", obj], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("compiling %s failed:\n%s" % (src, r.stderr[-4000:]))
-        objs.append(obj)
+    for src in [os.path.join(here, f) for f in STANDINS + (main,) + tuple(extra)] + [os.path.join(csrc, f) for f in LIBRARY]:
+        key = (sanitize, src, tuple(defines))  # (the programs of a session share their objects)
+        if key not in _built:
+            obj = os.path.join(work, os.path.basename(src) + ".o")
+            r = subprocess.run([hipcc] + flags + ["-c", src, "-o", obj], capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError("compiling %s failed:\n%s" % (src, r.stderr[-4000:]))
+            _built[key] = obj
+        objs.append(_built[key])
     # (-no-hip-rt: the stand-ins ARE the runtime; nothing of libamdhip64 is linked)
     prog = os.path.join(work, "sched_trace")
     r = subprocess.run([hipcc, "--offload-host-only", "-no-hip-rt"] + (SANITIZE if sanitize else []) + objs + ["-o", prog],
                        capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("linking the trace program failed:\n%s" % r.stderr[-4000:])
-    _built[sanitize] = prog
+    _built[variant] = prog
     return prog
 
 

@@ -5,9 +5,10 @@
 
 extern "C" __attribute__((visibility("default"))) long design_poison(mi_gp_handle* h) {
   if (!h) return -1;
-  if (!h->design_blk.p) return 0;
+  const CapBlock& b = h->blocks[BLK_DESIGN];
+  if (!b.p) return 0;
   if (hipSetDevice(h->device) != hipSuccess) return -1;
-  if (hipMemsetAsync(h->design_blk.p, 0xff, sizeof(double) * h->design_len, h->stream) != hipSuccess) return -1;
+  if (hipMemsetAsync(b.p, 0xff, sizeof(double) * b.len, h->stream) != hipSuccess) return -1;
   if (hipStreamSynchronize(h->stream) != hipSuccess) return -1;
-  return (long)h->design_len;
+  return (long)b.len;
 }

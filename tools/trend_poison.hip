@@ -5,10 +5,11 @@
 
 extern "C" __attribute__((visibility("default"))) long trend_poison(mi_gp_handle* h) {
   if (!h) return -1;
-  if (!h->trend_blk.p) return 0;
-  const size_t len = trend_scratch_len(h->trend_blk.cap);
+  const CapBlock& b = h->blocks[BLK_TREND];
+  if (!b.p) return 0;
+  const size_t len = b.len;
   if (hipSetDevice(h->device) != hipSuccess) return -1;
-  if (hipMemsetAsync(h->trend_blk.p, 0xff, sizeof(double) * len, h->stream) != hipSuccess) return -1;
+  if (hipMemsetAsync(b.p, 0xff, sizeof(double) * len, h->stream) != hipSuccess) return -1;
   if (hipStreamSynchronize(h->stream) != hipSuccess) return -1;
   return (long)len;
 }
