@@ -6,6 +6,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmi_gp.so")
 SPARSE_LIB_PATH = os.path.join(_HERE, "libmi_gp_sparse.so")  # the sparse inducing-point bound (include/mi_gp_sparse.h)
+# the same entry points and the data-side gradients (include/mi_gp_sparse_data.h)
+SPARSE_DATA_LIB_PATH = os.path.join(_HERE, "libmi_gp_sparse_data.so")
 
 MAX_KERN = 8
 KERNEL_IDS = {"RBF": 0, "Matern52": 1, "Matern32": 2, "Exponential": 3, "RatQuad": 4}
@@ -235,16 +237,11 @@ EXPORTS = [
 
 
 _sparse = None
+_sparse_data = None
 
 
-def load_sparse():
-    """Load libmi_gp_sparse.so and declare every entry point of include/mi_gp_sparse.h."""
-    global _sparse
-    if _sparse is not None:
-        return _sparse
-    if not os.path.exists(SPARSE_LIB_PATH):
-        raise RuntimeError(f"{SPARSE_LIB_PATH} not found: build it with `make -C andvaranaut_amd/csrc` (there is no CPU fallback)")
-    lib = ctypes.CDLL(SPARSE_LIB_PATH)
+def _declare_sparse(lib):
+    """the argument types of the eight entry points of include/mi_gp_sparse.h"""
     vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
     dp = ctypes.POINTER(ctypes.c_double)
     lib.mi_gp_sparse_create.argtypes = [ctypes.POINTER(MiGpSparseConfig), ctypes.POINTER(vp)]
@@ -257,9 +254,37 @@ def load_sparse():
     lib.mi_gp_sparse_bound_grad.argtypes = [vp, dp, dp, dp]
     lib.mi_gp_sparse_factor.argtypes = [vp, dp]
     lib.mi_gp_sparse_predict.argtypes = [vp, vp, ci, vp, vp, ci]
+
+
+def load_sparse():
+    """Load libmi_gp_sparse.so and declare every entry point of include/mi_gp_sparse.h."""
+    global _sparse
+    if _sparse is not None:
+        return _sparse
+    if not os.path.exists(SPARSE_LIB_PATH):
+        raise RuntimeError(f"{SPARSE_LIB_PATH} not found: build it with `make -C andvaranaut_amd/csrc` (there is no CPU fallback)")
+    lib = ctypes.CDLL(SPARSE_LIB_PATH)
+    _declare_sparse(lib)
     for name in SPARSE_EXPORTS:
         getattr(lib, name)  # raises AttributeError if a declared symbol is missing
     _sparse = lib
+    return lib
+
+
+def load_sparse_data():
+    """Load libmi_gp_sparse_data.so and declare every entry point of include/mi_gp_sparse_data.h (those of
+    include/mi_gp_sparse.h, the same code, and mi_gp_sparse_bind_data_grad)."""
+    global _sparse_data
+    if _sparse_data is not None:
+        return _sparse_data
+    if not os.path.exists(SPARSE_DATA_LIB_PATH):
+        raise RuntimeError(f"{SPARSE_DATA_LIB_PATH} not found: build it with `make -C andvaranaut_amd/csrc` (there is no CPU fallback)")
+    lib = ctypes.CDLL(SPARSE_DATA_LIB_PATH)
+    _declare_sparse(lib)
+    lib.mi_gp_sparse_bind_data_grad.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    for name in SPARSE_DATA_EXPORTS:
+        getattr(lib, name)  # raises AttributeError if a declared symbol is missing
+    _sparse_data = lib
     return lib
 
 
@@ -274,3 +299,7 @@ SPARSE_EXPORTS = [
     "mi_gp_sparse_factor",
     "mi_gp_sparse_predict",
 ]
+
+# every symbol include/mi_gp_sparse_data.h declares, with those of the header it includes (checked by
+# tests/test_sgpr_data_grad_host.py against the library's dynamic symbols)
+SPARSE_DATA_EXPORTS = SPARSE_EXPORTS + ["mi_gp_sparse_bind_data_grad"]

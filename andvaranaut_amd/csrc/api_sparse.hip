@@ -7,82 +7,11 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include "migp_kernels.h"
-#include "../../include/mi_gp_sparse.h"
+#include "sparse_object.h"  // struct mi_gp_sparse and the work block's layout (shared with api_sparse_data.hip)
 
 using namespace migp;
 
-namespace {
-
-constexpr int SPARSE_MAX_M = 2048;       // 16 tile columns: the widest panel the factorisation uses
-constexpr int SPARSE_CHUNK = 8192;       // default data points per pass step
-constexpr int SPARSE_VECS = 8;           // vectors of mp doubles at the end of the work block (seven used)
-
-inline int pad128(int x) { return (x + 127) / 128 * 128; }
-
-// The caller's work block: nine mp x mp blocks (leading dimension mp), two blocks of chunk work rows, the leaf inverses of L and
-// LB, eight vectors
-struct SparseWork {
-  double *Kuu, *Psi, *Bm, *U, *UB, *Binv, *H, *G0, *M2;  // Binv later holds G0 U^T, H later U G0 U^T (= -2 Guu)
-  double *Wc, *Tc;                                       // K(X_c, Z) -> A_c^T; T_c^T (predict: b* rows)
-  double *dinvL, *dinvB;
-  double *v, *vs, *cvec, *ahat, *traw, *tv, *zero;       // v, v / s, c, a^, L^-T a^, that / s, the zero alpha of Kuu's contraction
-};
-inline long sparse_work_len(long mp, long chunk) { return 9 * mp * mp + 2 * chunk * mp + 2 * (mp / 128) * MINV_ELEMS + SPARSE_VECS * mp; }
-inline SparseWork sparse_layout(double* base, long mp, long chunk) {
-  SparseWork w;
-  double* p = base;
-  double** blocks[9] = {&w.Kuu, &w.Psi, &w.Bm, &w.U, &w.UB, &w.Binv, &w.H, &w.G0, &w.M2};
-  for (auto b : blocks) { *b = p; p += mp * mp; }
-  w.Wc = p; p += chunk * mp;
-  w.Tc = p; p += chunk * mp;
-  w.dinvL = p; p += (mp / 128) * MINV_ELEMS;
-  w.dinvB = p; p += (mp / 128) * MINV_ELEMS;
-  double** vecs[7] = {&w.v, &w.vs, &w.cvec, &w.ahat, &w.traw, &w.tv, &w.zero};
-  for (auto v : vecs) { *v = p; p += mp; }
-  return w;
-}
-
-}  // namespace
-
-struct mi_gp_sparse {
-  mi_gp_sparse_config cfg;
-  KernSpec spec;
-  int n, m, mp, ntm, d, P, chunk;
-  hipStream_t stream = nullptr;
-  // the object's own scratch (first mi_gp_sparse_set_data): theta [P], the chunks' gradient [P], Kuu's gradient [P], two scalar
-  // records [8] each, yy [2], the two bad-pivot words [2 doubles], dF/dZ [m d, with zgrad_slabs >= 1 only], then the partial sums
-  // of the two contractions and, with zgrad_slabs >= 1, Kuu's part of dF/dZ [m d] and the slab scratch the two passes over Z share
-  double* own_dev = nullptr;
-  double* host = nullptr;  // pinned mirror of the first 3 P + 20 (+ m d) doubles
-  const double *X = nullptr, *y = nullptr, *Z = nullptr;
-  double* work = nullptr;
-  bool have_data = false, factored = false;
-  double fac_s = 0.0, fac_kdiag = 0.0;  // noise variance and prior variance at the factored theta
-  char err[256] = "";
-  int zcap() const { return cfg.zgrad_slabs; }  // 0: no dF/dZ, every call as it was before the field existed
-  long zlen() const { return zcap() > 0 ? (long)m * d : 0; }
-  long small_len() const { return 3L * P + 20 + zlen(); }
-  double* theta_dev() const { return own_dev; }
-  double* gacc_dev() const { return own_dev + P; }
-  double* gsym_dev() const { return own_dev + 2 * P; }
-  double* scal_dev() const { return own_dev + 3 * P; }        // [0..8) pass 1's record, [8..16) the gradient's
-  double* yy_dev() const { return own_dev + 3 * P + 16; }
-  int* info_dev() const { return reinterpret_cast<int*>(own_dev + 3 * P + 18); }  // [0] Kuu, [1] B
-  double* gz_dev() const { return own_dev + 3 * P + 20; }    // dF/dZ: the chunks' sums, then Kuu's part added
-  double* part_rect_dev() const { return own_dev + small_len(); }
-  double* part_sym_dev() const { return part_rect_dev() + (long)sparse_contract_blocks(chunk, m) * P; }
-  double* gzsym_dev() const { return part_sym_dev() + (long)grad_contract_blocks(m) * P; }
-  double* zscratch_dev() const { return gzsym_dev() + zlen(); }
-  // the slab scratch: the largest chunk's slabs of sparse_zgrad, or the column splits of grad_x over Z (one after the other)
-  long zscratch_len() const {
-    if (zcap() <= 0) return 0;
-    const int splits = grad_x_splits(m, d);
-    return std::max(sparse_zgrad_scratch(std::min(chunk, n), m, d, zcap()), splits > 1 ? (long)splits * m * d : 0L);
-  }
-};
-
-static thread_local char g_sparse_err[256] = "";
+thread_local char g_sparse_err[256] = "";
 
 static int sfail(mi_gp_sparse* s, hipError_t e, const char* where) {
   snprintf(s->err, sizeof(s->err), "%s: %s", where, hipGetErrorString(e));
@@ -106,10 +35,11 @@ extern "C" long mi_gp_sparse_work(int m, int chunk) {
 
 extern "C" int mi_gp_sparse_destroy(mi_gp_sparse* s) {
   if (!s) return 0;
-  if (s->stream || s->own_dev || s->host) {
+  if (s->stream || s->own_dev || s->host || s->xscratch) {
     (void)hipSetDevice(s->cfg.device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     (void)hipFree(s->own_dev);
+    (void)hipFree(s->xscratch);
     if (s->host) (void)hipHostFree(s->host);
     if (s->stream) (void)hipStreamDestroy(s->stream);
   }
@@ -314,6 +244,10 @@ static int gradient(mi_gp_sparse* s, const double* theta, double* grad_out) {
     if (s->zcap() > 0)  // Kuf's term of dF/dZ on the same weights: the chunks in chunk order onto gz
       SCK(launch_sparse_zgrad(s->spec, s->theta_dev(), s->X + i0 * d, cnt, s->Z, m, w.Tc, mp, s->y + i0, w.tv, s->zcap(),
                               s->zscratch_dev(), s->gz_dev(), first, s->stream), "dF/dZ contraction");
+    if (s->gy_out) {  // bound outputs (include/mi_gp_sparse_data.h): dF/dy on the resident rows, dF/dX on the same weights
+      if (!sparse_data_grad_chunk) { snprintf(s->err, sizeof(s->err), "mi_gp_sparse_bound_grad: the data-side gradients are not linked into this library"); return -1; }
+      if (int r = sparse_data_grad_chunk(s, w, i0, cnt, sv)) return r;
+    }
   }
   // Kuu's term through the symmetric contraction: W = -2 Guu and a zero alpha give sum_uv Guu_uv dK(Z,Z)_uv/dtheta (its gv and
   // jitter slots, 1/2 tr(-W), are not used)
@@ -362,6 +296,11 @@ extern "C" int mi_gp_sparse_bound_grad(mi_gp_sparse* s, const double* theta_host
   if (r == 0 && grad_out) {
     r = gradient(s, theta_host, grad_out);
     if (r != 0) *bound = -INFINITY;
+  }
+  if (r > 0 && grad_out && s->gy_out) {  // a bad pivot zeroes the bound data-side outputs too
+    SCK(hipMemsetAsync(s->gy_out, 0, sizeof(double) * (size_t)s->n, s->stream), "dF/dy reset");
+    if (s->gx_out) SCK(hipMemsetAsync(s->gx_out, 0, sizeof(double) * (size_t)s->n * s->d, s->stream), "dF/dX reset");
+    SCK(hipStreamSynchronize(s->stream), "stream sync");
   }
   return r;
 }

@@ -487,6 +487,19 @@ hipError_t launch_sparse_zgrad(const KernSpec& spec, const double* theta, const 
                                int first, hipStream_t stream);
 // gz[e] (first: =, else +=) sum_{k < nslab} part[k * slab + e] for e < len, in slab order
 hipError_t launch_sparse_zgrad_add(const double* part, int nslab, long slab, long len, double* gz, int first, hipStream_t stream);
+// (sparse_xgrad_f64.hip) Slabs of one chunk's dF/dX pass: min(64-column blocks of m, cap, ceil(1024 / 64-row blocks of the chunk)), lowered until the
+// slab scratch is at most 64 MB -- a function of (cnt, m, d, cap) alone -- and the doubles of scratch they take
+int sparse_xgrad_slabs(int cnt, int m, int d, int cap);
+long sparse_xgrad_scratch(int cnt, int m, int d, int cap);
+// gx[cnt x d] = sum_{u < m} (T[i][u] + y[i] tv[u]) dK(x_i, z_u)/dx_i: workgroup (rb, sl) of the grid (ceil(cnt / 64), slabs) walks
+// the blocks of Z sl, sl + slabs, ..., and the slabs' sum is written in slab order.  scratch: sparse_xgrad_scratch(cnt, m, d, cap)
+// doubles
+hipError_t launch_sparse_xgrad(const KernSpec& spec, const double* theta, const double* X, int cnt, const double* Z, int m,
+                               const double* T, long ldt, const double* y, const double* tv, int cap, double* scratch, double* gx,
+                               hipStream_t stream);
+// gy[i] = -y[i] / s + (sum_{u < m} At[i][u] ahat[u]) / s for i < cnt (rows ld apart), every row's sum in a fixed order
+hipError_t launch_sparse_ygrad(const double* At, long ld, int m, const double* ahat, const double* y, int cnt, double sv, double* gy,
+                               hipStream_t stream);
 // v[u] (first: =, else +=) sum_{i < cnt} At[i][u] y[i] for u < mp (a multiple of 64), yy[0] likewise sum y_i^2
 hipError_t launch_sparse_accum_vy(const double* At, long ld, int mp, const double* y, int cnt, double* v, double* yy, int first,
                                   hipStream_t stream);

@@ -654,6 +654,7 @@ class GPMCMC(ConsumersMixin):
         self.outputs = "first"
         self.output_cov = "shared"
         self.inducing = None
+        self.inducing_raw = None
 
     def __release(self):
         gp = getattr(self, "gp", None)
@@ -695,27 +696,40 @@ class GPMCMC(ConsumersMixin):
                              "factorisation; fit with inducing=None to use it")
 
     def _inducing_points(self, inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs, optimize_inducing=False):
-        """The converted inducing points Z of fit(inducing=...), or None.  Every refusal is raised here, before any device call."""
+        """(Z, Zraw) of fit(inducing=...): the inducing points converted by the installed xconrevs and as raw inputs, or
+        (None, None).  Every refusal is raised here, before any device call."""
         if optimize_inducing and (inducing is None or method != "map"):
             raise ValueError("optimize_inducing=True needs inducing points to move and method='map': give inducing=m or an array, "
                              "and fit with method='map'")
         if inducing is None:
-            return None
-        if method not in ("map", "none") or iwgp or cwgp or objective != "lml" or trend is not None or outputs != "first":
+            return None, None
+        warps = bool(iwgp or cwgp)
+        if (method not in ("map", "none") or (warps and method != "map") or objective != "lml" or trend is not None
+                or outputs != "first"):
             raise ValueError("inducing needs method='map' or 'none', objective='lml', trend=None, outputs='first' and neither iwgp "
                              "nor cwgp: the sparse bound has no sampler, no cross-validation objective, no trend, no warps and one output")
+        if warps and optimize_inducing:
+            raise ValueError("inducing: iwgp / cwgp and optimize_inducing=True do not combine -- under warps the inducing points "
+                             "are raw inputs that move with the input warp, not free parameters")
+        if iwgp and not any(isinstance(c, wgp) for c in self.xconrevs):
+            raise ValueError("inducing with iwgp=True needs at least one wgp among xconrevs: there is no input warp to fit")
+        if cwgp and (not isinstance(self.yconrevs[0], wgp) or self.yconrevs[0].np == 0):
+            raise ValueError("inducing with cwgp=True needs yconrevs[0] to be a wgp with tunable parameters: there is no output "
+                             "warp to fit")
         xin, _ = self._converted(self.x, self.y - self.ym)
         if isinstance(inducing, (int, np.integer)) and not isinstance(inducing, bool):
             if not 1 <= inducing <= min(len(xin), MAX_INDUCING):
                 raise ValueError(f"inducing = {inducing} points: 1 <= inducing <= min(n, {MAX_INDUCING}) is required (n = {len(xin)})")
-            return select_inducing(xin, int(inducing), seed=inducing_seed)
+            Z, idx = select_inducing(xin, int(inducing), seed=inducing_seed, return_index=True)
+            return Z, np.ascontiguousarray(self.x[idx], dtype=np.float64)
         Z = np.array(inducing, dtype=np.float64)
         if Z.ndim != 2 or Z.shape[1] != self.nx or not 1 <= Z.shape[0] <= min(len(xin), MAX_INDUCING) or not np.isfinite(Z).all():
             raise ValueError(f"inducing must be an int or a finite (m, nx = {self.nx}) array of raw inputs with 1 <= m <= "
                              f"min(n, {MAX_INDUCING})")
+        Zraw = np.ascontiguousarray(Z.copy())
         for i in range(self.nx):
             Z[:, i] = self.xconrevs[i].con(Z[:, i])
-        return np.ascontiguousarray(Z)
+        return np.ascontiguousarray(Z), Zraw
 
     def _no_all_outputs(self, what):
         """Raised, before any device call, by what has no form once every output is modelled (fit(outputs="all"))."""
@@ -757,7 +771,7 @@ class GPMCMC(ConsumersMixin):
         likelihood does not change under K_y -> c K_y, so only their priors identify the overall scale of kv, gv and the
         jitter.  The choice is part of the object's state (``self.output_cov``).
         ``inducing=m`` (an int) or an (m, nx) array of raw inputs (with ``method="map"`` or ``"none"``, ``objective="lml"``, no
-        trend, no warps, ``outputs="first"``) fits on m << n inducing points instead of the n x n covariance, for data sets one
+        trend, ``outputs="first"``) fits on m << n inducing points instead of the n x n covariance, for data sets one
         card cannot factorise: the fit maximises Titsias' collapsed variational bound (a lower bound of the log marginal
         likelihood, exact theta gradient, the data streamed in chunks) plus the priors, and ``predict`` returns the sparse
         predictive.  An int chooses the points by k-means++ seeding among the converted inputs (``select_inducing``,
@@ -767,9 +781,14 @@ class GPMCMC(ConsumersMixin):
         device, Z in converted input space without prior or bounds, started at the points ``inducing`` gives;
         ``data["inducing_start"]`` keeps those.  The choice is part of the object's state (``self.inducing``, the converted --
         with ``optimize_inducing`` the optimised -- points) and survives pickling;
+        ``iwgp`` / ``cwgp`` combine with ``inducing`` under ``method="map"`` (not with ``optimize_inducing``): the inducing points
+        are then raw inputs (``self.inducing_raw``, ``data["inducing_raw"]``; an int picks data rows by k-means++ over the
+        inputs as the installed warps convert them), every evaluation warps them along with the data and pulls the bound's exact
+        dF/dy, dF/dX and dF/dZ back onto the warp parameters, and ``self.inducing`` ends as those points under the fitted warps;
         what needs the dense factorisation (predict_joint, sample_posterior, log_predictive, cv_stats, predict_mean,
         sample_paths, predict_posterior, the resident paths of BO and inverse_opt) then raises ValueError."""
-        Z = self._inducing_points(inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs, optimize_inducing)
+        Z, Zraw = self._inducing_points(inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs, optimize_inducing)
+        sparse_warps = Z is not None and bool(iwgp or cwgp)
         if outputs not in ("first", "all"):
             raise ValueError(f"outputs must be 'first' or 'all' (got {outputs!r})")
         if output_cov not in MiGP.OUTPUT_COVS:
@@ -798,8 +817,10 @@ class GPMCMC(ConsumersMixin):
         self.m, self.gp, self.hypers, data = self.__fit(self.x, self.y - self.ym, method, iwgp, cwgp, jitter,
                                                         truncate, restarts, objective=objective, cv=cv, trend=trend, outputs=outputs,
                                                         output_cov=output_cov, inducing=Z, optimize_inducing=optimize_inducing,
-                                                        **kwargs)
-        self.inducing = data["inducing"] if optimize_inducing else Z
+                                                        inducing_raw=Zraw if sparse_warps else None, **kwargs)
+        # (under warps the stored points are the raw ones converted by the FITTED warps: what predict and a rebuilt object need)
+        self.inducing = data["inducing"] if (optimize_inducing or sparse_warps) else Z
+        self.inducing_raw = Zraw
         # what adaptive_sample(refit=True) fits again with
         self._fit_args = dict(method=method, iwgp=iwgp, cwgp=cwgp, jitter=jitter, truncate=truncate, restarts=restarts, objective=objective,
                               nfolds=nfolds, fold_seed=fold_seed, trend=trend, outputs=outputs, output_cov=output_cov, inducing=inducing,
@@ -889,24 +910,34 @@ class GPMCMC(ConsumersMixin):
                 rc += 1
         return out
 
-    def _warp_likelihood(self, gp, x, y, xin0, iwgp, cwgp):
+    def _warp_likelihood(self, gp, x, y, xin0, iwgp, cwgp, zraw=None):
         """likelihood(values, theta) for HyperModel.logp_dlogp with warp variables: warp the data with the
         current parameters (torch, host), evaluate LML + its theta / X / y gradients on the device, add the
-        warp Jacobian sum(log y') (gpmcmc.py:319) and pull the data gradients back onto the warp parameters."""
+        warp Jacobian sum(log y') (gpmcmc.py:319) and pull the data gradients back onto the warp parameters.
+        ``zraw`` (a sparse fit: gp is the bound's object) are the inducing points as raw inputs: under iwgp they go through the
+        warpers that warp x, the object is moved onto them and dF/dZ joins the pull-back."""
         import torch
 
         xt = torch.from_numpy(np.ascontiguousarray(x))
         yt = torch.from_numpy(np.ascontiguousarray(y))
+        if zraw is not None:
+            zt = torch.from_numpy(np.ascontiguousarray(zraw, dtype=np.float64))
+            zin0 = np.column_stack([self.xconrevs[i].con(np.asarray(zraw, dtype=np.float64)[:, i]) for i in range(self.nx)])
 
         def likelihood(values, theta):
             leaves = {}
-            xin_t = yin_t = yder_t = None
+            xin_t = yin_t = yder_t = zin_t = None
             if iwgp:
                 leaves["iwgp"] = torch.tensor(values["iwgp"], dtype=torch.float64, requires_grad=True)
                 warpers = self.iwgp_set(leaves["iwgp"], mode="torch", x=xt)
                 cols = [warpers[i].conmc(xt[:, i]) if isinstance(warpers[i], wgp) else torch.from_numpy(xin0[:, i])
                         for i in range(self.nx)]
                 xin_t = torch.stack(cols, dim=1)
+                if zraw is not None:
+                    zin_t = torch.stack([warpers[i].conmc(zt[:, i]) if isinstance(warpers[i], wgp) else torch.from_numpy(zin0[:, i])
+                                         for i in range(self.nx)], dim=1)
+                    if not bool(torch.all(torch.isfinite(zin_t))):
+                        return -np.inf, None, {}
             if cwgp:
                 for nm in ("cwgp_pos", "cwgp"):
                     if nm in values:
@@ -919,7 +950,14 @@ class GPMCMC(ConsumersMixin):
                     return -np.inf, None, {}
             gp.update_data(X=None if xin_t is None else xin_t.detach().numpy(),
                            y=None if yin_t is None else yin_t.detach().numpy())
-            val, gth, gy, gx = gp.lml_grad_data(theta, want_x=iwgp)
+            gz = None
+            if zraw is None:
+                val, gth, gy, gx = gp.lml_grad_data(theta, want_x=iwgp)
+            elif iwgp:
+                gp.set_inducing(zin_t.detach().numpy())
+                val, gth, gy, gx, gz = gp.lml_grad_data(theta, want_x=True, want_z=True)
+            else:  # the output warp alone moves nothing but y
+                val, gth, gy, gx = gp.lml_grad_data(theta, want_x=False, want_z=False)
             if not np.isfinite(val):
                 return -np.inf, None, {}
             s = torch.zeros((), dtype=torch.float64)
@@ -928,13 +966,15 @@ class GPMCMC(ConsumersMixin):
                 val = val + float(torch.log(yder_t).sum().detach())
             if iwgp:
                 s = s + (torch.from_numpy(gx) * xin_t).sum()
+                if gz is not None:
+                    s = s + (torch.from_numpy(gz) * zin_t).sum()
             s.backward()
             return val, gth, {k: v.grad.numpy().copy() for k, v in leaves.items()}
 
         return likelihood
 
     def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", cv=None, trend=None,
-              outputs="first", output_cov="shared", inducing=None, optimize_inducing=False, **kwargs):
+              outputs="first", output_cov="shared", inducing=None, optimize_inducing=False, inducing_raw=None, **kwargs):
         n_i, n_pos, n_free = self._warp_sizes(iwgp, cwgp)
         model = HyperModel(self.nx, self.kerns, noise=self.noise, truncate=truncate, jitter=jitter, n_iwgp=n_i,
                            n_cwgp_pos=n_pos, n_cwgp=n_free)
@@ -943,13 +983,15 @@ class GPMCMC(ConsumersMixin):
         # (inducing points: gp.lml_grad is then the sparse bound and its gradient, gp.predict the sparse predictive)
         gp = MiGP(xin, yin, self.kernel, device=self.device) if inducing is None else MiSparseGP(xin, yin, inducing, self.kernel,
                                                                                                   device=self.device,
-                                                                                                  z_grad=bool(optimize_inducing))
+                                                                                                  z_grad=bool(optimize_inducing)
+                                                                                                  or (inducing_raw is not None and iwgp),
+                                                                                                  data_grad=inducing_raw is not None)
         if trend is not None:
             gp.set_trend(trend)  # (gp.lml_grad then returns the trend's marginal likelihood; the stored handle keeps the trend)
         if outputs == "all":
             gp.set_outputs(self._converted_outputs(y))  # (gp.lml_grad then returns the sum of the columns' marginal likelihoods)
             gp.set_output_cov(output_cov)  # ("integrated": the marginal likelihood with the between-output covariance integrated out)
-        lik = self._warp_likelihood(gp, x, y, xin, iwgp, cwgp) if (iwgp or cwgp) else None
+        lik = self._warp_likelihood(gp, x, y, xin, iwgp, cwgp, zraw=inducing_raw) if (iwgp or cwgp) else None
         # pm.find_MAP maximises without the transform Jacobian, pm.sample with it (priors.py header)
         fun_map = lambda q: model.logp_dlogp(q, gp.lml_grad, jacobian=False, likelihood=lik)  # noqa: E731
         data = None
@@ -1048,6 +1090,10 @@ class GPMCMC(ConsumersMixin):
                                                               np.atleast_1d(mp.get("cwgp", [])))))
             xin, yin = self._converted(x, y)
             gp.update_data(X=xin, y=yin)
+            if inducing_raw is not None:  # a sparse fit: the raw inducing points through the fitted warps, on the device too
+                zin = np.ascontiguousarray(np.column_stack([self.xconrevs[i].con(inducing_raw[:, i]) for i in range(self.nx)]))
+                gp.set_inducing(zin)
+                data["inducing"], data["inducing_raw"] = zin, inducing_raw.copy()
         return model, gp, mp, data
 
     def __sample(self, model, gp, x, y, xin, yin, iwgp=False, cwgp=False, draws=1000, tune=1000, chains=None,

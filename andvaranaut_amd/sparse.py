@@ -14,12 +14,14 @@ from .backend import parse_kernel
 MAX_INDUCING = 2048
 DEFAULT_CHUNK = 8192
 DEFAULT_ZGRAD_SLABS = 1024  # no cap of its own: the library's rule (row blocks of the chunk, 1024 workgroups, 64 MB) decides
+DEFAULT_XGRAD_SLABS = 1024  # likewise for dF/dX (column blocks of m, 1024 workgroups, 64 MB)
 
 
-def select_inducing(X, m, seed=None):
+def select_inducing(X, m, seed=None, return_index=False):
     """m distinct rows of X (converted inputs) by k-means++ seeding: the first uniformly, every further one with probability
     proportional to its squared distance to the nearest row chosen so far (D^2 sampling).  Plain NumPy, O(n m d).  Rows that
-    coincide with a chosen one have distance 0 and are never drawn; with fewer than m distinct rows a ValueError is raised."""
+    coincide with a chosen one have distance 0 and are never drawn; with fewer than m distinct rows a ValueError is raised.
+    ``return_index=True`` returns (rows, their indices into X)."""
     X = np.asarray(X, dtype=np.float64)
     if X.ndim != 2:
         raise ValueError("X must be (n, d)")
@@ -38,7 +40,8 @@ def select_inducing(X, m, seed=None):
         idx[k] = rng.choice(n, p=d2 / total)
         d2 = np.minimum(d2, ((X - X[idx[k]]) ** 2).sum(axis=1))
         d2[idx[k]] = 0.0
-    return np.ascontiguousarray(X[idx])
+    rows = np.ascontiguousarray(X[idx])
+    return (rows, idx) if return_index else rows
 
 
 class MiSparseGP:
@@ -46,12 +49,22 @@ class MiSparseGP:
     gradient and the sparse predictive.  lml_grad has MiGP.lml_grad's signature, so HyperModel.logp_dlogp takes it unchanged.
     ``z_grad=True`` adds the exact gradient of the bound by the inducing locations: lml_grad_z returns (F, dF/dtheta, dF/dZ),
     set_inducing moves Z (lml_grad still returns (F, dF/dtheta) alone).  ``zgrad_slabs`` caps the slabs per chunk of its kernel
-    (None: the library's rule); another count regroups sums, the same count returns the same bits."""
+    (None: the library's rule); another count regroups sums, the same count returns the same bits.
+    ``data_grad=True`` adds the gradients of the bound by the data (include/mi_gp_sparse_data.h; the object then runs on
+    libmi_gp_sparse_data.so, the same code with one entry point more): lml_grad_data returns (F, dF/dtheta, dF/dy, dF/dX), which
+    is MiGP.lml_grad_data's shape, and update_data overwrites the resident data in place -- what warps fitted with the
+    hyper-parameters need.  ``xgrad_slabs`` caps the slabs of dF/dX's kernel as zgrad_slabs does for dF/dZ's.  Without data_grad
+    every call returns the bits it returns without the argument."""
 
-    def __init__(self, X, y, Z, kernel="RBF", device=0, chunk=None, z_grad=False, zgrad_slabs=None):
+    def __init__(self, X, y, Z, kernel="RBF", device=0, chunk=None, z_grad=False, zgrad_slabs=None, data_grad=False,
+                 xgrad_slabs=None):
         if not torch.cuda.is_available():
             raise RuntimeError("MiSparseGP needs a ROCm GPU: the GP hot path has no CPU implementation")
-        self.lib = _lib.load_sparse()
+        self.data_grad = bool(data_grad)
+        if xgrad_slabs is not None and (not self.data_grad or int(xgrad_slabs) < 1):
+            raise ValueError(f"xgrad_slabs needs data_grad=True and a count >= 1, got {xgrad_slabs}")
+        self.xgrad_slabs = DEFAULT_XGRAD_SLABS if xgrad_slabs is None else int(xgrad_slabs)
+        self.lib = _lib.load_sparse_data() if self.data_grad else _lib.load_sparse()
         X = np.ascontiguousarray(X, dtype=np.float64)
         y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
         Z = np.ascontiguousarray(Z, dtype=np.float64)
@@ -98,8 +111,16 @@ class MiSparseGP:
             self.y_t = torch.from_numpy(y).to(self.dev)
             self.Z_t = torch.from_numpy(Z).to(self.dev)
             self.work_t = torch.empty(self.work_len, dtype=torch.float64, device=self.dev)
+            self.gy_t = self.gx_t = None
+            if self.data_grad:
+                self.gy_t = torch.zeros(self.n, dtype=torch.float64, device=self.dev)
+                self.gx_t = torch.zeros((self.n, self.d), dtype=torch.float64, device=self.dev)
             torch.cuda.synchronize(self.dev)
+        self._bad_X = self._bad_y = False
+        self._bound_x = None  # whether dF/dX is bound beside dF/dy (None: nothing is bound)
         self._bind()
+        if self.data_grad:
+            self._bind_data_grad(True)
 
     def _bind(self):
         self._factored_theta = None
@@ -117,6 +138,46 @@ class MiSparseGP:
             torch.cuda.synchronize(self.dev)
         self._bind()
 
+    def _bind_data_grad(self, want_x):
+        """dF/dy's output and, with want_x, dF/dX's behind every later gradient call (None: unbound)"""
+        if self._bound_x is not want_x:
+            gy = None if want_x is None else self.gy_t.data_ptr()
+            gx = self.gx_t.data_ptr() if want_x else None
+            self._check(self.lib.mi_gp_sparse_bind_data_grad(self.h, gy, gx, self.xgrad_slabs), "mi_gp_sparse_bind_data_grad")
+            self._bound_x = want_x
+
+    def update_data(self, X=None, y=None):
+        """Overwrites the resident inputs / outputs in place (same shapes) and binds the buffers again, as MiGP.update_data does
+        for the dense handle and by its rule for non-finite data: a non-finite array is not uploaded, and until a finite one
+        replaces it lml_grad, lml_grad_z, lml_grad_data and bound return -inf (zero gradients) like a bad pivot."""
+        if X is not None:
+            self._bad_X = not np.isfinite(np.asarray(X, dtype=np.float64)).all()
+            if self._bad_X:
+                X = None
+        if y is not None:
+            self._bad_y = not np.isfinite(np.asarray(y, dtype=np.float64)).all()
+            if self._bad_y:
+                y = None
+        if X is None and y is None:
+            self._factored_theta = None
+            return
+        with torch.cuda.device(self.dev):
+            if X is not None:
+                X = np.ascontiguousarray(X, dtype=np.float64)
+                if X.shape != (self.n, self.d):
+                    raise ValueError("X must keep its shape")
+                self.X_t.copy_(torch.from_numpy(X))
+            if y is not None:
+                y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+                if y.shape != (self.n,):
+                    raise ValueError("y must keep its shape")
+                self.y_t.copy_(torch.from_numpy(y))
+            torch.cuda.synchronize(self.dev)
+        self._bind()
+
+    def _bad_data(self):
+        return self._bad_X or self._bad_y
+
     def _check(self, r, what):
         if r < 0:
             raise RuntimeError(f"{what} failed ({r}): {self.lib.mi_gp_sparse_last_error(self.h).decode()}")
@@ -133,6 +194,8 @@ class MiSparseGP:
         theta, tp = self._theta(theta)
         out = ctypes.c_double()
         self._factored_theta = None
+        if self._bad_data():
+            return -np.inf
         self.info = self._check(self.lib.mi_gp_sparse_bound_grad(self.h, tp, ctypes.byref(out), None), "mi_gp_sparse_bound_grad")
         return out.value
 
@@ -149,11 +212,32 @@ class MiSparseGP:
         F, grad = self._bound_grad(theta)
         return F, grad[: self.ntheta].copy(), grad[self.ntheta:].reshape(self.m, self.d).copy()
 
+    def lml_grad_data(self, theta, want_x=True, want_z=False):
+        """(F, dF/dtheta, dF/dy, dF/dX or None[, dF/dZ with want_z]) at natural-scale theta (data_grad=True; want_z needs
+        z_grad=True): MiGP.lml_grad_data's shape.  want_x=False binds dF/dy alone, so dF/dX's kernel does not run.
+        (-inf, zeros, ...) on a bad pivot or non-finite data."""
+        if not self.data_grad:
+            raise ValueError("lml_grad_data needs MiSparseGP(..., data_grad=True)")
+        if want_z and not self.z_grad:
+            raise ValueError("lml_grad_data(want_z=True) needs MiSparseGP(..., z_grad=True)")
+        self._bind_data_grad(bool(want_x))
+        F, grad = self._bound_grad(theta)
+        if np.isfinite(F):
+            with torch.cuda.device(self.dev):
+                gy = self.gy_t.cpu().numpy()
+                gx = self.gx_t.cpu().numpy() if want_x else None
+        else:
+            gy, gx = np.zeros(self.n), (np.zeros((self.n, self.d)) if want_x else None)
+        out = (F, grad[: self.ntheta].copy(), gy, gx)
+        return out + (grad[self.ntheta:].reshape(self.m, self.d).copy(),) if want_z else out
+
     def _bound_grad(self, theta):
         theta, tp = self._theta(theta)
         out = ctypes.c_double()
         grad = np.zeros(self.ntheta + (self.m * self.d if self.z_grad else 0))
         self._factored_theta = None
+        if self._bad_data():
+            return -np.inf, grad
         self.info = self._check(self.lib.mi_gp_sparse_bound_grad(self.h, tp, ctypes.byref(out),
                                                                  grad.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
                                 "mi_gp_sparse_bound_grad")
@@ -194,7 +278,7 @@ class MiSparseGP:
         if getattr(self, "h", None) is not None:
             self.lib.mi_gp_sparse_destroy(self.h)
             self.h = None
-        self.X_t = self.y_t = self.Z_t = self.work_t = None
+        self.X_t = self.y_t = self.Z_t = self.work_t = self.gy_t = self.gx_t = None
 
     def __del__(self):
         try:
