@@ -8,6 +8,8 @@ LIB_PATH = os.path.join(_HERE, "libmi_gp.so")
 SPARSE_LIB_PATH = os.path.join(_HERE, "libmi_gp_sparse.so")  # the sparse inducing-point bound (include/mi_gp_sparse.h)
 # the same entry points and the data-side gradients (include/mi_gp_sparse_data.h)
 SPARSE_DATA_LIB_PATH = os.path.join(_HERE, "libmi_gp_sparse_data.so")
+# the entry points of include/mi_gp.h and the gradient binding (include/mi_gp_deriv.h)
+DERIV_LIB_PATH = os.path.join(_HERE, "libmi_gp_deriv.so")
 
 MAX_KERN = 8
 KERNEL_IDS = {"RBF": 0, "Matern52": 1, "Matern32": 2, "Exponential": 3, "RatQuad": 4}
@@ -86,6 +88,7 @@ class MiGpSparseConfig(ctypes.Structure):
 
 
 _lib = None
+_deriv = None
 
 
 def load():
@@ -99,6 +102,33 @@ def load():
             "or `make -C andvaranaut_amd/csrc` (there is no CPU fallback for the GP hot path)"
         )
     lib = ctypes.CDLL(LIB_PATH)
+    _declare(lib)
+    _lib = lib
+    return lib
+
+
+def load_deriv():
+    """Load libmi_gp_deriv.so and declare every entry point of include/mi_gp_deriv.h (those of include/mi_gp.h, the same code,
+    and the gradient binding's three)."""
+    global _deriv
+    if _deriv is not None:
+        return _deriv
+    if not os.path.exists(DERIV_LIB_PATH):
+        raise RuntimeError(f"{DERIV_LIB_PATH} not found: build it with `make -C andvaranaut_amd/csrc` (there is no CPU fallback)")
+    lib = ctypes.CDLL(DERIV_LIB_PATH)
+    _declare(lib)
+    vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
+    lib.mi_gp_deriv_bind.argtypes = [vp, ci]
+    lib.mi_gp_deriv_assemble.argtypes = [ci, ci, vp, vp, ci, ci, vp, ci, ci, vp, cl, ci, ci, ci, ci, vp, vp]
+    lib.mi_gp_deriv_contract.argtypes = [ci, ci, vp, vp, ci, vp, cl, vp, vp, cl, vp, vp]
+    for name in DERIV_EXPORTS:
+        getattr(lib, name)  # raises AttributeError if a declared symbol is missing
+    _deriv = lib
+    return lib
+
+
+def _declare(lib):
+    """the argument types of the entry points of include/mi_gp.h"""
     vp, ci, cl, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_double
     dp = ctypes.POINTER(ctypes.c_double)
     ip = ctypes.POINTER(ctypes.c_int)
@@ -170,8 +200,6 @@ def load():
     lib.mi_gp_shard_last_error.restype = ctypes.c_char_p
     for name in EXPORTS:
         getattr(lib, name)  # raises AttributeError if a declared symbol is missing
-    _lib = lib
-    return lib
 
 
 # every symbol include/mi_gp.h declares (checked by tests/test_abi.py against the header text)
@@ -234,6 +262,10 @@ EXPORTS = [
     "mi_gp_shard_chain_stream",
     "mi_gp_shard_last_error",
 ]
+
+# every symbol include/mi_gp_deriv.h declares, with those of the header it includes (checked by tests/test_deriv_host.py against
+# the library's dynamic symbols)
+DERIV_EXPORTS = EXPORTS + ["mi_gp_deriv_bind", "mi_gp_deriv_assemble", "mi_gp_deriv_contract"]
 
 
 _sparse = None

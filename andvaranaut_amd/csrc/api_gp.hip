@@ -208,6 +208,11 @@ static int set_mode_option(mi_gp_handle* h, const ModeOption& o, int value) {
     return -1;
   }
   if (o.refuse && o.refuse(h, value)) return -1;
+  if (value != o.def && h->deriv_npts) {
+    snprintf(h->err, sizeof(h->err), "mi_gp_set_option: option %d = %d has no form under a gradient binding (mi_gp_deriv_bind, %d points): "
+             "unbind with npts = 0 first", o.id, value, h->deriv_npts);
+    return -1;
+  }
   if (value != o.def && o.built && !o.built()) {
     snprintf(h->err, sizeof(h->err), o.not_built, value);
     return -1;
@@ -220,6 +225,12 @@ static int set_mode_option(mi_gp_handle* h, const ModeOption& o, int value) {
     drop_block(h->blocks[BLK_MULTI]);
   }
   return 0;
+}
+
+bool modes_at_default(const mi_gp_handle* h) {
+  for (const ModeOption& o : mode_options)
+    if (h->*o.member != o.def) return false;
+  return true;
 }
 
 // defaults of the options below (2: mi_gp_config's panel_tiles)
@@ -499,7 +510,7 @@ static int factor_internal(mi_gp_handle* h, const double* theta, int what) {
 
 extern "C" int mi_gp_lml(mi_gp_handle* h, const double* theta, double* lml_out) {
   if (!h || !theta || !lml_out) return -1;
-  if (int r = refuse_plain_model(h, "mi_gp_lml")) return r;
+  if (int r = refuse_trend_or_multi(h, "mi_gp_lml")) return r;
   const int r = factor_internal(h, theta, 0);
   if (r < 0) return r;
   if (r > 0) { *lml_out = -INFINITY; return r; }
@@ -619,6 +630,7 @@ extern "C" int mi_gp_set_diag(mi_gp_handle* h, const double* diag_dev) {
 // instead of on separate handles and streams (which stops paying at the fourth handle: hardware queues).
 extern "C" int mi_gp_set_batch(mi_gp_handle* h, const mi_gp_batch_buffers* b) {
   if (!h) return -1;
+  if (int r = refuse_deriv(h, "mi_gp_set_batch")) return r;
   if (!b || !b->K_dev || b->count < 1) {
     snprintf(h->err, sizeof(h->err), "mi_gp_set_batch: buffers with K_dev and count >= 1 are required");
     return -1;
@@ -757,8 +769,11 @@ extern "C" int mi_gp_predict(mi_gp_handle* h, const double* Xnew_dev, int m, dou
   HCK(hipSetDevice(h->device), "hipSetDevice");
   const int mp = (m + 127) / 128 * 128;
   // K(Xnew, X): one prediction point per row, zeros in the padding
-  HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, mp, h->np, 0, 0, h->stream),
-      "assemble cross");
+  if (h->deriv_npts)  // a gradient binding: cov(f(x*), [f ; grad f](X)) in the launch's place
+    HCK(deriv_assemble_cross(h, Xnew_dev, m, work_dev, ldw, mp), "assemble cross (gradient binding)");
+  else
+    HCK(launch_assemble(h->spec, h->one.theta_dev, Xnew_dev, m, h->buf.X_dev, h->n, work_dev, ldw, mp, h->np, 0, 0, h->stream),
+        "assemble cross");
   HCK(trsm_rec(h, one_eval(h), work_dev, ldw, mp, 0, h->ntc), "trsm");
   if (h->nout > 1) HCK(multi_predict_reduce(h, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "outputs predict_reduce");
   else if (h->trend != 0) HCK(trend_predict_reduce(h, Xnew_dev, work_dev, ldw, m, mean_dev, var_dev, pred_noise), "trend predict_reduce");
@@ -782,6 +797,7 @@ extern "C" int mi_gp_predict_cov(mi_gp_handle* h, const double* Xnew_dev, int m,
                   : !h ? "null handle"
                   : h->trend != 0 ? "no form under a trend (option 50): set option 50 to 0 first"
                   : h->nout > 1 ? "no form under several outputs (option 51): set option 51 to 1 first"
+                  : h->deriv_npts ? "no form under a gradient binding (mi_gp_deriv_bind): unbind with npts = 0 first"
                   : !h->factored ? "call mi_gp_factor first"
                   : (ldw < h->np || (ldw & 1)) ? "ldw must be even and >= padded n" : nullptr;
   if (why) {
@@ -828,7 +844,8 @@ extern "C" int mi_gp_sample_cov(mi_gp_handle* h, double* cov_dev, long ldc, int 
                   : ldd < m ? "ldd must be >= m"
                   : !(extra_jitter >= 0.0 && std::isfinite(extra_jitter)) ? "extra_jitter must be finite and >= 0"
                   : work_len < sample_cov_work(m, s) ? "work_len is shorter than mi_gp_sample_cov_work(m, s)"
-                  : !h ? "null handle" : nullptr;
+                  : !h ? "null handle"
+                  : h->deriv_npts ? "no form under a gradient binding (mi_gp_deriv_bind): unbind with npts = 0 first" : nullptr;
   if (why) {
     char text[200];
     snprintf(text, sizeof(text), "mi_gp_sample_cov: %s", why);
@@ -1032,6 +1049,7 @@ extern "C" int mi_gp_predict_grad(mi_gp_handle* h, const double* Xnew_dev, int m
 // The handle's n-dependent scratch for up to `capacity` points; the resident contents (leaf inverses, alpha) are kept.
 extern "C" int mi_gp_reserve(mi_gp_handle* h, int capacity) {
   if (!h) { set_global_error("mi_gp_reserve: null handle"); return -1; }
+  if (int r = refuse_deriv(h, "mi_gp_reserve")) return r;
   if (capacity < h->n) { snprintf(h->err, sizeof(h->err), "mi_gp_reserve: capacity %d < n = %d", capacity, h->n); return -1; }
   const int cap_np = (capacity + 127) / 128 * 128;
   if (h->have_data && h->buf.lda < cap_np) {

@@ -163,6 +163,8 @@ struct mi_gp_handle {
   int design_nref;         // option 57: Mr, the reference points behind the candidates in Xnew_dev (0: the maximum-variance criterion;
                            // read only under option 56 >= 1)
   CapBlock blocks[BLK_COUNT];  // the modes' scratch, by BlockId (each allocated by its mode's first use)
+  int deriv_npts;          // 0 (default), or the points of a GRADIENT BINDING (mi_gp_deriv_bind, api_deriv.hip, the only writer): the
+                           // n = deriv_npts (1 + d) observations are [y ; d_1 y ; .. ; d_d y] at the deriv_npts x d points of X_dev
   char err[256];
 };
 
@@ -369,9 +371,31 @@ inline int refuse_multi(mi_gp_handle* h, const char* entry) {
   snprintf(h->err, sizeof(h->err), "%s has no form under several outputs (option 51 = %d): set option 51 to 1 first", entry, h->nout);
   return -1;
 }
-// an entry point of the plain model alone (no trend, one output): 0, or the -1 of the trend's refusal, else of the outputs'
-inline int refuse_plain_model(mi_gp_handle* h, const char* entry) {
+// api_deriv.hip: the gradient binding (include/mi_gp_deriv.h has the algebra).  Weak like loo_objective: a library without the file
+// has no mi_gp_deriv_bind, so deriv_npts stays 0 and none of the three is reached.  Each stands where the plain launch stands --
+// the training assembly of enqueue_factor, the contraction of enqueue_gradient, the cross-covariance of mi_gp_predict -- with the
+// plain launch's arguments and stream
+hipError_t deriv_assemble_train(mi_gp_handle* h, const Eval& E, int noise_form, hipStream_t st) __attribute__((weak));
+hipError_t deriv_grad_contract(mi_gp_handle* h, const Eval& E) __attribute__((weak));
+hipError_t deriv_assemble_cross(mi_gp_handle* h, const double* Xnew_dev, int m, double* work_dev, long ldw, int mp) __attribute__((weak));
+// the -1 of an entry point that has no form under a gradient binding (0 without one)
+inline int refuse_deriv(mi_gp_handle* h, const char* entry) {
+  if (!h->deriv_npts) return 0;
+  snprintf(h->err, sizeof(h->err), "%s has no form under a gradient binding (mi_gp_deriv_bind, %d points): unbind with npts = 0 first",
+           entry, h->deriv_npts);
+  return -1;
+}
+// api_gp.hip: is every mode option (48-57) at its default
+bool modes_at_default(const mi_gp_handle* h);
+
+// an entry point that has no form under a trend or several outputs: 0, or the -1 of the trend's refusal, else of the outputs'
+inline int refuse_trend_or_multi(mi_gp_handle* h, const char* entry) {
   return h->trend != 0 ? refuse_trend(h, entry) : h->nout > 1 ? refuse_multi(h, entry) : 0;
+}
+// an entry point of the plain model alone (no trend, one output, no gradient binding): 0 or the -1 of the first that refuses
+inline int refuse_plain_model(mi_gp_handle* h, const char* entry) {
+  if (int r = refuse_trend_or_multi(h, entry)) return r;
+  return refuse_deriv(h, entry);
 }
 // option 52 = 1 under q >= 2 outputs integrates a q x q covariance out: n >= q + 2 (the predictive t has n - q + 1 degrees of
 // freedom, its variance needs more than two).  True -- and the text is set -- when the entry point must return -1

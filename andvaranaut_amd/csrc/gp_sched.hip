@@ -628,8 +628,11 @@ static int enqueue_factor(mi_gp_handle* h, const Eval& E, Sched& S, int noise_fo
   // (Until round 6 evaluations of 96 tile columns and more assembled the first super-panel's columns first and the rest one
   // workgroup per CU beside its factorisation, option 24: with the faster assembly it measured level to 0.5 % behind one launch at
   // N = 12288 .. 20480 and 0.8 % behind at N = 8192, profiles/NOTES_r06.md -- removed.)
-  HCK(launch_assemble(h->spec, E.s.theta_dev, h->buf.X_dev, h->n, h->buf.X_dev, h->n, E.K, h->buf.lda, h->np,
-                      h->np, 1, noise_form, s0, 0, h->diag_dev, E.lb()), "assemble");
+  if (h->deriv_npts)  // a gradient binding: the joint covariance of the values and the derivatives in the launch's place
+    HCK(deriv_assemble_train(h, E, noise_form, s0), "assemble (gradient binding)");
+  else
+    HCK(launch_assemble(h->spec, E.s.theta_dev, h->buf.X_dev, h->n, h->buf.X_dev, h->n, E.K, h->buf.lda, h->np,
+                        h->np, 1, noise_form, s0, 0, h->diag_dev, E.lb()), "assemble");
   if (prof) (void)hipEventRecord(h->ev[1], s0);
   HCK(cholesky(h, E, S, E.K, h->buf.lda, h->ntc + 1, h->ntc), "cholesky");
   if (prof) (void)hipEventRecord(h->ev[2], h->stream);
@@ -789,9 +792,12 @@ static int enqueue_gradient(mi_gp_handle* h, const Eval& E, Sched& S, bool prof)
   if (prof) (void)hipEventRecord(h->ev[6], h->stream);
   HCK(launch_trmv_upper(E.Z, ld, E.K + (long)h->np * ld, h->n, E.s.alpha_dev, h->stream, E.lb()), "trmv");
   // the final reduction writes the gradient straight into the handle's pinned host buffer (device-visible)
-  HCK(launch_grad_contract(h->spec, E.s.theta_dev, h->buf.X_dev, h->n, E.W, ld, E.s.alpha_dev, E.s.part_dev,
-                           E.s.grad_host, h->stream, E.lb(), E.s.lr_sync_dev + E.bt.nb, E.s.out_host + 5, h->eval_seq),
-      "grad_contract");
+  if (h->deriv_npts)  // a gradient binding: the joint covariance's contraction in the launch's place (the same publication)
+    HCK(deriv_grad_contract(h, E), "grad_contract (gradient binding)");
+  else
+    HCK(launch_grad_contract(h->spec, E.s.theta_dev, h->buf.X_dev, h->n, E.W, ld, E.s.alpha_dev, E.s.part_dev,
+                             E.s.grad_host, h->stream, E.lb(), E.s.lr_sync_dev + E.bt.nb, E.s.out_host + 5, h->eval_seq),
+        "grad_contract");
   if (prof) (void)hipEventRecord(h->ev[7], h->stream);
   return 0;
 }

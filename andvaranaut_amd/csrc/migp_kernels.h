@@ -517,6 +517,24 @@ hipError_t launch_sparse_hg(const double* Psi, const double* Binv, const double*
 hipError_t launch_sparse_predict_reduce(const double* A, const double* Bq, long ld, const double* cvec, int m, int mq, double kdiag,
                                         double noise, double* mean, double* var, hipStream_t stream);
 
+// ---------------------------------------------------------------- deriv_f64.hip (the joint GP over f and grad f, api_deriv.hip)
+constexpr int DERIV_MAX_D = 32;  // input dimensions the two kernels stage in one LDS block
+// The covariance of [f ; d_1 f ; .. ; d_d f] at two point sets (include/mi_gp_deriv.h has the blocks): q1 / q2 are the component
+// counts of the rows / columns, 1 (values only) or 1 + d; row a = c n1 + i is component c at point i of X1 (n1 x d), N1 = n1 q1 rows
+// and N2 = n2 q2 columns.  kid: KID_RBF or KID_MATERN52; theta = [l(d), kv, alpha, gv, jitter]; d <= DERIV_MAX_D.
+// launch_assemble's tiling and padding contract: sym = 1 the lower 64x64 tiles of the N1 x N1 matrix with the diagonal -- the
+// value rows' noise_form terms, the jitter alone on the derivative rows, extra_diag[N1] (optional) on both -- and the identity in
+// the padding; sym = 0 the full rectangle, zeros in the padding, no diagonal.  rows_pad / cols_pad: multiples of 64
+hipError_t launch_assemble_deriv(int kid, int d, const double* theta, const double* X1, int n1, int q1, const double* X2, int n2, int q2,
+                                 double* K, long ldk, int rows_pad, int cols_pad, int sym, int noise_form, hipStream_t stream,
+                                 const double* extra_diag = nullptr);
+// launch_grad_contract for that covariance over the N = n (1 + d) observations: grad[d + 4] = 1/2 sum_ab (alpha_a alpha_b - W_ab)
+// dK~_ab/dtheta from the LOWER triangle of W; part: [grad_contract_blocks(N)][d + 4] scratch; done / flag / seq as there.  No
+// atomics on the sums: per-tile partials, added in tile order
+hipError_t launch_grad_contract_deriv(int kid, int d, const double* theta, const double* X, int n, const double* W, long ldw,
+                                      const double* alpha, double* part, double* grad, hipStream_t stream, unsigned* done = nullptr,
+                                      double* flag = nullptr, double seq = 0.0);
+
 // ---------------------------------------------------------------- api_blocks.hip
 // X L^T = B in place for the tile columns [c0, c0 + w) of a lower factor L (the body of mi_gp_trsm_block)
 hipError_t trsm_blocks(const double* L, long ldl, const double* dinv, double* B, long ldb, int m, int c0, int w, hipStream_t st);

@@ -79,6 +79,28 @@ __device__ __forceinline__ void base_kernel_val_der(int kid, double r2, double a
   }
 }
 
+// k and its first three derivatives by s = r2 for the two families a joint GP over f and grad f is built from (deriv_f64.hip):
+// k and k1 are base_kernel_val_der's k and dk, from the same exp / sqrt sequences.
+//   RBF:        k_m = (-1/2)^m k
+//   Matern-5/2: k2 = 25/12 e^(-sqrt5 r), k3 = -(25 sqrt5 / 24) e^(-sqrt5 r) / r with r = sqrt(s + 1e-12) >= 1e-6; every use of k3
+//               multiplies it by four differences, so it is finite and its term vanishes at coincident points
+__device__ __forceinline__ void base_kernel_val_der3(int kid, double r2, double& k, double& k1, double& k2, double& k3) {
+  if (kid == KID_RBF) {
+    const double e = exp_nonpos(-0.5 * r2);
+    k = e;
+    k1 = -0.5 * e;
+    k2 = 0.25 * e;
+    k3 = -0.125 * e;
+    return;
+  }
+  const double r = sqrt_pos(r2 + 1e-12);
+  const double e = exp_nonpos(-1.0 * 2.23606797749979 * r);
+  k = (1.0 + 2.23606797749979 * r + 5.0 / 3.0 * (r * r)) * e;
+  k1 = -(5.0 / 6.0) * (1.0 + 2.23606797749979 * r) * e;
+  k2 = (25.0 / 12.0) * e;
+  k3 = -(25.0 * 2.23606797749979 / 24.0) * e / r;
+}
+
 // NK = 8 is the one instantiation for 5..8 components: it reads the count at run time, `RUNTIME_NK<NK> ? spec.nkern : NK`
 template <int NK>
 constexpr bool RUNTIME_NK = NK > 4;

@@ -18,6 +18,7 @@ from time import time as stopwatch
 import numpy as np
 
 from .backend import MiGP, parse_kernel
+from .deriv import KERNELS as DERIV_KERNELS, MAX_D as DERIV_MAX_D, MiDerivGP
 from .sparse import MAX_INDUCING, MiSparseGP, select_inducing
 from .consumers import ConsumersMixin
 from .lhc import latin_sample
@@ -118,6 +119,7 @@ class GPMCMC(ConsumersMixin):
         self.nsamp = 0
         self.x = np.empty((0, nx))
         self.y = np.empty((0, ny))
+        self.dy = None
         self.xc = copy.deepcopy(self.x)
         self.yc = copy.deepcopy(self.y)
         self.__conrev_check(xconrevs, yconrevs)
@@ -220,6 +222,7 @@ class GPMCMC(ConsumersMixin):
         xs, ys = self.__evaluate(xs, self.target)
         self.x = np.r_[self.x, xs]
         self.y = np.r_[self.y, ys]
+        self.dy = None  # (the target returns values alone: gradients come with set_data)
         self.nsamp = len(self.x)
         self.__mean_eval()
         self.__reconvert()
@@ -317,8 +320,12 @@ class GPMCMC(ConsumersMixin):
             else:
                 self.__release()  # (same hyper-parameters: _ensure_gp builds the handle on the extended data)
 
-    def set_data(self, x, y):
-        """gpmcmc.py:122-137 + lhc.py:113-131."""
+    def set_data(self, x, y, dy=None):
+        """gpmcmc.py:122-137 + lhc.py:113-131.  ``dy`` (optional): the (n, nx) raw gradients d y[:, 0] / d x of an adjoint solver,
+        for ``fit(gradients=True)``; without it the object behaves as it always has."""
+        if dy is not None and (not isinstance(dy, np.ndarray) or dy.dtype != "float64" or dy.shape != (len(x), self.nx)
+                               or not np.isfinite(dy).all()):
+            raise Exception("Error: Setting gradient data requires a finite 2d numpy array of float64 of shape (n, nx)")
         if not isinstance(x, np.ndarray) or len(x.shape) != 2 or x.dtype != "float64" or x.shape[1] != self.nx:
             raise Exception("Error: Setting data requires a 2d numpy array of float64 inputs")
         if not isinstance(y, np.ndarray) or len(y.shape) != 2 or y.dtype != "float64" or y.shape[1] != self.ny:
@@ -328,9 +335,46 @@ class GPMCMC(ConsumersMixin):
             if not all(x[:, i] >= intv[0]) or not all(x[:, i] <= intv[1]):
                 raise Exception("Error: provided x data must fit within provided input distribution ranges.")
         self.x, self.y, self.nsamp = x, y, len(x)
+        self.dy = dy
         self.__mean_eval()
         self.__reconvert()
         self.train = self.test = None
+
+    def converted_gradients(self, x=None, y=None, dy=None):
+        """d yc / d xc at the data (default: the stored x, y[:, 0], dy) by the chain rule through the installed transforms' own
+        derivatives: ``yconrevs[0].der`` at y over ``xconrevs[m].der`` at x[:, m], per point and input dimension."""
+        x = self.x if x is None else x
+        y = self.y[:, 0] if y is None else y
+        dy = self.dy if dy is None else dy
+        out = np.empty_like(dy)
+        dyc = np.asarray(self.yconrevs[0].der(y), dtype=np.float64)
+        for m in range(self.nx):
+            out[:, m] = dyc * dy[:, m] / np.asarray(self.xconrevs[m].der(x[:, m]), dtype=np.float64)
+        return np.ascontiguousarray(out)
+
+    def _gradient_fit_check(self, method, iwgp, cwgp, objective, trend, outputs, inducing):
+        """Every refusal of fit(gradients=True), raised before any device call."""
+        if getattr(self, "dy", None) is None:
+            raise ValueError("gradients=True needs gradient data: call set_data(x, y, dy) first")
+        if self.mean != self.zero_mean:
+            raise ValueError("gradients=True needs a zero mean function: the gradients of a non-zero mean are not known here")
+        if iwgp or cwgp:
+            raise ValueError("gradients=True has no form under iwgp / cwgp: the chain rule runs through fixed transforms")
+        if method not in ("map", "none"):
+            raise ValueError(f"gradients=True needs method='map' or 'none' (got {method!r}): there is no sampler on the gradient binding")
+        if objective != "lml":
+            raise ValueError(f"gradients=True needs objective='lml' (got {objective!r})")
+        if trend is not None:
+            raise ValueError(f"gradients=True has no form under trend={trend!r}")
+        if outputs != "first":
+            raise ValueError("gradients=True has no form under outputs='all': the gradients are those of y[:, 0]")
+        if inducing is not None:
+            raise ValueError("gradients=True has no form under inducing points: the sparse bound takes values alone")
+        if self.nkern != 1 or self.kernel not in DERIV_KERNELS:
+            raise ValueError(f"gradients=True needs one kernel out of {DERIV_KERNELS} (got {self.kernel!r}): no composite kernel, and "
+                             "a kernel that is twice differentiable")
+        if self.nx > DERIV_MAX_D:
+            raise ValueError(f"gradients=True needs nx <= {DERIV_MAX_D} (got {self.nx})")
 
     def del_samples(self, ndels=None, method="coarse_lhc", idx=None):
         """Drop samples (gpmcmc.py:57-72 + lhc.py:50-97): the ndels points nearest to a fresh Latin-hypercube
@@ -357,6 +401,8 @@ class GPMCMC(ConsumersMixin):
             self.x, self.y, self.xc, self.yc, self.ym = (a[mask] for a in (self.x, self.y, self.xc, self.yc, self.ym))
         else:
             raise Exception("Error: method must be one of 'coarse_lhc','random','specific'")
+        if getattr(self, "dy", None) is not None and len(self.dy) != len(self.x):
+            self.dy = None  # (the gradients no longer belong to the rows that are left)
         self.nsamp = len(self.x)
         self.train = self.test = None
 
@@ -383,6 +429,9 @@ class GPMCMC(ConsumersMixin):
         training split (``train_test``; refitted there with ``method``, 'none' = the stored hypers), predict the held-out
         points and return RMSE, mean absolute / percentage error and R^2 with the arrays ``returndat`` hands back."""
         self._no_all_outputs("test_stats")
+        grads = getattr(self, "gradients", False)  # (an object fitted on gradient observations is tested with them)
+        if grads:
+            self._gradient_fit_check(method, iwgp, cwgp, "lml", None, "first", None)
         trend = getattr(self, "trend", None)  # (an object fitted with a trend is tested with it)
         if trend is not None and (method not in ("none", "map") or iwgp or cwgp):
             raise ValueError(f"test_stats under trend={trend!r} needs method='none' or 'map' and neither iwgp nor cwgp")
@@ -391,7 +440,8 @@ class GPMCMC(ConsumersMixin):
         xtrain, xtest = self.x[self.train, :], self.x[self.test, :]
         ytrain, ytest = self.y[self.train, :], self.y[self.test, :]
         ymtrain, ymtest = self.ym[self.train, :], self.ym[self.test, :]
-        m, gp, hypers, _ = self.__fit(xtrain, ytrain - ymtrain, method, iwgp, cwgp, jitter, trend=trend)
+        m, gp, hypers, _ = self.__fit(xtrain, ytrain - ymtrain, method, iwgp, cwgp, jitter, trend=trend,
+                                      dy=self.dy[self.train, :] if grads else None, grad_noise=getattr(self, "grad_noise", None))
         try:
             xctest = np.column_stack([self.xconrevs[i].con(xtest[:, i]) for i in range(self.nx)])
             saved = self.m, self.hypers
@@ -655,6 +705,8 @@ class GPMCMC(ConsumersMixin):
         self.output_cov = "shared"
         self.inducing = None
         self.inducing_raw = None
+        self.gradients = False
+        self.grad_noise = None
 
     def __release(self):
         gp = getattr(self, "gp", None)
@@ -673,6 +725,10 @@ class GPMCMC(ConsumersMixin):
     def _ensure_gp(self):
         if self.gp is None and self.hypers is not None and self.m is not None:
             xin, yin = self._converted(self.x, self.y - self.ym)
+            if getattr(self, "gradients", False):  # a fit on gradient observations: the handle under its binding
+                self.gp = MiDerivGP(xin, yin, self.converted_gradients(), self.kernel, device=self.device,
+                                    grad_noise=getattr(self, "grad_noise", None))
+                return self.gp
             if getattr(self, "inducing", None) is not None:  # a sparse fit: the bound's object on the stored inducing points
                 self.gp = MiSparseGP(xin, yin, self.inducing, self.kernel, device=self.device)
                 return self.gp
@@ -690,7 +746,11 @@ class GPMCMC(ConsumersMixin):
             raise ValueError(f"{what} has no form under trend={self.trend!r}: fit without a trend to use it")
 
     def _no_sparse(self, what):
-        """Raised, before any device call, by what needs the dense factorisation after a fit on inducing points."""
+        """Raised, before any device call, by what needs the dense factorisation after a fit on inducing points -- or the plain
+        handle after a fit on gradient observations, whose binding serves fit, predict and test_stats alone."""
+        if getattr(self, "gradients", False):
+            raise ValueError(f"{what} has no form under a fit on gradient observations (gradients=True): fit with "
+                             "gradients=False to use it")
         if getattr(self, "inducing", None) is not None:
             raise ValueError(f"{what} has no form under a sparse fit (inducing={len(self.inducing)} points): it needs the dense "
                              "factorisation; fit with inducing=None to use it")
@@ -743,8 +803,15 @@ class GPMCMC(ConsumersMixin):
     # ------------------------------------------------------------------ fit
     def fit(self, method="map", return_data=False, iwgp=False, cwgp=False, jitter=1e-6, truncate=False,
             restarts=1, objective="lml", nfolds=10, fold_seed=None, trend=None, outputs="first", output_cov="shared",
-            inducing=None, inducing_seed=None, optimize_inducing=False, **kwargs):
-        """gpmcmc.py:175-182.  ``objective="loo"`` (with ``method="map"``) maximises the leave-one-out log predictive density
+            inducing=None, inducing_seed=None, optimize_inducing=False, gradients=False, grad_noise=None, **kwargs):
+        """gpmcmc.py:175-182.  ``gradients=True`` (with ``set_data(x, y, dy)``, ``method="map"`` or ``"none"``) conditions on the
+        gradients as well as the values: the n (1 + nx) observations of a joint GP over f and grad f (gradient-enhanced kriging),
+        the raw gradients converted by the chain rule through the installed transforms (``converted_gradients``).  It needs a
+        zero mean function, one RBF or Matern52 kernel, ``objective="lml"``, no trend, ``outputs="first"``, no inducing points
+        and neither iwgp nor cwgp; ``grad_noise`` is a fixed noise variance of the converted gradients (scalar or (n, nx); None:
+        the jitter alone).  The choice is part of the object's state (``self.gradients``): ``predict`` and ``test_stats`` follow
+        it, what needs the plain handle raises ValueError.
+        ``objective="loo"`` (with ``method="map"``) maximises the leave-one-out log predictive density
         sum_i log p(y_i | y_-i) plus the priors instead of the log marginal likelihood (Rasmussen & Williams section 5.4.2: the
         criterion for a misspecified kernel family); the hyper-parameters are stored as a MAP fit stores them.  It has no
         sampler (a pseudo-likelihood) and no warps (their data-side gradients are the marginal likelihood's).
@@ -787,6 +854,8 @@ class GPMCMC(ConsumersMixin):
         dF/dy, dF/dX and dF/dZ back onto the warp parameters, and ``self.inducing`` ends as those points under the fitted warps;
         what needs the dense factorisation (predict_joint, sample_posterior, log_predictive, cv_stats, predict_mean,
         sample_paths, predict_posterior, the resident paths of BO and inverse_opt) then raises ValueError."""
+        if gradients:
+            self._gradient_fit_check(method, iwgp, cwgp, objective, trend, outputs, inducing)
         Z, Zraw = self._inducing_points(inducing, inducing_seed, method, iwgp, cwgp, objective, trend, outputs, optimize_inducing)
         sparse_warps = Z is not None and bool(iwgp or cwgp)
         if outputs not in ("first", "all"):
@@ -817,14 +886,18 @@ class GPMCMC(ConsumersMixin):
         self.m, self.gp, self.hypers, data = self.__fit(self.x, self.y - self.ym, method, iwgp, cwgp, jitter,
                                                         truncate, restarts, objective=objective, cv=cv, trend=trend, outputs=outputs,
                                                         output_cov=output_cov, inducing=Z, optimize_inducing=optimize_inducing,
-                                                        inducing_raw=Zraw if sparse_warps else None, **kwargs)
+                                                        inducing_raw=Zraw if sparse_warps else None,
+                                                        dy=self.dy if gradients else None, grad_noise=grad_noise, **kwargs)
         # (under warps the stored points are the raw ones converted by the FITTED warps: what predict and a rebuilt object need)
         self.inducing = data["inducing"] if (optimize_inducing or sparse_warps) else Z
         self.inducing_raw = Zraw
         # what adaptive_sample(refit=True) fits again with
         self._fit_args = dict(method=method, iwgp=iwgp, cwgp=cwgp, jitter=jitter, truncate=truncate, restarts=restarts, objective=objective,
                               nfolds=nfolds, fold_seed=fold_seed, trend=trend, outputs=outputs, output_cov=output_cov, inducing=inducing,
-                              inducing_seed=inducing_seed, optimize_inducing=optimize_inducing, **kwargs)
+                              inducing_seed=inducing_seed, optimize_inducing=optimize_inducing, gradients=gradients,
+                              grad_noise=grad_noise, **kwargs)
+        self.gradients = bool(gradients)
+        self.grad_noise = grad_noise if gradients else None
         self.trend = trend
         self.outputs = outputs
         self.output_cov = output_cov
@@ -974,18 +1047,24 @@ class GPMCMC(ConsumersMixin):
         return likelihood
 
     def __fit(self, x, y, method, iwgp, cwgp, jitter=1e-6, truncate=False, restarts=1, objective="lml", cv=None, trend=None,
-              outputs="first", output_cov="shared", inducing=None, optimize_inducing=False, inducing_raw=None, **kwargs):
+              outputs="first", output_cov="shared", inducing=None, optimize_inducing=False, inducing_raw=None, dy=None,
+              grad_noise=None, **kwargs):
         n_i, n_pos, n_free = self._warp_sizes(iwgp, cwgp)
         model = HyperModel(self.nx, self.kerns, noise=self.noise, truncate=truncate, jitter=jitter, n_iwgp=n_i,
                            n_cwgp_pos=n_pos, n_cwgp=n_free)
         xin, yin = self._converted(x, y)
         self.__release()
         # (inducing points: gp.lml_grad is then the sparse bound and its gradient, gp.predict the sparse predictive)
-        gp = MiGP(xin, yin, self.kernel, device=self.device) if inducing is None else MiSparseGP(xin, yin, inducing, self.kernel,
-                                                                                                  device=self.device,
-                                                                                                  z_grad=bool(optimize_inducing)
-                                                                                                  or (inducing_raw is not None and iwgp),
-                                                                                                  data_grad=inducing_raw is not None)
+        if dy is not None:
+            # gradient observations: gp.lml_grad is then the joint GP's marginal likelihood, gp.predict the value's conditional
+            # (y is y - ym under the zero mean the fit insists on: the values the output transform's derivative is taken at)
+            gp = MiDerivGP(xin, yin, self.converted_gradients(x, y[:, 0], dy), self.kernel, device=self.device, grad_noise=grad_noise)
+        else:
+            gp = MiGP(xin, yin, self.kernel, device=self.device) if inducing is None else MiSparseGP(xin, yin, inducing, self.kernel,
+                                                                                                      device=self.device,
+                                                                                                      z_grad=bool(optimize_inducing)
+                                                                                                      or (inducing_raw is not None and iwgp),
+                                                                                                      data_grad=inducing_raw is not None)
         if trend is not None:
             gp.set_trend(trend)  # (gp.lml_grad then returns the trend's marginal likelihood; the stored handle keeps the trend)
         if outputs == "all":
